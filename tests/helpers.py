@@ -1,6 +1,7 @@
 """Shared test plumbing: golden fixtures, synthetic parameters, oracle runs, comparison helpers."""
 from __future__ import annotations
 
+import contextlib
 import functools
 import json
 import os
@@ -41,6 +42,21 @@ def case_images(meta):
     return synth_images(meta['B'], meta['size'], meta['size'], seed=1000 + meta['seed'])
 
 
+# torch-CPU's summation order (oneDNN blocking, work split) depends on the intra-op thread count, and the oracle's detections are
+# compared with the fixtures at 1e-6: the oracle runs with the thread count the fixtures were written with, on every host
+ORACLE_THREADS = 8
+
+
+@contextlib.contextmanager
+def oracle_threads():
+    prev = torch.get_num_threads()
+    torch.set_num_threads(ORACLE_THREADS)
+    try:
+        yield
+    finally:
+        torch.set_num_threads(prev)
+
+
 @functools.lru_cache(maxsize=None)
 def oracle_run(name):
     """(meta, arrays, raw head outputs, detections) of the CPU oracle on a golden case."""
@@ -48,7 +64,7 @@ def oracle_run(name):
     meta, arrays = load_golden(name)
     cfg = case_cfg(meta)
     sd = case_state_dict(meta)
-    with torch.no_grad():
+    with torch.no_grad(), oracle_threads():
         raw = O.forward_raw(case_images(meta), sd, cfg)
         dets = O.detect(raw, cfg, cross_class=bool(meta.get('cross_class', False)))
     return meta, arrays, cfg, sd, raw, dets

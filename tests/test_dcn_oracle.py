@@ -8,6 +8,7 @@
 """
 import math
 
+import pytest
 import torch
 import torch.nn.functional as F
 

@@ -7,8 +7,8 @@ grayscale / EXIF orientations 1-8, and files with the sampling ratios only oracl
 4:1:0, mixed chroma factors: libjpeg's h1v2 and replication upsamplers).  Integer / byte work: the bar is bit-exact.
 
 CPU (this file, no GPU):
-  * the oracle (oracle/jpeg_oracle.py) against every golden file, and live against Pillow on photographs when Pillow is
-    importable (it is in the build image);
+  * the oracle (oracle/jpeg_oracle.py) against every golden file, and live against Pillow on two photographs
+    (tests/golden/photos.npz) when Pillow is importable (it is in the build image);
   * the product's HOST half (csrc/jpeg_host.cpp through the C ABI): quantised coefficients and latched quantisation
     tables equal to the oracle's for every golden file; error codes for non-JPEG / unsupported / corrupt input;
   * the product's DEVICE arithmetic, executed on the host: tests/jpeg_emul.cpp (built here with g++) loops over blocks
@@ -16,7 +16,6 @@ CPU (this file, no GPU):
 GPU: tests/test_gpu_jpeg.py runs the kernels themselves through ymi_jpeg_reconstruct_bgr_u8 on the same files.
 """
 import ctypes as C
-import glob
 import io
 import os
 import subprocess
@@ -78,15 +77,12 @@ def test_oracle_matches_libjpeg_turbo_on_every_golden_file():
 
 
 def test_oracle_matches_pillow_live_on_photographs():
+    # tests/golden/photos.npz: the bytes of two camera JPEGs (matplotlib's grace_hopper.jpg sample, highlight.js's pojoaque.jpg)
     Image = pytest.importorskip('PIL.Image')
-    files = []
-    for pat in ('/usr/local/lib/python3*/dist-packages/matplotlib/mpl-data/sample_data/grace_hopper.jpg',
-                '/usr/share/javascript/highlight.js/styles/*.jpg'):
-        files += sorted(glob.glob(pat))
-    if not files:
-        pytest.skip('no photographs on this machine')
-    for f in files[:3]:
-        data = open(f, 'rb').read()
+    photos = np.load(os.path.join(HERE, 'golden', 'photos.npz'))
+    assert len(photos.files) >= 2
+    for f in sorted(photos.files):
+        data = photos[f].tobytes()
         ref = np.array(Image.open(io.BytesIO(data)).convert('RGB'))[..., ::-1]
         assert np.array_equal(J.imread_bgr(data, honour_exif=False), ref), f
 

@@ -3,7 +3,7 @@ by oracle/make_golden.py from /root/reference).  CPU only."""
 import pytest
 import torch
 
-from helpers import ALL_CASES, NOMASK_CASE, check_digest, load_golden, match_detections, oracle_run, unpack_masks
+from helpers import ALL_CASES, NOMASK_CASE, check_digest, load_golden, match_detections, oracle_run, oracle_threads, unpack_masks
 
 
 @pytest.mark.parametrize('name', ALL_CASES)
@@ -39,7 +39,8 @@ def test_postprocess_matches_reference(name):
         if n_post == 0:
             assert O.postprocess(dets[b], w, h, cfg, sd, score_threshold=thr) is None
             continue
-        classes, scores, boxes, masks, soft = O.postprocess(dets[b], w, h, cfg, sd, score_threshold=thr, return_soft=True)
+        with oracle_threads():
+            classes, scores, boxes, masks, soft = O.postprocess(dets[b], w, h, cfg, sd, score_threshold=thr, return_soft=True)
         assert classes.shape[0] == n_post
         assert torch.equal(classes, torch.from_numpy(arrays['post%d_class' % b]))
         assert torch.equal(boxes, torch.from_numpy(arrays['post%d_box' % b]))

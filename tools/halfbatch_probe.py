@@ -10,7 +10,6 @@ import os
 import sys
 import time
 
-os.environ.setdefault('GPU_MAX_HW_QUEUES', '8')
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

@@ -9,7 +9,6 @@ import json
 import os
 import sys
 
-os.environ.setdefault('GPU_MAX_HW_QUEUES', '8')
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

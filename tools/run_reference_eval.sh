@@ -4,7 +4,6 @@
 #   2. the engine bound through shim/                              -> the same evaluator, same dataset: mAP, FPS, COCO json
 # $1 = output dir.  Needs _scratch_reference/ (tools/stage_reference.sh).
 O=$1; N=${2:-24}
-export GPU_MAX_HW_QUEUES=8
 PY="python tools/run_reference_eval.py --out $O --images $N"
 export MIOPEN_FIND_MODE=FAST MIOPEN_USER_DB_PATH=/tmp/miopen_db MIOPEN_CUSTOM_CACHE_DIR=/tmp/miopen_cache
 timeout 420 $PY --who reference --mode gt || { echo "reference on GPU failed or too slow: falling back to the reference on the host CPU"; REFCPU="--cuda 0"; timeout 600 $PY --who reference --mode gt $REFCPU; }
