@@ -17,7 +17,7 @@
 extern "C" {
 #endif
 
-#define YMI_ABI_VERSION 8
+#define YMI_ABI_VERSION 9
 
 /* negative return codes (ymi_strerror) */
 #define YMI_EFORMAT (-4)       /* corrupt or truncated input stream (ymi_jpeg_*) */
@@ -315,6 +315,23 @@ typedef struct {
 } ymi_detect_desc;
 int ymi_detect_f32(const ymi_detect_desc *d, void *stream);
 
+/* -- Detect with traditional NMS (ABI 9; csrc/detect_greedy.hip) ------------------------------------------------------------------
+ * The reference's use_fast_nms = False mode (detection.py:80-108,182-228, utils/cython_nms.pyx): per class, every prior whose class
+ * score is > conf_thresh is a candidate (no top_k cap); boxes are decoded and scaled by box_scale (cfg.max_size); candidates are
+ * visited in descending score and a kept box suppresses every later one with overlap >= nms_thresh, overlap in pixels with the
+ * "+1" convention of cython_nms.pyx; the survivors of all classes are sorted by score and cut to max_det.  Returned boxes are
+ * (box * box_scale) / box_scale.  Ties (undefined in the reference): score desc, then class asc, then prior asc.
+ * Reads from `d`: conf, loc, coef, priors, B, P, C, D, conf_ld, conf_is_logits, max_det (<= 256), conf_thresh, nms_thresh, scores_t
+ * (workspace, [B,C-1,P]) and the outputs out_* (out_rec optional) with cap = max_det whatever `cross_class` says (the reference runs
+ * per-class greedy NMS with use_cross_class_nms too); top_k, keep, num_keep, maxsc, argmax, cand_score and cand_prior are unused.
+ * No host synchronisation, fixed launch shapes: graph-capturable. */
+typedef struct {
+  float box_scale;      /* cfg.max_size */
+  int32_t _pad0;
+  void *ws;             /* workspace of ymi_workspace_bytes(YMI_WS_DETECT_GREEDY, d) bytes, 16-byte aligned */
+} ymi_detect_greedy_ws;
+int ymi_detect_traditional_f32(const ymi_detect_desc *d, const ymi_detect_greedy_ws *g, void *stream);
+
 /* -- postprocess: mask assembly (layers/output_utils.py:69-99, layers/box_utils.py:327-373) */
 /* masks_lo[n,y,x] = crop(sigmoid(sum_k proto[y,x,k]*coef[n,k]), box[n]);  proto [ph,pw,D], coef [N,D], box [N,4] */
 int ymi_lincomb_crop_f32(const float *proto, const float *coef, const float *box, float *masks_lo,
@@ -532,7 +549,9 @@ enum {
   YMI_WS_DETECT_CAND = 9,       /* desc: ymi_detect_desc -> cand_score / cand_prior: [B,(C-1)*top_k] 4-byte elements EACH */
   YMI_WS_DETECT_REC = 10,       /* desc: ymi_detect_desc -> out_rec [B, 1 + cap*(6+D)] floats, cap = cross_class ? top_k : max_det */
   YMI_WS_AMAX_SLOT = 11,        /* desc: NULL            -> one magnitude-bound slot (x_amax / y_amax): YMI_AMAX_SUB * YMI_AMAX_STRIDE floats */
-  YMI_WS_RLE_COUNTS = 12        /* desc: ymi_rle_shape   -> ymi_mask_rle_f32's counts [N,cap] uint32 (cap = h*w + 1 covers every mask) */
+  YMI_WS_RLE_COUNTS = 12,       /* desc: ymi_rle_shape   -> ymi_mask_rle_f32's counts [N,cap] uint32 (cap = h*w + 1 covers every mask) */
+  YMI_WS_DETECT_GREEDY = 13     /* desc: ymi_detect_desc -> ymi_detect_greedy_ws.ws: boxes [B,P,4] floats, survivor keys / priors
+                                 * [B,(C-1)*max_det] 8 + 4 bytes, large-K candidate keys [B,C-1,P] 8 bytes; each part 256-byte aligned */
 };
 typedef struct { int32_t A, B; int64_t n; } ymi_mask_iou_shape;
 typedef struct { int32_t N, h, w, cap; } ymi_rle_shape;      /* cap <= 0: the safe capacity h*w + 1 */

@@ -10,7 +10,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libyolact_amd.so')
 
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 ACT_NONE, ACT_RELU, ACT_LEAKY01, ACT_TANH, ACT_SIGMOID = 0, 1, 2, 3, 4
 RES_NONE, RES_ADD, RES_BILINEAR = 0, 1, 2
@@ -114,6 +114,10 @@ class DetectDesc(C.Structure):
                 ('out_class', C.c_void_p), ('out_coef', C.c_void_p), ('out_prior', C.c_void_p), ('out_rec', C.c_void_p)]
 
 
+class DetectGreedyWs(C.Structure):
+    _fields_ = [('box_scale', C.c_float), ('_pad0', C.c_int32), ('ws', C.c_void_p)]
+
+
 class JpegInfo(C.Structure):
     _fields_ = [('width', C.c_int32), ('height', C.c_int32), ('ncomp', C.c_int32), ('progressive', C.c_int32),
                 ('orientation', C.c_int32), ('color', C.c_int32), ('out_width', C.c_int32), ('out_height', C.c_int32),
@@ -159,7 +163,7 @@ class RleShape(C.Structure):
 
 # ymi_workspace_bytes selectors (include/yolact_amd.h YMI_WS_*)
 (WS_WINO_V, WS_WINO_M, WS_SPLITK, WS_MASK_IOU, WS_JPEG_COEFS, WS_JPEG_PLANES, WS_DETECT_SCORES_T, WS_DETECT_PER_PRIOR,
- WS_DETECT_CAND, WS_DETECT_REC, WS_AMAX_SLOT, WS_RLE_COUNTS) = range(1, 13)
+ WS_DETECT_CAND, WS_DETECT_REC, WS_AMAX_SLOT, WS_RLE_COUNTS, WS_DETECT_GREEDY) = range(1, 14)
 
 EFORMAT, EUNSUPPORTED = -4, -5
 
@@ -182,6 +186,7 @@ SYMBOLS = [
     ('ymi_conv2d_direct_nhwc_f32', C.c_int, [_P, _P, _P, _P] + [_I] * 12 + [_P]),
     ('ymi_global_maxpool_nhwc_f32', C.c_int, [_P, _P, _I, _I, _I, _P]),
     ('ymi_detect_f32', C.c_int, [C.POINTER(DetectDesc), _P]),
+    ('ymi_detect_traditional_f32', C.c_int, [C.POINTER(DetectDesc), C.POINTER(DetectGreedyWs), _P]),
     ('ymi_lincomb_crop_f32', C.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     ('ymi_mask_upsample_f32', C.c_int, [_P, _P, _I, _I, _I, _I, _I, _F, _P]),
     ('ymi_lincomb_crop_batch_f32', C.c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),

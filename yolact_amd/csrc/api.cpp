@@ -4,6 +4,8 @@
 
 extern "C" {
 
+int64_t ymi_detect_greedy_layout(const ymi_detect_desc *d, int64_t off[4]);   // csrc/detect_greedy.hip
+
 int ymi_abi_version(void) { return YMI_ABI_VERSION; }
 
 const char *ymi_strerror(int code) {
@@ -57,6 +59,12 @@ int64_t ymi_workspace_bytes(int what, const void *desc) {
       if (what == YMI_WS_DETECT_CAND) return 4 * (int64_t)d->B * (d->C - 1) * d->top_k;
       const int64_t cap = d->cross_class ? d->top_k : d->max_det;
       return 4 * (int64_t)d->B * (1 + cap * (6 + d->D));
+    }
+    case YMI_WS_DETECT_GREEDY: {
+      const ymi_detect_desc *d = (const ymi_detect_desc *)desc;
+      if (d->B < 1 || d->P < 1 || d->C < 2 || d->max_det < 1) return -1;
+      int64_t off[4];
+      return ymi_detect_greedy_layout(d, off);
     }
     case YMI_WS_RLE_COUNTS: {
       const ymi_rle_shape *d = (const ymi_rle_shape *)desc;

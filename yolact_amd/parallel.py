@@ -219,7 +219,9 @@ def _cap_of(forward_device):
     det = getattr(net, 'detect', None)
     if det is None:
         raise RuntimeError('sharded_forward: an empty shard needs the record length; pass a bound Yolact.forward_device')
-    from .config import active_cfg
+    if hasattr(det, 'capacity'):
+        return int(det.capacity())
+    from .config import active_cfg                    # a stand-in without capacity(): the Fast NMS rule
     return det.top_k if det.use_cross_class_nms else int(active_cfg().max_num_detections)
 
 

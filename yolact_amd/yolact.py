@@ -193,8 +193,9 @@ class Yolact(nn.Module):
 
     def forward(self, x):
         """x: float32 [B,3,H,W], normalised RGB (resnet_transform, data/config.py:181-186)."""
-        self.detect._require_fast_nms()      # traditional NMS (the reference's Detect default) is not on the hot path: Fast NMS runs
-                                             # instead with one UserWarning per Detect object (YOLACT_AMD_STRICT_NMS=1: raise)
+        self.detect._require_fast_nms()      # traditional NMS (the reference's Detect default) runs on the device when
+                                             # detect.traditional_nms_on_device is set; otherwise Fast NMS runs instead with one
+                                             # UserWarning per Detect object (YOLACT_AMD_STRICT_NMS=1: raise)
         L.require_cuda(x, 'input batch')
         if x.dim() != 4 or x.shape[1] != 3:
             raise ValueError('expected [B,3,H,W], got %s' % (tuple(x.shape),))
@@ -310,7 +311,8 @@ class Yolact(nn.Module):
         batches (batch 1: the GPU idles between 10-20 us kernels while Python issues the next one).  The graph owns a
         static input and static outputs; every call copies x in and clones the results out, so returned tensors keep
         the eager path's lifetime rules."""
-        key = ('graph', tuple(x.shape), x.device, slot, bool(nomask))   # cfg.eval_mask_branch changes the captured launches
+        # cfg.eval_mask_branch and the NMS mode (fast, cross-class, greedy) change the captured launches
+        key = ('graph', tuple(x.shape), x.device, slot, bool(nomask), self.detect.nms_mode())
         # capture and replay touch the plan's shared arena / head buffers exactly like an eager run: same host lock, and
         # the device-side ordering against the previous run (possibly on another stream) through the plan's done-event
         with self._run_lock_for(x.device):
