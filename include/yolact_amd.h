@@ -376,6 +376,54 @@ int ymi_mask_upsample_bits(const float *masks_lo, int N, int ph, int pw, int h, 
  * fp32 exactly as box_utils.py:98-113 evaluates the float masks: bit-identical results. */
 int ymi_mask_iou_bits(const uint64_t *bits_a, const uint64_t *bits_b, int A, int B, long W64, int iscrowd, float *iou, void *stream);
 
+/* -- COCO box / mask AP (ABI 9, additive; csrc/ap_eval.hip) ---------------------------------------------------------------------
+ * eval.py's metric mode on device: prep_metrics' matching (eval.py:445-510) per image, APDataObject.get_ap (eval.py:533-581) per
+ * (type, threshold, class) at the end.  Types: 0 = box, 1 = mask; threshold k = (50 + 5 k) / 100, k < YMI_AP_NUM_THRESH.
+ *
+ * ymi_ap_match_f32: one image, one workgroup, no host synchronisation.  Inputs: N detections (classes int64, box / mask scores: the
+ * same pointer for single-score models), IoU [N,G] against the non-crowd GT and crowd IoU (iscrowd) [N,Gc] for both types, GT and
+ * crowd classes int32 (a class outside [0, num_classes) matches nothing; COCO crowds carry -1).  For each type t and each position
+ * p of the type's order (box: stable by -box score; mask: the box order stably re-sorted by -mask score) it writes record
+ * r = t * cap + base + p: rec_key = (class << 32) | 32-bit key ascending in -score (-0.0 == +0.0), rec_score = the type's score,
+ * rec_flags = bit k: true positive at threshold k, bit 16 + k: pushed at threshold k (clear = matched a crowd region and dropped).
+ * gt_count[c] += the image's non-crowd GT of class c.  N == 0 returns 0 without a launch: nothing is recorded, not even gt_count
+ * (eval.py:405-406).  Limits: N <= YMI_AP_MAX_DET, G and Gc <= YMI_AP_MAX_GT, base + N <= cap.
+ *
+ * ymi_ap_finalize_f64: sorted_key [2,M] = rec_key[t, :M] stably sorted per row, perm [2,M] their positions in the row.  Writes
+ * ap [2, YMI_AP_NUM_THRESH, num_classes] = get_ap() in fp64 (bit-equal to the reference) and empty [...] = is_empty(). */
+#define YMI_AP_NUM_THRESH 10
+#define YMI_AP_MAX_DET 1024
+#define YMI_AP_MAX_GT 2048
+typedef struct {
+  const int64_t *cls;           /* [N] */
+  const float *box_score;       /* [N] */
+  const float *mask_score;      /* [N] */
+  const float *box_iou;         /* [N,G] */
+  const float *mask_iou;        /* [N,G] */
+  const float *crowd_box_iou;   /* [N,Gc] */
+  const float *crowd_mask_iou;  /* [N,Gc] */
+  const int32_t *gt_cls;        /* [G] */
+  const int32_t *crowd_cls;     /* [Gc] */
+  int64_t *rec_key;             /* [2,cap] */
+  float *rec_score;             /* [2,cap] */
+  int32_t *rec_flags;           /* [2,cap] */
+  int64_t *gt_count;            /* [num_classes], accumulated */
+  int64_t base, cap;
+  int32_t N, G, Gc, num_classes;
+} ymi_ap_match_desc;
+typedef struct {
+  const int64_t *sorted_key;    /* [2,M] */
+  const int64_t *perm;          /* [2,M] */
+  const int32_t *rec_flags;     /* [2,cap] */
+  const int64_t *gt_count;      /* [num_classes] */
+  double *ap;                   /* [2,YMI_AP_NUM_THRESH,num_classes] */
+  int32_t *empty;               /* [2,YMI_AP_NUM_THRESH,num_classes] */
+  int64_t M, cap;
+  int32_t num_classes, _pad0;
+} ymi_ap_finalize_desc;
+int ymi_ap_match_f32(const ymi_ap_match_desc *d, void *stream);
+int ymi_ap_finalize_f64(const ymi_ap_finalize_desc *d, void *stream);
+
 /* -- prep_display, GPU half (eval.py:186-209,228): alpha-composite n instance masks onto a frame.
  * img [h,w,3] float32 0..255 (channel order as given), masks [n,h,w] float32, colors [n,3] float32 0..1 (device, same
  * channel order as img), out [h,w,3] uint8.  n = 0 just converts the frame. */

@@ -157,6 +157,23 @@ class MaskIouShape(C.Structure):
     _fields_ = [('A', C.c_int32), ('B', C.c_int32), ('n', C.c_int64)]
 
 
+class ApMatchDesc(C.Structure):
+    _fields_ = [('cls', C.c_void_p), ('box_score', C.c_void_p), ('mask_score', C.c_void_p), ('box_iou', C.c_void_p),
+                ('mask_iou', C.c_void_p), ('crowd_box_iou', C.c_void_p), ('crowd_mask_iou', C.c_void_p), ('gt_cls', C.c_void_p),
+                ('crowd_cls', C.c_void_p), ('rec_key', C.c_void_p), ('rec_score', C.c_void_p), ('rec_flags', C.c_void_p),
+                ('gt_count', C.c_void_p), ('base', C.c_int64), ('cap', C.c_int64),
+                ('N', C.c_int32), ('G', C.c_int32), ('Gc', C.c_int32), ('num_classes', C.c_int32)]
+
+
+class ApFinalizeDesc(C.Structure):
+    _fields_ = [('sorted_key', C.c_void_p), ('perm', C.c_void_p), ('rec_flags', C.c_void_p), ('gt_count', C.c_void_p),
+                ('ap', C.c_void_p), ('empty', C.c_void_p), ('M', C.c_int64), ('cap', C.c_int64),
+                ('num_classes', C.c_int32), ('_pad0', C.c_int32)]
+
+
+AP_NUM_THRESH, AP_MAX_DET, AP_MAX_GT = 10, 1024, 2048       # include/yolact_amd.h YMI_AP_*
+
+
 class RleShape(C.Structure):
     _fields_ = [('N', C.c_int32), ('h', C.c_int32), ('w', C.c_int32), ('cap', C.c_int32)]
 
@@ -199,6 +216,8 @@ SYMBOLS = [
     ('ymi_mask_bits_f32', C.c_int, [_P, _I, C.c_long, _P, _P]),
     ('ymi_mask_upsample_bits', C.c_int, [_P, _I, _I, _I, _I, _I, _F, _P, _P]),
     ('ymi_mask_iou_bits', C.c_int, [_P, _P, _I, _I, C.c_long, _I, _P, _P]),
+    ('ymi_ap_match_f32', C.c_int, [C.POINTER(ApMatchDesc), _P]),
+    ('ymi_ap_finalize_f64', C.c_int, [C.POINTER(ApFinalizeDesc), _P]),
     ('ymi_stem_pool_f32', C.c_int, [_P, _P]),
     ('ymi_pointwise_chain_f32', C.c_int, [_P, _P]),
     ('ymi_mask_rle_f32', C.c_int, [_P, _I, _I, _I, _P, _P, _I, _P]),
