@@ -21,9 +21,10 @@ def nchw(x_nhwc):
 
 def run_conv(x, weight, bias=None, bn=None, stride=1, pad=0, act=L.ACT_NONE, res=None, res_mode=L.RES_NONE,
              res_after_act=0, tile=L.TILE_AUTO, cin_pad=None, dcn_offmask=None, planes=True, split_k=0, om_layout=0, seg_bounds=None,
-             seg_acts=None):
+             seg_acts=None, mask_is_prob=0):
     """x: CPU NCHW tensor. Returns CPU NCHW output of the HIP conv.  `planes`: for bf16x3 tiles also hand the kernel the
-    pre-split filter planes (ymi_conv_desc.w_x3); False = both operands are split on the fly."""
+    pre-split filter planes (ymi_conv_desc.w_x3); False = both operands are split on the fly.  `mask_is_prob` (DCN only,
+    ymi_dcn_desc.mask_is_prob): 1 = the mask channels of dcn_offmask are the modulation itself, 0 = logits (sigmoid in the kernel)."""
     pk = Packed(weight, bias, bn, stride, pad, cin_pad, DEV)
     xn = nhwc(x)
     if cin_pad and cin_pad != xn.shape[-1]:
@@ -72,7 +73,7 @@ def run_conv(x, weight, bias=None, bn=None, stride=1, pad=0, act=L.ACT_NONE, res
         om = nhwc(dcn_offmask).to(DEV)
         dd = L.DcnDesc()
         dd.conv = d
-        dd.offmask, dd.ldo, dd.om_layout = om.data_ptr(), om.shape[3], om_layout
+        dd.offmask, dd.ldo, dd.om_layout, dd.mask_is_prob = om.data_ptr(), om.shape[3], om_layout, mask_is_prob
         L.check(L.lib().ymi_dcn_v2_forward_f32(C.byref(dd), s), 'dcn')
     else:
         L.check(L.lib().ymi_conv2d_nhwc_f32(C.byref(d), s), 'conv')

@@ -1,5 +1,7 @@
-"""Pins the CPU DCNv2 restatement (oracle/yolact_oracle.py::dcn_v2_forward).  The reference has no CPU DCN
-(external/DCNv2/src/cpu/dcn_v2_cpu.cpp:23) and its CUDA source does not build against this torch, so the pins are:
+"""Self-consistency checks of the CPU DCNv2 restatement (oracle/yolact_oracle.py::dcn_v2_forward).  The reference has no CPU DCN
+(external/DCNv2/src/cpu/dcn_v2_cpu.cpp:23) and its CUDA source does not build against this torch.  The oracle's pin is
+tests/test_dcn_kat_host.py (equality with the independent fp64 reference tests/dcn_ref.py on closed-form known answers, edge
+placements and random offsets); the checks here were written by the oracle's author and are kept as additional evidence:
   1. the reference's own known-answer test, external/DCNv2/test.py:32-67 (zero offsets, mask = sigmoid(0), identity
      centre-tap weights  =>  2 * DCN(x) == x, tolerance 1e-10 there);
   2. the derived KAT offset = 0, mask = 1  =>  F.conv2d (same test file's premise);

@@ -1,11 +1,12 @@
 """The DCNv2 forward path against the REFERENCE'S OWN kernel, compiled for gfx950 (oracle/build_ref.sh ->
 oracle/_ref/libdcn_v2_im2col_ref.so from /root/reference/external/DCNv2/src/cuda/dcn_v2_im2col_cuda.cu, no source copied).
 
-The reference ships no CPU DCN (src/cpu/dcn_v2_cpu.cpp:23), so until round 3 the DCN restatement in oracle/yolact_oracle.py
-was pinned only by zero-offset KATs and the `plus_r50` golden was circular for the DCN layers.  Here both the CPU oracle and
-the HIP kernel are compared with  columns = modulated_deformable_im2col_cuda(...)  (dcn_v2_im2col_cuda.cu:125-195, :329-352)
-followed by  out[b] = weight.view(Co, -1) @ columns[b] + bias  (dcn_v2_cuda.cu:123-163; the GEMM in fp64), with random
-NON-INTEGER offsets, many of them leaving the image, stride 1 and 2, batch > 1.
+Both the CPU oracle and the HIP kernel are compared with  columns = modulated_deformable_im2col_cuda(...)
+(dcn_v2_im2col_cuda.cu:125-195, :329-352) followed by  out[b] = weight.view(Co, -1) @ columns[b] + bias  (dcn_v2_cuda.cu:123-163;
+the GEMM in fp64), with random NON-INTEGER offsets, many of them leaving the image, stride 1 and 2, batch > 1.
+
+That kernel is built with stand-in headers and -D renames (oracle/build_ref.sh), so this file is additional evidence only.  The
+DCN pin is the fp64 known-answer suite: tests/dcn_ref.py, tests/test_dcn_kat_host.py and tests/test_gpu_dcn_kat.py.
 """
 import ctypes as C
 import os
