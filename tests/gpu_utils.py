@@ -101,14 +101,24 @@ def build_net(meta, device=DEV):
 
 
 def run_wino(x, weight, bias=None, bn=None, act=L.ACT_NONE, tile=L.TILE_AUTO, m=2, v_planes=False, up_from=None, up_relu=False,
-             proj=None):
+             proj=None, segs=None, proj_ldy=None):
     """3x3 / stride 1 / pad 1 conv through ymi_conv3x3_winograd_f32. x: CPU NCHW. Returns CPU NCHW.
-    up_from (CPU NCHW, half the size of x): the launch interpolates its input from it (ymi_wino_desc.x_up); `x` only gives the shape."""
+    up_from (CPU NCHW, half the size of x): the launch interpolates its input from it (ymi_wino_desc.x_up); `x` only gives the shape
+    and the input's magnitude bound — or, x None, the bound is that of up_from (what the plan hands the fused launch).
+    segs = [(n0, n1, act, rows, off), ...]: the segmented output transform (ymi_wino_desc.seg, the prediction heads): segment k
+    writes channels [n0, n1) of pixel p to row off + p of its own [B, rows, n1 - n0] tensor (NaN elsewhere); returns those tensors.
+    proj_ldy: row stride of the fused projection's output (default proj's Cout); the padding channels keep their NaN.
+    run_wino.last_amax = bounds reported for (x, y); run_wino.last_slots = all four slots (x, then one per output segment)."""
     from yolact_amd.engine import WinoPacked
     pk = Packed(weight, bias, bn, 1, 1, None, DEV)          # folded scale / bias
     wp = WinoPacked(weight, DEV, m)
-    xd = nhwc(x).to(DEV)
-    B, H, W, Cc = xd.shape
+    if x is None:
+        lo = up_from
+        xd = nhwc(lo).to(DEV)
+        B, H, W, Cc = xd.shape[0], 2 * lo.shape[2], 2 * lo.shape[3], xd.shape[3]
+    else:
+        xd = nhwc(x).to(DEV)
+        B, H, W, Cc = xd.shape
     Cout = weight.shape[0]
     T = B * ((H + m - 1) // m) * ((W + m - 1) // m)
     g = (m + 2) ** 2
@@ -122,12 +132,18 @@ def run_wino(x, weight, bias=None, bn=None, act=L.ACT_NONE, tile=L.TILE_AUTO, m=
     d.B, d.H, d.W, d.C, d.Cout, d.act, d.tile, d.m = B, H, W, Cc, Cout, act, tile, m
     if tile & L.TILE_X3:
         d.u_x3 = wp.u3().data_ptr()
-    amax = torch.zeros(2 * 1024, device=DEV)
+    amax = torch.zeros(4 * 1024, device=DEV)              # [0] bound of x, [1 ..]: what the launch reports (one slot per segment)
     L.check(L.lib().ymi_amax_f32(xd.data_ptr(), xd.numel(), amax.data_ptr(), L.stream_ptr()), 'amax')
     d.x_amax, d.y_amax = amax.data_ptr(), amax.data_ptr() + 4096
     if up_from is not None:
-        lo = nhwc(up_from).to(DEV)
+        lo = xd if x is None else nhwc(up_from).to(DEV)
         d.x, d.x_up, d.up_relu = None, lo.data_ptr(), 1 if up_relu else 0
+    ysegs = None
+    if segs is not None:
+        ysegs = [torch.full((B, rows, n1 - n0), float('nan'), device=DEV) for n0, n1, _, rows, _ in segs]
+        d.nseg, d.y = len(segs), None
+        for k, ((n0, n1, sact, rows, off), t) in enumerate(zip(segs, ysegs)):
+            d.seg[k] = L.ConvSeg(n0, n1, sact, n1 - n0, rows * (n1 - n0), t.data_ptr() + off * (n1 - n0) * 4)
     if tile & L.TILE_H2:
         up, uinv = wp.h2()
         d.u_h2, d.uinv_h2, d.v_planes = up.data_ptr(), uinv.data_ptr(), 1 if v_planes else 0
@@ -136,15 +152,19 @@ def run_wino(x, weight, bias=None, bn=None, act=L.ACT_NONE, tile=L.TILE_AUTO, m=
         pw, pb, pact = proj
         ppk = Packed(pw, pb, None, 1, 0, None, DEV)
         planes, sc2, _ = ppk.h2()
-        py = torch.full((B, H, W, pw.shape[0]), float('nan'), device=DEV)
+        ldy = proj_ldy or pw.shape[0]
+        py = torch.full((B, H, W, ldy), float('nan'), device=DEV)
         d.proj_w_h2, d.proj_scale_h2 = planes.data_ptr(), sc2.data_ptr()
         d.proj_bias = ppk.bias.data_ptr() if ppk.bias is not None else None
         d.proj_y, d.proj_y_amax = py.data_ptr(), amax.data_ptr() + 4096
-        d.proj_cout, d.proj_ldy, d.proj_act = pw.shape[0], pw.shape[0], pact
+        d.proj_cout, d.proj_ldy, d.proj_act = pw.shape[0], ldy, pact
         d.y = None
     L.check(L.lib().ymi_conv3x3_winograd_f32(C.byref(d), L.stream_ptr()), 'winograd')
     torch.cuda.synchronize()
-    run_wino.last_amax = amax.view(2, 1024).amax(1).cpu().tolist()
+    run_wino.last_slots = amax.view(4, 1024).amax(1).cpu().tolist()
+    run_wino.last_amax = run_wino.last_slots[:2]
+    if ysegs is not None:
+        return [t.cpu() for t in ysegs]
     if py is not None:
         assert torch.isnan(y).all()                   # the 3x3's own output was not touched
         return nchw(py.cpu())
