@@ -20,8 +20,11 @@ definition (eval.py:264-281 prep_benchmark: batch 1, postprocess, top-k `.cpu().
 Other BASELINE configs: `--config yolact_im700_config --batch 8` (configs[4], per-GPU share; size 700 is implied),
 `--config yolact_base_config --batch 16` (configs[2]), `--config yolact_plus_resnet50_config` (configs[3]).
 
-One JSON line on rank 0, with `roofline`, `box_calibration` and, at N=1, `cpu_baseline` (the CPU oracle = port of the reference's
-path, timed on this host's cores).
+One JSON line on rank 0.  A plain run does what the headline needs and nothing else: set-up, `box_calibration` (below; the timed
+steps have always started right after its load), the warm-up steps, the timed steps, --dump-outputs, and one serialised per-kernel
+pass whose GEMM time shares `dtype` quotes (< 1 s).  `--full` adds, after the timed steps: `gather_us`, the `strong_scaling` region,
+the `roofline` block (from that same per-kernel pass), `secondary` and, at N=1, `cpu_baseline` (the CPU oracle = port of the
+reference's path, timed on this host's cores; about 40 s); the --no-* switches below leave single parts out.
 
 `roofline` (round 5 layout): the TOP LEVEL is SURVEY 8(d)'s whole-path figure — `achieved` = algorithmic conv FLOPs of a step (118.28
 GFLOP per image) / the TIMED step on one GPU, `peak` = the matrix pipe at the precision used (fp16x2: 2500 / 3 = 833.3 TFLOP/s),
@@ -885,8 +888,10 @@ def main():
     ap.add_argument('--config', default=CONFIG, help='other BASELINE configs (parity-test cases; the metric is quoted on '
                     'the default yolact_resnet50_config)')
     ap.add_argument('--with-postprocess', action='store_true')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-secondary', action='store_true')
+    ap.add_argument('--full', action='store_true', help='also measure everything besides the headline: the record gather alone, the '
+                    'strong-scaling region, the roofline block, the secondary lines and the CPU baseline')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
+    ap.add_argument('--no-secondary', action='store_true', help='with --full: skip the secondary lines')
     ap.add_argument('--no-calibration', action='store_true', help='skip the box calibration block (csrc/calib.hip)')
     ap.add_argument('--no-pipeline', action='store_true', help='block on the host read of every step before launching the next')
     ap.add_argument('--exchange-after-join', action='store_true', help='A/B: enqueue the record gather + count read behind the whole '
@@ -894,11 +899,11 @@ def main():
     ap.add_argument('--prealloc-gb', type=int, default=0, help='experiment: reserve ONE allocation of this size in torch\'s caching '
                     'allocator before anything else is allocated, so that weights / activations / workspaces are carved from one mapping')
     ap.add_argument('--layers', action='store_true', help='also print the per-layer conv table to stderr')
-    ap.add_argument('--global-batch', type=int, default=0, help='strong scaling: a FIXED global batch split over the ranks '
+    ap.add_argument('--global-batch', type=int, default=0, help='with --full, strong scaling: a FIXED global batch split over the ranks '
                     '(parallel.shard_range; eval.py:630-634 splits one batch the same way).  Default: --batch, i.e. BASELINE '
                     'configs[1] at 8 GPUs = one image per GPU.  The weak-scaling region (--batch images per GPU) stays the headline value; '
                     'this second timed region is reported as `strong_scaling`')
-    ap.add_argument('--no-strong', action='store_true', help='skip the strong-scaling region')
+    ap.add_argument('--no-strong', action='store_true', help='with --full: skip the strong-scaling region')
     ap.add_argument('--dump-outputs', metavar='DIR', default=None,
                     help='after the timed steps, write what the last timed step computed (the detections up to each image\'s count, '
                          'the prototypes; with --with-postprocess also its results) as DIR/<name>.npy, float32 / float64, at most 64 MB '
@@ -1048,6 +1053,8 @@ def main():
         net.plan_for(x)                          # plan build (weight packing, table look-ups) is set-up, not a step
         if pipeline is not None:
             pipeline.warm(x)
+        # (not behind --full: on some boxes the timed steps run 1 - 2 % slower right after the calibration's load, so it stays
+        #  where every earlier headline was measured)
         calib = box_calibration(dev) if (rank == 0 and not args.no_calibration) else None
         run_steps(args.warmup)
         if have_pg:
@@ -1077,6 +1084,7 @@ def main():
             t = mine_t.clone()
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             dt = float(t.item())
+        if have_pg and args.full:
             # the collective alone: the record gather of the last step repeated 50 times, host-paired wall time
             # per call (launch + RCCL kernel + completion), after the timed region
             last = parallel.pack_records(net.forward_device(x))
@@ -1092,7 +1100,7 @@ def main():
         # (eval.py:630-634,661).  Rank r computes images shard_range(G, r, world) — an empty share enters the same gather — through
         # parallel.sharded_forward's per-rank-shard form; same barrier / synchronize / MAX-over-ranks timing as the weak region.
         strong = None
-        if not args.no_strong:
+        if args.full and not args.no_strong:
             G = args.global_batch or args.batch
             lo_s, hi_s = parallel.shard_range(G, rank, world)
             xs = synth_images(max(hi_s - lo_s, 1), size, size, seed=4321 + rank).to(dev)[:hi_s - lo_s]
@@ -1152,8 +1160,8 @@ def main():
             if got['n'] != args.batch * world:
                 raise SystemExit('bench.py: rank 0 gathered %d records, expected %d' % (got['n'], args.batch * world))
             plan = net.plan_for(x)
+            # the serialised per-kernel pass: `dtype` quotes its GEMM time shares; --full reports the roofline built from it
             rk, layers = roofline(net, x)
-            rf = whole_path_roofline(rk, dt / args.steps * 1e3, args.batch)
             imgs = args.batch * world * args.steps
             is_headline = args.config == CONFIG and size == 550 and args.batch == 8
             result = {
@@ -1184,27 +1192,30 @@ def main():
                 # steps).  Far below ms_per_step = the GPU sets the pace; close to it = this box's host does (box_calibration.host)
                 'host_issue_ms_per_step': {'median': round(sorted(issue_s)[len(issue_s) // 2] * 1e3, 3), 'max': round(max(issue_s) * 1e3, 3)},
                 'per_rank_ms_per_step': per_rank_ms,            # each rank's own clock over the timed region (value uses the MAX)
-                'gather_us': gather_us,                         # the record gather alone, host-paired, 50 back-to-back calls
                 'record_bytes_per_image': 4 * int(parallel.pack_records(net.forward_device(x)).shape[1]),
-                'roofline': rf,
-                # both scaling modes in one line: `value` / `scaling` above = weak (--batch images per GPU);
-                # strong_scaling = a fixed global batch split over the ranks
-                'strong_scaling': strong,
             }
+            if args.full:
+                result.update({
+                    'gather_us': gather_us,                     # the record gather alone, host-paired, 50 back-to-back calls
+                    'roofline': whole_path_roofline(rk, dt / args.steps * 1e3, args.batch),
+                    # both scaling modes in one line: `value` / `scaling` above = weak (--batch images per GPU);
+                    # strong_scaling = a fixed global batch split over the ranks
+                    'strong_scaling': strong,
+                })
+                result['roofline']['all_conv']['sustained_tflops_in_timed_region'] = round(
+                    rk['all_conv']['gflop_per_step'] / (dt / args.steps * 1e3), 2)
             if dumped is not None:
                 result['dumped_outputs'] = dumped
-            if rf['engine']['h2_share_of_time'] > 0:
+            if rk['engine']['h2_share_of_time'] > 0:
                 result['dtype'] = ('f32 (fp32 in / fp32 accumulate / fp32 out; %.0f %% of the GEMM time on fp16x2 tiles = every fp32 '
                                    'operand as two fp16 pieces by round to nearest (22 significant bits + 2 signs: exact for ~2/3 of '
                                    'all fp32 values, one fp32 ulp otherwise), 3 exact piece products per product on the fp16 matrix '
                                    'pipe; measured against fp64 the error is below the exact-fp32 MFMA kernel\'s own (fp32 accumulation '
-                                   'dominates both); the rest on exact-fp32 MFMA)' % (100 * rf['engine']['h2_share_of_time']))
-            elif rf['engine']['x3_share_of_time'] > 0:
+                                   'dominates both); the rest on exact-fp32 MFMA)' % (100 * rk['engine']['h2_share_of_time']))
+            elif rk['engine']['x3_share_of_time'] > 0:
                 result['dtype'] = ('f32 (fp32 in / fp32 accumulate; %.0f %% of the GEMM time on bf16x3 tiles = every fp32 product as 6 '
                                    'exact bf16 piece products on the bf16 matrix pipe, error class of one fp32 rounding; the rest '
-                                   'on exact-fp32 MFMA)' % (100 * rf['engine']['x3_share_of_time']))
-            result['roofline']['all_conv']['sustained_tflops_in_timed_region'] = round(
-                rf['all_conv']['gflop_per_step'] / (dt / args.steps * 1e3), 2)
+                                   'on exact-fp32 MFMA)' % (100 * rk['engine']['x3_share_of_time']))
             if calib is not None:
                 result['box_calibration'] = calib
                 # the same value had this box delivered 2000 TFLOP/s on the calibration loop (a typical MI355X under fp16 MFMA
@@ -1219,12 +1230,12 @@ def main():
                 for k, (ms, fl, kern) in layers.items():
                     print('%-22s %8.3f ms %8.2f GFLOP %7.1f TF/s  %s' % (k, ms, fl / 1e9, fl / ms / 1e9, kern),
                           file=sys.stderr)
-            if world == 1 and not args.no_secondary:
+            if args.full and world == 1 and not args.no_secondary:
                 result['secondary'] = secondary_lines(net, x, size, config=args.config)
                 if is_headline:
                     result['secondary']['outlier_plan'] = outlier_plan_line(dev, x, size, args.config)
                     result['secondary']['outlier_plan_guard_only'] = outlier_plan_line(dev, x, size, args.config, rebalance=False)
-        if rank == 0 and world == 1 and not args.no_cpu_baseline and args.config == CONFIG:
+        if rank == 0 and args.full and world == 1 and not args.no_cpu_baseline and args.config == CONFIG:
             result['cpu_baseline'] = cpu_baseline(sd, size, args.batch)
     if have_pg:
         dist.barrier()

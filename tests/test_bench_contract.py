@@ -1,9 +1,12 @@
-"""The bench.py output contract, checked on the committed result of the last GPU session (profiles/r06_bench.json): the
-keys the driver and the judge read, their types, and the internal consistency of the roofline and calibration blocks."""
+"""The bench.py output contract, checked on the committed result of the last GPU session (profiles/r06_bench.json, a run of
+what `--full` runs now): the keys the driver and the judge read, their types, and the internal consistency of the roofline and
+calibration blocks; on the GPU, what a plain run and a `--full` run print."""
 import json
 import os
 import subprocess
 import sys
+
+import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -199,3 +202,50 @@ def test_dump_outputs_writes_what_the_caller_receives(tmp_path):
 def test_dump_outputs_flag_is_offered():
     out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--help'], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0 and '--dump-outputs' in out.stdout
+
+
+def test_full_flag_is_offered():
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--help'], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0 and '--full' in out.stdout
+
+
+FULL_ONLY = ('gather_us', 'roofline', 'strong_scaling', 'secondary', 'cpu_baseline')
+
+
+def _bench_line(*extra):
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1'] + list(extra),
+                         capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = out.stdout.splitlines()
+    assert len(lines) == 1, out.stdout[-2000:]
+    return json.loads(lines[0])
+
+
+def _check_headline(b):
+    assert b['unit'] == 'images/s' and b['higher_is_better'] is True and b['steps'] == 3 and b['warmup'] == 1
+    assert b['metric'].startswith('images/sec (550x550, batch 8 per GPU)') and b['dtype'].startswith('f32 (')
+    assert abs(b['value'] - 8 * 3 / (b['ms_per_step'] * 3 / 1e3)) / b['value'] < 1e-3
+    assert b['rccl_ranks'] == 1 and b['gathered_records'] == 8 and b['config']['plan']['tune_misses'] == 0
+
+
+@pytest.mark.gpu
+def test_plain_run_prints_the_headline_only():
+    """`bench.py --gpus 1 --steps N --warmup W` without --full: the headline line (after the box calibration, as always), none of
+    the blocks that take runs of their own after the timed steps."""
+    b = _bench_line()
+    _check_headline(b)
+    assert not [k for k in FULL_ONLY if k in b] and b['box_calibration']['compute_units'] == 256
+
+
+@pytest.mark.gpu
+def test_full_run_adds_the_other_measurements():
+    """--full (here without the ~40 s CPU baseline): strong scaling, roofline and the secondary lines, as before."""
+    b = _bench_line('--full', '--no-cpu-baseline')
+    _check_headline(b)
+    for k in ('roofline', 'strong_scaling', 'box_calibration', 'secondary'):
+        assert isinstance(b[k], dict), k
+    assert 'cpu_baseline' not in b and b['gather_us'] > 0
+    r = b['roofline']
+    assert r['bound'] == 'mfma' and abs(r['achieved'] - r['all_conv']['gflop_per_step'] / b['ms_per_step']) / r['achieved'] < 2e-3
+    assert b['strong_scaling']['global_batch'] == 8 and b['box_calibration']['compute_units'] == 256
+    assert b['secondary']['outlier_plan']['layers_on_bf16x3'] == 0 and b['secondary']['sparse_regime']['value'] > 0

@@ -7,8 +7,8 @@
 #   tune         re-measure the shipped tile table (all plans);   tune1 = configs[1] + batch 1/2 only
 #   pytest       full `-m gpu` suite;   pytest:<expr> = `-k <expr>` (+ for spaces: pytest:stem+or+detect);   pytestf:<file> = one test file
 #   smoke        __graft_entry__.smoke()
-#   bench        driver-style bench line + per-layer table;   bench:<extra args> (use _ for spaces)
-#   configs      the other BASELINE configs (R101 B16, im700 B8, R50++ B8, Darknet53 B8), batch 1, exact-fp32-only
+#   bench        driver-style bench line with everything --full measures + per-layer table;   bench:<extra args> (use _ for spaces)
+#   configs      the other BASELINE configs (R101 B16, im700 B8, R50++ B8, Darknet53 B8), batch 1, exact-fp32-only (--full lines)
 #   stats        rocprofv3 --kernel-trace --stats of the bench command, single- and two-stream
 #   traffic      PMC FETCH_SIZE / WRITE_SIZE passes (separate runs, kernel-trace only) + tools/traffic_summary.py
 #   pmc          SQ busy / MFMA counters over the real plan (tools/pmc_summary.py)
@@ -49,17 +49,17 @@ for st in "$@"; do
     pytest) timeout ${PYTEST_TIMEOUT:-2400} python -m pytest tests -m gpu -q --timeout 600 -rA ${arg:+-k "$arg"} > $O/pytest.log 2>&1; grep -E "passed|failed" $O/pytest.log | tail -3; grep -E "^FAILED|^ERROR" $O/pytest.log | head -20 ;;
     pytestf) timeout 1200 python -m pytest tests/$arg -m gpu -q --timeout 600 -rA -s > $O/pytest_${arg%.py}.log 2>&1; grep -E "passed|failed" $O/pytest_${arg%.py}.log | tail -3; grep -E "^FAILED|^ERROR" $O/pytest_${arg%.py}.log | head -20 ;;
     smoke) timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; tail -1 $O/smoke.log ;;
-    bench) timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --layers $arg > $O/bench.json 2> $O/bench_layers.txt; head -1 $O/bench.json | cut -c1-600 ;;
+    bench) timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full --layers $arg > $O/bench.json 2> $O/bench_layers.txt; head -1 $O/bench.json | cut -c1-600 ;;
     configs)
-      timeout 300 python bench.py --batch 1 --steps 50 --no-cpu-baseline --no-secondary > $O/bench_b1.json 2>/dev/null; head -1 $O/bench_b1.json | cut -c1-200
+      timeout 300 python bench.py --batch 1 --steps 50 --full --no-cpu-baseline --no-secondary > $O/bench_b1.json 2>/dev/null; head -1 $O/bench_b1.json | cut -c1-200
       for c in "yolact_base_config 16 r101_b16" "yolact_im700_config 8 im700_b8" "yolact_darknet53_config 8 darknet_b8" "yolact_plus_base_config 8 plus_base_b8" "yolact_im400_config 8 im400_b8"; do
         set -- $c
-        timeout 400 python bench.py --config $1 --batch $2 --steps 10 --no-cpu-baseline --no-secondary > $O/bench_$3.json 2>/dev/null; head -1 $O/bench_$3.json | cut -c1-200
+        timeout 400 python bench.py --config $1 --batch $2 --steps 10 --full --no-cpu-baseline --no-secondary > $O/bench_$3.json 2>/dev/null; head -1 $O/bench_$3.json | cut -c1-200
       done
       # configs[3] WITH its secondary lines (YOLACT++: batched FastMaskIoUNet in postprocess_batch, the reference FPS definition with two score tensors)
-      timeout 500 python bench.py --config yolact_plus_resnet50_config --batch 8 --steps 10 --no-cpu-baseline > $O/bench_plus_b8.json 2>/dev/null; head -1 $O/bench_plus_b8.json | cut -c1-200
-      YOLACT_AMD_SPLIT=0 timeout 400 python bench.py --no-cpu-baseline --no-secondary > $O/bench_fp32only.json 2>/dev/null; head -1 $O/bench_fp32only.json | cut -c1-200
-      YOLACT_AMD_SPLIT=1 timeout 400 python bench.py --no-cpu-baseline --no-secondary > $O/bench_bf16x3.json 2>/dev/null; head -1 $O/bench_bf16x3.json | cut -c1-200 ;;
+      timeout 500 python bench.py --config yolact_plus_resnet50_config --batch 8 --steps 10 --full --no-cpu-baseline > $O/bench_plus_b8.json 2>/dev/null; head -1 $O/bench_plus_b8.json | cut -c1-200
+      YOLACT_AMD_SPLIT=0 timeout 400 python bench.py --full --no-cpu-baseline --no-secondary > $O/bench_fp32only.json 2>/dev/null; head -1 $O/bench_fp32only.json | cut -c1-200
+      YOLACT_AMD_SPLIT=1 timeout 400 python bench.py --full --no-cpu-baseline --no-secondary > $O/bench_bf16x3.json 2>/dev/null; head -1 $O/bench_bf16x3.json | cut -c1-200 ;;
     ab) # same-box A/B of the three arithmetics on configs[1] (box-to-box spread is larger than most single changes)
       for m in 2 1 0 2 1; do YOLACT_AMD_SPLIT=$m timeout 300 python bench.py --steps 30 --no-cpu-baseline --no-secondary 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.readline()); print('SPLIT=$m', d['value'], d['ms_per_step'], d['config']['plan']['tune_misses'])"; done | tee $O/ab.txt ;;
     stats)
@@ -191,7 +191,7 @@ PY
         YOLACT_AMD_OM_PAD=$1 YOLACT_AMD_OM_INTERLEAVE=$2 timeout 400 $PB 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.readline()); print('OM_PAD=$1 OM_INTERLEAVE=$2', d['value'], d['ms_per_step'], 'misses', d['config']['plan']['tune_misses'])"
       done | tee $O/plus_ab.txt ;;
     tuneplus) timeout 900 python tools/make_tune_table.py --only configs3_plus_b8 plus_b1 --copy-to $O/gfx950.json > $O/tune.log 2>&1; grep -E "plan|table" $O/tune.log | cut -c1-160
-      timeout 400 python bench.py --config yolact_plus_resnet50_config --batch 8 --steps 20 --no-cpu-baseline --no-secondary --layers > $O/bench_plus_b8.json 2> $O/plus_layers.txt; head -1 $O/bench_plus_b8.json | cut -c1-200; grep -E "offmask|dcn" $O/plus_layers.txt | cut -c1-150 ;;
+      timeout 400 python bench.py --config yolact_plus_resnet50_config --batch 8 --steps 20 --full --no-cpu-baseline --no-secondary --layers > $O/bench_plus_b8.json 2> $O/plus_layers.txt; head -1 $O/bench_plus_b8.json | cut -c1-200; grep -E "offmask|dcn" $O/plus_layers.txt | cut -c1-150 ;;
     dcnref) timeout 600 python -m pytest tests/test_gpu_dcn_reference.py -m gpu -q -rA -s > $O/dcnref.log 2>&1; tail -5 $O/dcnref.log ;;
     evalpy) timeout 1500 bash tools/run_reference_eval.sh $O > $O/evalpy.log 2>&1; tail -30 $O/evalpy.log ;;
     py) n=$(basename ${arg%% *} .py); k=0; while [ -e $O/$n$k.log ]; do k=$((k+1)); done
