@@ -21,15 +21,35 @@ def nchw(x_nhwc):
 
 def run_conv(x, weight, bias=None, bn=None, stride=1, pad=0, act=L.ACT_NONE, res=None, res_mode=L.RES_NONE,
              res_after_act=0, tile=L.TILE_AUTO, cin_pad=None, dcn_offmask=None, planes=True, split_k=0, om_layout=0, seg_bounds=None,
-             seg_acts=None, mask_is_prob=0):
+             seg_acts=None, mask_is_prob=0, res_ld=None, ldx=None, x_fill=float('nan'), segs=None, bands=None, twice=False,
+             x_dev=None):
     """x: CPU NCHW tensor. Returns CPU NCHW output of the HIP conv.  `planes`: for bf16x3 tiles also hand the kernel the
     pre-split filter planes (ymi_conv_desc.w_x3); False = both operands are split on the fly.  `mask_is_prob` (DCN only,
-    ymi_dcn_desc.mask_is_prob): 1 = the mask channels of dcn_offmask are the modulation itself, 0 = logits (sigmoid in the kernel)."""
+    ymi_dcn_desc.mask_is_prob): 1 = the mask channels of dcn_offmask are the modulation itself, 0 = logits (sigmoid in the kernel).
+    Conv only (tests/test_gpu_conv_kat.py):
+      res_ld: channel stride of the residual's pixels (> its channels: the padding holds NaN);
+      ldx: channel stride of the input's pixels (> Cin: channels [Cin, ldx) hold x_fill; the bound x_amax is that of [0, Cin));
+      segs = [(n0, n1, act, rows, off), ...]: segment k writes channels [n0, n1) of output pixel p to row off + p of its own
+        NaN-filled [B, rows, n1 - n0] tensor (the prediction heads' level-concatenated tensors); returns those tensors, or with
+        `bands` one list per segment of [B, (r1 - r0) Wo, n1 - n0] pieces;
+      bands = [(r0, r1), ...]: return only these output rows (dense: one NCHW tensor per band);
+      twice: launch a second time; run_conv.last_identical = both launches wrote the same bits;
+      x_dev: x already on the device as NHWC (cin_pad applied): reused instead of copying x again.
+    Also set: run_conv.last_slots (the four bound slots: x, then one per output segment), run_conv.last_out_amax (max|y| of
+    each segment over what it owns, on the device), run_conv.last_finite (every owned output finite), run_conv.last_sentinels
+    (segs: the rows outside [off, off + Ho Wo) kept their NaN)."""
     pk = Packed(weight, bias, bn, stride, pad, cin_pad, DEV)
-    xn = nhwc(x)
-    if cin_pad and cin_pad != xn.shape[-1]:
-        xn = torch.nn.functional.pad(xn, (0, cin_pad - xn.shape[-1]))
-    xd = xn.to(DEV)
+    if x_dev is not None:
+        xd = x_dev
+    else:
+        xn = nhwc(x)
+        if cin_pad and cin_pad != xn.shape[-1]:
+            xn = torch.nn.functional.pad(xn, (0, cin_pad - xn.shape[-1]))
+        xd = xn.to(DEV)
+    xclean = xd
+    if ldx is not None and ldx != xd.shape[-1]:
+        assert ldx > xd.shape[-1] and dcn_offmask is None
+        xd = torch.nn.functional.pad(xd, (0, ldx - xd.shape[-1]), value=x_fill).contiguous()
     B, H, W, Cx = xd.shape
     Ho, Wo = out_size(H, pk.kh, stride, pad), out_size(W, pk.kw, stride, pad)
     y = torch.full((B, Ho, Wo, pk.Cout), float('nan'), device=DEV)
@@ -44,6 +64,8 @@ def run_conv(x, weight, bias=None, bn=None, stride=1, pad=0, act=L.ACT_NONE, res
     rd = None
     if res is not None:
         rd = nhwc(res).to(DEV)
+        if res_ld is not None and res_ld != rd.shape[3]:
+            rd = torch.nn.functional.pad(rd, (0, res_ld - rd.shape[3]), value=float('nan')).contiguous()
         d.res, d.res_ld, d.res_H, d.res_W = rd.data_ptr(), rd.shape[3], rd.shape[1], rd.shape[2]
     d.nseg, d.tile = 1, tile
     d.seg[0] = L.ConvSeg(0, pk.Cout, act, pk.Cout, Ho * Wo * pk.Cout, y.data_ptr())
@@ -55,11 +77,17 @@ def run_conv(x, weight, bias=None, bn=None, stride=1, pad=0, act=L.ACT_NONE, res
         for i, ys in enumerate(ysegs):
             w_ = edges[i + 1] - edges[i]
             d.seg[i] = L.ConvSeg(edges[i], edges[i + 1], (seg_acts or [act] * 3)[i], w_, Ho * Wo * w_, ys.data_ptr())
+    if segs is not None:      # caller-shaped segment tensors [B, rows, n1 - n0], written from row `off` on
+        assert seg_bounds is None
+        ysegs = [torch.full((B, rows, n1 - n0), float('nan'), device=DEV) for n0, n1, _, rows, _ in segs]
+        d.nseg = len(segs)
+        for i, ((n0, n1, sact, rows, off), t) in enumerate(zip(segs, ysegs)):
+            d.seg[i] = L.ConvSeg(n0, n1, sact, n1 - n0, rows * (n1 - n0), t.data_ptr() + off * (n1 - n0) * 4)
     if (tile & L.TILE_X3) and planes and dcn_offmask is None:
         d.w_x3 = pk.w3().data_ptr()
     amax = torch.zeros(4 * 1024, device=DEV)          # magnitude-bound slots (16 sub-slots, 64 floats apart): [0] bound of x
                                                       # (ymi_amax_f32), [1] what the launch reports for y ([1 .. 3]: per output segment)
-    L.check(L.lib().ymi_amax_f32(xd.data_ptr(), xd.numel(), amax.data_ptr(), L.stream_ptr()), 'amax')
+    L.check(L.lib().ymi_amax_f32(xclean.data_ptr(), xclean.numel(), amax.data_ptr(), L.stream_ptr()), 'amax')
     d.x_amax, d.y_amax = amax.data_ptr(), amax.data_ptr() + 4096
     if tile & L.TILE_H2:
         hp, sc2, winv = pk.h2()
@@ -78,10 +106,36 @@ def run_conv(x, weight, bias=None, bn=None, stride=1, pad=0, act=L.ACT_NONE, res
     else:
         L.check(L.lib().ymi_conv2d_nhwc_f32(C.byref(d), s), 'conv')
     torch.cuda.synchronize()
-    run_conv.last_amax = amax.view(4, 1024).amax(1).cpu().tolist()
-    if ysegs is not None:
-        return [nchw(t.cpu()) for t in ysegs]
-    return nchw(y.cpu())
+    run_conv.last_slots = amax.view(4, 1024).amax(1).cpu().tolist()
+    run_conv.last_amax = run_conv.last_slots
+    if segs is None and bands is None and not twice:
+        if ysegs is not None:
+            return [nchw(t.cpu()) for t in ysegs]
+        return nchw(y.cpu())
+    outs = ysegs if ysegs is not None else [y]
+    if segs is not None:
+        owned = [t[:, off:off + Ho * Wo] for t, (_, _, _, _, off) in zip(ysegs, segs)]
+        run_conv.last_sentinels = [bool(torch.isnan(t[:, :off]).all() and torch.isnan(t[:, off + Ho * Wo:]).all())
+                                   for t, (_, _, _, _, off) in zip(ysegs, segs)]
+    else:
+        owned = outs
+    run_conv.last_finite = all(bool(torch.isfinite(t).all()) for t in owned)
+    run_conv.last_out_amax = [t.abs().max().item() for t in owned]
+    if twice:
+        first = [t.clone() for t in outs]
+        for t in outs:
+            t.fill_(float('nan'))
+        L.check(L.lib().ymi_conv2d_nhwc_f32(C.byref(d), s), 'conv')
+        torch.cuda.synchronize()
+        run_conv.last_identical = all(torch.equal(a.nan_to_num(7.0), b.nan_to_num(7.0)) for a, b in zip(first, outs))
+        del first
+    rows_ = bands if bands is not None else [(0, Ho)]
+    if segs is not None:
+        return [[t[:, r0 * Wo:r1 * Wo].cpu() for r0, r1 in rows_] for t in owned]
+    pieces = [[nchw(t[:, r0:r1].cpu()) for r0, r1 in rows_] for t in outs]
+    if ysegs is None:
+        return pieces[0] if bands is not None else nchw(y.cpu())
+    return pieces if bands is not None else [nchw(t.cpu()) for t in ysegs]
 
 
 def rel_err(a, b):
@@ -171,9 +225,10 @@ def run_wino(x, weight, bias=None, bn=None, act=L.ACT_NONE, tile=L.TILE_AUTO, m=
     return nchw(y.cpu())
 
 
-def run_chain(x, wa, ba, res, wb=None, bb=None, act_a=L.ACT_RELU, act_b=L.ACT_RELU):
+def run_chain(x, wa, ba, res, wb=None, bb=None, act_a=L.ACT_RELU, act_b=L.ACT_RELU, in_place=False):
     """ymi_pointwise_chain_f32 on CPU tensors: x [M,P], wa [4P,P], res [M,4P] or None, wb [P,4P] or None (P = 64: csrc/chain.hip;
-    P = 128 / 256: csrc/chain2.hip).  Returns (y [M,4P], z [M,P] or None) on the CPU; run_chain.last_amax = the bounds reported for (y, z)."""
+    P = 128 / 256: csrc/chain2.hip).  Returns (y [M,4P], z [M,P] or None) on the CPU; run_chain.last_amax = the bounds reported for (y, z).
+    in_place: z is written over x (same base, same row stride: the one overlap include/yolact_amd.h allows)."""
     M, P = x.shape
     pa = Packed(wa.view(4 * P, P, 1, 1), ba, None, 1, 0, None, DEV)
     pla, sca, _ = pa.h2()
@@ -199,7 +254,7 @@ def run_chain(x, wa, ba, res, wb=None, bb=None, act_a=L.ACT_RELU, act_b=L.ACT_RE
         pb = Packed(wb.view(P, 4 * P, 1, 1), bb, None, 1, 0, None, DEV)
         plb, scb, _ = pb.h2()
         keep = (pb, plb, scb)
-        z = torch.full((M, P), float('nan'), device=DEV)
+        z = xd if in_place else torch.full((M, P), float('nan'), device=DEV)
         d.z, d.ldz, d.w_b_h2, d.scale_b_h2, d.cout_pad_b = z.data_ptr(), P, plb.data_ptr(), scb.data_ptr(), pb.CoutPad
         d.bias_b = pb.bias.data_ptr() if pb.bias is not None else None
     L.check(L.lib().ymi_pointwise_chain_f32(C.byref(d), L.stream_ptr()), 'chain')

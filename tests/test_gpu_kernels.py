@@ -467,6 +467,58 @@ def test_pointwise_chain_matches_fp64(M, mode):
         assert z is None
 
 
+def _shipped_chains():
+    """(kind, B, H, W) of every 'chain' / 'chain1' entry of yolact_amd/tune/gfx950.json the plan installs (decision 1)."""
+    import ast
+    import json
+    import os
+    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'yolact_amd', 'tune', 'gfx950.json')
+    with open(path) as f:
+        entries = json.load(f)['entries']
+    out = []
+    for k, v in sorted(entries.items()):
+        kind, _, rest = k.partition('(')
+        if kind in ('chain', 'chain1') and v[0] == 1:
+            key = ast.literal_eval('(' + rest.partition('|')[0])
+            if len(key) == 3:                                 # (P = 64: csrc/chain.hip)
+                out.append((kind,) + key)
+    return out
+
+
+SHIPPED_CHAINS = _shipped_chains()
+
+
+def test_shipped_chain_entries_reach_the_largest_batch():
+    assert len(SHIPPED_CHAINS) >= 10 and max(b * h * w for _, b, h, w in SHIPPED_CHAINS) == 16 * 138 * 138, SHIPPED_CHAINS
+    assert {k for k, _, _, _ in SHIPPED_CHAINS} == {'chain', 'chain1'}
+
+
+@pytest.mark.parametrize('kind,B,H,W', SHIPPED_CHAINS, ids=['%s-B%d-%dx%d' % c for c in SHIPPED_CHAINS])
+def test_pointwise_chain_at_shipped_sizes(kind, B, H, W):
+    """test_pointwise_chain_matches_fp64 at every M = B H W the table installs the chain for (up to 16 * 138^2 = 304 704 rows):
+    'chain' with z written over x in place (the aliasing the plan produces), 'chain1' = conv3 alone; same bars."""
+    from gpu_utils import run_chain
+    M = B * H * W
+    g = _g(910 + B + H)
+    x = torch.randn(M, 64, generator=g) * 3
+    wa = torch.randn(256, 64, generator=g) / 8
+    ba = torch.randn(256, generator=g) * 0.3
+    res = torch.randn(M, 256, generator=g) * 2
+    pair = kind == 'chain'
+    wb = torch.randn(64, 256, generator=g) / 16 if pair else None
+    bb = torch.randn(64, generator=g) * 0.1 if pair else None
+    yr = torch.relu(x.double() @ wa.double().t() + ba.double() + res.double())
+    y, z = run_chain(x, wa, ba, res, wb, bb, in_place=pair)
+    assert ((y.double() - yr).abs().max() / yr.abs().max()).item() < 5e-7
+    assert abs(run_chain.last_amax[0] - yr.abs().max().item()) <= 1e-6 * yr.abs().max().item()
+    if pair:
+        zr = torch.relu(yr @ wb.double().t() + bb.double())
+        assert ((z.double() - zr).abs().max() / zr.abs().max()).item() < 1e-6
+        assert abs(run_chain.last_amax[1] - zr.abs().max().item()) <= 2e-6 * zr.abs().max().item()
+    else:
+        assert z is None
+
+
 PATCH2_ALL = [t | L.TILE_H2 | L.TILE_DCNP for t in sorted(L.PATCH2_TILES)]          # csrc/patch2.hip: 256- / 192-pixel tiles
 
 
