@@ -479,6 +479,38 @@ int ymi_jpeg_decode_coefs(const uint8_t *data, size_t n, int16_t *coefs, int64_t
 int ymi_jpeg_reconstruct_bgr_u8(const ymi_jpeg_info *info, const int16_t *coefs, const uint16_t *qt, uint8_t *planes_ws,
                                 uint8_t *out, void *stream);
 
+/* -- the image write of evalimage / evalimages / evalvideo (eval.py: `cv2.imwrite(save_path, img_numpy)`) ------------------
+ * cv2.imwrite of a .jpg = libjpeg with its defaults at quality 95: baseline sequential (SOF0), one interleaved scan, JFIF APP0,
+ * the T.81 Annex K quantisation tables scaled by the quality, the four Annex K Huffman tables, YCbCr 4:2:0, ISLOW forward DCT.
+ * Marker order SOI, APP0, DQT, DQT, SOF0, DHT x 4, SOS, data, EOI.  Here the whole encoder runs on the GPU (colour conversion,
+ * edge padding, chroma downsampling, FDCT, quantisation, Huffman coding, byte stuffing: csrc/jpeg_enc.hip); the host writes
+ * only the fixed-size header.  The stream is BYTE-EQUAL to libjpeg-turbo's through Pillow (`Image.save(.., 'JPEG', quality=q,
+ * subsampling=2 or 0)`; tests/test_jpeg_encode.py, tests/test_gpu_jpeg_encode.py); cv2 calls the same library with the same
+ * defaults but is not available to check against.
+ *   file = [ymi_jpeg_write_header bytes] + [out[0 .. *out_len) of ymi_jpeg_encode_bgr_u8]       (the EOI marker is in `out`)
+ * No host synchronisation, no device allocation, everything on `stream`. */
+enum { YMI_JPEG_SUB_444 = 0, YMI_JPEG_SUB_420 = 2 };      /* Pillow's `subsampling` numbering; 4:2:0 is libjpeg's default */
+#define YMI_JPEG_HEADER_BYTES 623
+typedef struct ymi_jpeg_enc_desc {
+  const uint8_t *img;    /* device, uint8 BGR [h,w,3] (display.prep_display's frame, ymi_jpeg_reconstruct_bgr_u8's output) */
+  int32_t h, w;          /* 1..65535 each */
+  int64_t row_stride;    /* bytes between rows, >= 3 * w; pixels inside a row are packed */
+  int32_t quality;       /* 1..100 (cv2.imwrite's default: 95) */
+  int32_t subsampling;   /* YMI_JPEG_SUB_420 / YMI_JPEG_SUB_444 */
+  uint8_t *out;          /* device: entropy-coded scan (byte-stuffed, padded with 1-bits) followed by the EOI marker */
+  int64_t out_capacity;  /* bytes at `out`, >= ymi_workspace_bytes(YMI_WS_JPEG_ENC_OUT, desc) (YMI_EARG otherwise) */
+  int64_t *out_len;      /* device: bytes written to `out` */
+  void *ws;              /* device workspace of ymi_workspace_bytes(YMI_WS_JPEG_ENC, desc) bytes, 256-byte aligned */
+} ymi_jpeg_enc_desc;
+/* HOST.  SOI .. SOS (YMI_JPEG_HEADER_BYTES bytes) into out [cap]; *n = bytes written.  YMI_EARG: h / w outside 1..65535,
+ * quality outside 1..100, unknown subsampling, cap too small. */
+int ymi_jpeg_write_header(int h, int w, int quality, int subsampling, uint8_t *out, size_t cap, size_t *n);
+/* HOST.  The two quantisation tables header and kernels both use: qt [2][64] (luminance, chrominance), natural order. */
+int ymi_jpeg_enc_qtables(int quality, uint16_t *qt);
+/* DEVICE.  YMI_EARG: the cases of ymi_jpeg_write_header, row_stride < 3 * w, out_capacity below the bound; YMI_ENULL: a
+ * null img / out / out_len / ws. */
+int ymi_jpeg_encode_bgr_u8(const ymi_jpeg_enc_desc *d, void *stream);
+
 /* -- COCODetection.pull_item's ground-truth masks (data/coco.py:144-148: `self.coco.annToMask(obj)`), HOST code -----------
  * pycocotools maskApi.c restated (pycocotools is an unpinned pip dependency of the reference, environment.yml:30):
  * rleFrPoly / rleFrString / rleDecode.  Every call ORs its region into mask [h,w] uint8 ROW-major (0/1), so a polygon
@@ -598,8 +630,11 @@ enum {
   YMI_WS_DETECT_REC = 10,       /* desc: ymi_detect_desc -> out_rec [B, 1 + cap*(6+D)] floats, cap = cross_class ? top_k : max_det */
   YMI_WS_AMAX_SLOT = 11,        /* desc: NULL            -> one magnitude-bound slot (x_amax / y_amax): YMI_AMAX_SUB * YMI_AMAX_STRIDE floats */
   YMI_WS_RLE_COUNTS = 12,       /* desc: ymi_rle_shape   -> ymi_mask_rle_f32's counts [N,cap] uint32 (cap = h*w + 1 covers every mask) */
-  YMI_WS_DETECT_GREEDY = 13     /* desc: ymi_detect_desc -> ymi_detect_greedy_ws.ws: boxes [B,P,4] floats, survivor keys / priors
+  YMI_WS_DETECT_GREEDY = 13,    /* desc: ymi_detect_desc -> ymi_detect_greedy_ws.ws: boxes [B,P,4] floats, survivor keys / priors
                                  * [B,(C-1)*max_det] 8 + 4 bytes, large-K candidate keys [B,C-1,P] 8 bytes; each part 256-byte aligned */
+  YMI_WS_JPEG_ENC = 14,         /* desc: ymi_jpeg_enc_desc, h / w / subsampling read -> ymi_jpeg_enc_desc.ws */
+  YMI_WS_JPEG_ENC_OUT = 15      /* desc: ymi_jpeg_enc_desc, same fields -> least ymi_jpeg_enc_desc.out_capacity: an upper bound of
+                                 * the stuffed scan + EOI for ANY pixels (416 bytes per coded 8x8 block + 2) */
 };
 typedef struct { int32_t A, B; int64_t n; } ymi_mask_iou_shape;
 typedef struct { int32_t N, h, w, cap; } ymi_rle_shape;      /* cap <= 0: the safe capacity h*w + 1 */

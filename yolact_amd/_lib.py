@@ -126,6 +126,16 @@ class JpegInfo(C.Structure):
                 ('coef_count', C.c_int64), ('plane_bytes', C.c_int64)]
 
 
+class JpegEncDesc(C.Structure):
+    _fields_ = [('img', C.c_void_p), ('h', C.c_int32), ('w', C.c_int32), ('row_stride', C.c_int64), ('quality', C.c_int32),
+                ('subsampling', C.c_int32), ('out', C.c_void_p), ('out_capacity', C.c_int64), ('out_len', C.c_void_p),
+                ('ws', C.c_void_p)]
+
+
+JPEG_SUB_444, JPEG_SUB_420 = 0, 2       # include/yolact_amd.h YMI_JPEG_SUB_*
+JPEG_HEADER_BYTES = 623
+
+
 class ChainDesc(C.Structure):
     _fields_ = [('x', C.c_void_p), ('res', C.c_void_p), ('y', C.c_void_p), ('z', C.c_void_p),
                 ('w_a_h2', C.c_void_p), ('w_b_h2', C.c_void_p),
@@ -180,7 +190,7 @@ class RleShape(C.Structure):
 
 # ymi_workspace_bytes selectors (include/yolact_amd.h YMI_WS_*)
 (WS_WINO_V, WS_WINO_M, WS_SPLITK, WS_MASK_IOU, WS_JPEG_COEFS, WS_JPEG_PLANES, WS_DETECT_SCORES_T, WS_DETECT_PER_PRIOR,
- WS_DETECT_CAND, WS_DETECT_REC, WS_AMAX_SLOT, WS_RLE_COUNTS, WS_DETECT_GREEDY) = range(1, 14)
+ WS_DETECT_CAND, WS_DETECT_REC, WS_AMAX_SLOT, WS_RLE_COUNTS, WS_DETECT_GREEDY, WS_JPEG_ENC, WS_JPEG_ENC_OUT) = range(1, 16)
 
 EFORMAT, EUNSUPPORTED = -4, -5
 
@@ -227,6 +237,9 @@ SYMBOLS = [
     ('ymi_jpeg_parse', C.c_int, [_P, C.c_size_t, C.POINTER(JpegInfo)]),
     ('ymi_jpeg_decode_coefs', C.c_int, [_P, C.c_size_t, _P, C.c_int64, _P, C.POINTER(JpegInfo)]),
     ('ymi_jpeg_reconstruct_bgr_u8', C.c_int, [C.POINTER(JpegInfo), _P, _P, _P, _P, _P]),
+    ('ymi_jpeg_write_header', C.c_int, [_I, _I, _I, _I, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ('ymi_jpeg_enc_qtables', C.c_int, [_I, _P]),
+    ('ymi_jpeg_encode_bgr_u8', C.c_int, [C.POINTER(JpegEncDesc), _P]),
     ('ymi_coco_poly_fill_u8', C.c_int, [_P, _I, _I, _I, _P]),
     ('ymi_coco_rle_fill_u8', C.c_int, [_P, C.c_long, _I, _I, _P]),
     ('ymi_coco_rle_string_fill_u8', C.c_int, [C.c_char_p, C.c_long, _I, _I, _P]),

@@ -5,6 +5,7 @@
 extern "C" {
 
 int64_t ymi_detect_greedy_layout(const ymi_detect_desc *d, int64_t off[4]);   // csrc/detect_greedy.hip
+int64_t ymi_jpeg_enc_layout(int h, int w, int sub, int64_t off[8], int64_t *out_bound);   // csrc/jpeg_enc_host.cpp
 
 int ymi_abi_version(void) { return YMI_ABI_VERSION; }
 
@@ -65,6 +66,13 @@ int64_t ymi_workspace_bytes(int what, const void *desc) {
       if (d->B < 1 || d->P < 1 || d->C < 2 || d->max_det < 1) return -1;
       int64_t off[4];
       return ymi_detect_greedy_layout(d, off);
+    }
+    case YMI_WS_JPEG_ENC:
+    case YMI_WS_JPEG_ENC_OUT: {
+      const ymi_jpeg_enc_desc *d = (const ymi_jpeg_enc_desc *)desc;
+      int64_t off[8], bound = 0;
+      const int64_t total = ymi_jpeg_enc_layout(d->h, d->w, d->subsampling, off, &bound);
+      return total < 0 ? total : (what == YMI_WS_JPEG_ENC ? total : bound);
     }
     case YMI_WS_RLE_COUNTS: {
       const ymi_rle_shape *d = (const ymi_rle_shape *)desc;
