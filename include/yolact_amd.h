@@ -535,6 +535,32 @@ typedef struct {
 } ymi_dcn_desc;
 int ymi_dcn_v2_forward_f32(const ymi_dcn_desc *d, void *stream);
 
+/* -- DCNv2 backward (dcn_v2.py:35-52, dcn_v2_cuda.cu:174-335, dcn_v2_im2col_cuda.cu:197-327; csrc/dcn_bwd.hip; additive at ABI 9) --
+ * Gradients of y = ymi_dcn_v2_forward_f32(x, offmask, w, bias) for the geometry the forward takes: 3x3, pad 1, dilation 1, one
+ * deformable group, square stride 1 or 2, Cin % 32 == 0 (the caller pads with zero channels), mask_is_prob = 1 (channels 18.. of
+ * offmask ARE the modulation; a caller that holds logits applies the sigmoid and its derivative itself).  Everything is fp32 NHWC.
+ * One pointer per gradient; NULL = not wanted, and its work is skipped (all NULL: no launch).  The call zeroes what it
+ * accumulates into, so outputs need no initialisation.  No workspace: neither the column tensor nor its gradient is
+ * materialised.  gx, gw, gbias (and g_offset / g_mask on small maps) are sums of fp32 atomics: fp32-class accurate, NOT
+ * bit-reproducible from run to run.  YMI_EARG: kernel / pad / dilation / groups / stride / mask_is_prob / om_layout outside the
+ * above; YMI_ESHAPE: Cin % 32, ldx < Cin or ldx % 4, ldo < 27, Ho / Wo not the convolution's output size, a tensor of 2^31
+ * elements or more, x / gy / gx not 16-byte aligned; YMI_ENULL: a needed input is NULL.  No error path launches anything. */
+typedef struct ymi_dcn_bwd_desc {
+  const float *x;        /* [B,H,W,ldx] the forward's input */
+  const float *offmask;  /* [B,Ho,Wo,ldo] the forward's offsets and modulation, ldo / om_layout as in ymi_dcn_desc */
+  const float *w;        /* fp32 filters [Cout][3][3][Cin] (UNPACKED: k = (3i + j) * Cin + c); may be NULL when only gw / gbias are wanted */
+  const float *gy;       /* [B,Ho,Wo,Cout] dense: gradient of the output */
+  float *gx;             /* [B,H,W,ldx] (channels >= Cin are zeroed) */
+  float *g_offset;       /* [B,Ho,Wo,18] dense: channel 2k = d/d dh_k, 2k+1 = d/d dw_k (whatever om_layout the input has) */
+  float *g_mask;         /* [B,Ho,Wo,9] dense: d/d mu_k */
+  float *gw;             /* [Cout][3][3][Cin], the layout of w */
+  float *gbias;          /* [Cout] */
+  int32_t B, H, W, Cin, ldx, Ho, Wo, Cout;
+  int32_t kh, kw, stride, pad, dilation, deformable_groups;
+  int32_t ldo, mask_is_prob, om_layout, _pad0;
+} ymi_dcn_bwd_desc;
+int ymi_dcn_v2_backward_f32(const ymi_dcn_bwd_desc *d, void *stream);
+
 /* -- ResNet stem in one launch (backbone.py:126-133 + the layout change of yolact.py:564) ---------------------------------
  * x [B,3,H,W] NCHW fp32 (the normalised image) -> conv 7x7 / 2 / pad 3 (3 -> 64) + folded BN + ReLU -> max-pool 3x3 / 2 / pad 1
  * -> y [B,Hp,Wp,64] NHWC fp32, Hp = ((H - 1) / 2 + 1 - 1) / 2 + 1.  The 64-channel stem output stays in LDS (csrc/stem.hip).

@@ -101,6 +101,17 @@ class DcnDesc(C.Structure):
                 ('om_layout', C.c_int32), ('_pad1', C.c_int32)]
 
 
+class DcnBwdDesc(C.Structure):
+    """include/yolact_amd.h ymi_dcn_bwd_desc."""
+    _fields_ = [('x', C.c_void_p), ('offmask', C.c_void_p), ('w', C.c_void_p), ('gy', C.c_void_p),
+                ('gx', C.c_void_p), ('g_offset', C.c_void_p), ('g_mask', C.c_void_p), ('gw', C.c_void_p), ('gbias', C.c_void_p),
+                ('B', C.c_int32), ('H', C.c_int32), ('W', C.c_int32), ('Cin', C.c_int32), ('ldx', C.c_int32),
+                ('Ho', C.c_int32), ('Wo', C.c_int32), ('Cout', C.c_int32),
+                ('kh', C.c_int32), ('kw', C.c_int32), ('stride', C.c_int32), ('pad', C.c_int32), ('dilation', C.c_int32),
+                ('deformable_groups', C.c_int32),
+                ('ldo', C.c_int32), ('mask_is_prob', C.c_int32), ('om_layout', C.c_int32), ('_pad0', C.c_int32)]
+
+
 class DetectDesc(C.Structure):
     _fields_ = [('conf', C.c_void_p), ('loc', C.c_void_p), ('coef', C.c_void_p), ('priors', C.c_void_p),
                 ('B', C.c_int32), ('P', C.c_int32), ('C', C.c_int32), ('D', C.c_int32),
@@ -220,6 +231,7 @@ SYMBOLS = [
     ('ymi_mask_upsample_batch_f32', C.c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P]),
     ('ymi_boxes_to_pixels', C.c_int, [_P, _P, _I, _I, _I, _P]),
     ('ymi_dcn_v2_forward_f32', C.c_int, [C.POINTER(DcnDesc), _P]),
+    ('ymi_dcn_v2_backward_f32', C.c_int, [C.POINTER(DcnBwdDesc), _P]),
     ('ymi_composite_masks_u8', C.c_int, [_P, _P, _P, _I, _I, _I, _F, _P, _P]),
     ('ymi_mask_iou_f32', C.c_int, [_P, _P, _I, _I, C.c_long, _I, _P, _P, _P]),
     ('ymi_jaccard_f32', C.c_int, [_P, _P, _I, _I, _I, _P, _P]),

@@ -7,9 +7,18 @@
 Inside a `Yolact` plan these modules are parameter containers (the engine reads weight / bias / conv_offset_mask once and
 emits `ymi_dcn_v2_forward_f32` ops, yolact_amd/engine.py).  Called on their own — the reference's own known-answer test does
 that (external/DCNv2/test.py:32-67) — they run the same C-ABI entry points: NCHW fp32 in, NCHW fp32 out, like
-`_ext.dcn_v2_forward` (src/vision.cpp:3-8, src/dcn_v2.h:9-39).  Forward only (the reference's backward is training code, out of
-scope); what YOLACT++ constructs is supported: 3x3, padding 1, dilation 1, one deformable group (backbone.py:22-26).
-PyTorch does the layout changes (NCHW <-> NHWC) and owns the memory; all arithmetic is in the HIP library.
+`_ext.dcn_v2_forward` (src/vision.cpp:3-8, src/dcn_v2.h:9-39).  What YOLACT++ constructs is supported: 3x3, padding 1,
+dilation 1, one deformable group (backbone.py:22-26).  PyTorch does the layout changes (NCHW <-> NHWC) and owns the memory; the
+arithmetic of the deformable op is in the HIP library.
+
+Differentiable: the deformable op itself.  When grad mode is on and one of input / offset / mask / weight / bias requires grad,
+`dcn_v2_conv` is a `torch.autograd.Function` (the reference's `_DCNv2`, dcn_v2.py:16-52) whose backward is
+`ymi_dcn_v2_backward_f32` (csrc/dcn_bwd.hip): gradients for all five tensors, once differentiable (no double backward), sums of
+fp32 atomics (fp32-class accurate, not bit-reproducible from run to run).  The forward VALUE is the one the no-grad path
+computes, bit for bit.  `DCN.forward` under grad mode is the reference's formulation (dcn_v2.py:118-128): conv_offset_mask, chunk
+and sigmoid through PyTorch (whose autograd carries their gradients), then the deformable op.  Not differentiable: anything
+inside an engine plan (there the modules are parameter containers), `Yolact` in training mode (it raises), CPU tensors (they
+raise: there is no CPU path).
 """
 from __future__ import annotations
 
@@ -17,6 +26,7 @@ import ctypes as C
 
 import torch
 import torch.nn as nn
+from torch.autograd.function import once_differentiable
 from torch.nn.modules.utils import _pair
 
 from . import _lib as L
@@ -106,18 +116,71 @@ def _dcn_launch(xd, om, mask_is_prob, pk, Ho, Wo):
     return y
 
 
-def dcn_v2_conv(input, offset, mask, weight, bias, stride, padding, dilation, deformable_groups):
-    """`_DCNv2.apply` (dcn_v2.py:16-52), forward only: input [B,Cin,H,W], offset [B,18,Ho,Wo] (channel 2k = dh_k, 2k+1 = dw_k),
-    mask [B,9,Ho,Wo] = the modulation itself (callers pass torch.sigmoid(...), dcn_v2.py:122), weight [Cout,Cin,3,3], bias
-    [Cout] -> [B,Cout,Ho,Wo]."""
+def _weight_nhwc_padded(weight, cpad):
+    """[Cout,Cin,3,3] -> fp32 [Cout,3,3,cpad] (the unpacked layout of ymi_dcn_bwd_desc.w)."""
+    return _nhwc_padded(weight, cpad)
+
+
+def _dcn_backward(input, offset, mask, weight, gy, st, needs):
+    """ymi_dcn_v2_backward_f32 for NCHW / OIHW tensors; needs = (input, offset, mask, weight, bias) wanted.  Returns the five
+    gradients (None where not wanted) in NCHW / OIHW fp32."""
     from .engine import out_size
-    L.require_cuda(input, 'dcn_v2_conv input')
-    st = _check_geometry(weight, stride, padding, dilation, deformable_groups)
+    B, Cin, H, W = input.shape
+    Cout = weight.shape[0]
+    Ho, Wo = out_size(H, 3, st, 1), out_size(W, 3, st, 1)
+    dev = input.device
+    with torch.cuda.device(dev), torch.no_grad():
+        cin_p = _ceil(Cin, 32)
+        xd = _nhwc_padded(input, cin_p)
+        om = torch.cat([offset, mask], 1).detach().to(torch.float32).permute(0, 2, 3, 1).contiguous()
+        wd = _weight_nhwc_padded(weight, cin_p)
+        gyd = gy.detach().to(torch.float32).permute(0, 2, 3, 1).contiguous()
+        new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
+        gx = new(B, H, W, cin_p) if needs[0] else None
+        go = new(B, Ho, Wo, 18) if needs[1] else None
+        gm = new(B, Ho, Wo, 9) if needs[2] else None
+        gw = new(Cout, 3, 3, cin_p) if needs[3] else None
+        gb = new(Cout) if needs[4] else None
+        d = L.DcnBwdDesc()
+        d.x, d.offmask, d.w, d.gy = xd.data_ptr(), om.data_ptr(), wd.data_ptr(), gyd.data_ptr()
+        for name, t in (('gx', gx), ('g_offset', go), ('g_mask', gm), ('gw', gw), ('gbias', gb)):
+            setattr(d, name, None if t is None else t.data_ptr())
+        d.B, d.H, d.W, d.Cin, d.ldx, d.Ho, d.Wo, d.Cout = B, H, W, cin_p, cin_p, Ho, Wo, Cout
+        d.kh, d.kw, d.stride, d.pad, d.dilation, d.deformable_groups = 3, 3, st, 1, 1, 1
+        d.ldo, d.mask_is_prob, d.om_layout = 27, 1, 0
+        L.check(L.lib().ymi_dcn_v2_backward_f32(C.byref(d), L.stream_ptr()), 'ymi_dcn_v2_backward_f32')
+        nchw = lambda t: None if t is None else t.permute(0, 3, 1, 2).contiguous()
+        return (nchw(None if gx is None else gx[..., :Cin]), nchw(go), nchw(gm), nchw(None if gw is None else gw[..., :Cin]), gb)
+
+
+class _DCNv2Function(torch.autograd.Function):
+    """`_DCNv2` (dcn_v2.py:16-52).  `value`: None, or a callable that computes the forward value another (equivalent) way —
+    DCN.forward passes its two-launch no-grad path, so that the module's output does not depend on grad mode."""
+
+    @staticmethod
+    def forward(ctx, input, offset, mask, weight, bias, stride, padding, dilation, deformable_groups, value=None):
+        ctx.st = _check_geometry(weight, stride, padding, dilation, deformable_groups)
+        ctx.save_for_backward(input, offset, mask, weight, bias)
+        if value is not None:
+            return value()
+        return _dcn_forward(input, offset, mask, weight, bias, ctx.st)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        input, offset, mask, weight, bias = ctx.saved_tensors
+        needs = tuple(ctx.needs_input_grad[:5])
+        needs = needs[:4] + (needs[4] and bias is not None,)
+        grads = _dcn_backward(input, offset, mask, weight, gy, ctx.st, needs)
+        like = (input, offset, mask, weight, bias)
+        grads = tuple(None if g is None else g.to(t.dtype) for g, t in zip(grads, like))
+        return grads + (None, None, None, None, None)
+
+
+def _dcn_forward(input, offset, mask, weight, bias, st):
+    from .engine import out_size
     B, Cin, H, W = input.shape
     Ho, Wo = out_size(H, 3, st, 1), out_size(W, 3, st, 1)
-    if tuple(offset.shape) != (B, 18, Ho, Wo) or tuple(mask.shape) != (B, 9, Ho, Wo) or weight.shape[1] != Cin:
-        raise ValueError('dcn_v2_conv: offset %s / mask %s / weight %s do not fit input %s at stride %d'
-                         % (tuple(offset.shape), tuple(mask.shape), tuple(weight.shape), tuple(input.shape), st))
     dev = input.device
     with torch.cuda.device(dev), torch.no_grad():
         cin_p = _ceil(Cin, 32)                    # zero channels x zero filters: the kernels take Cin % 32 == 0
@@ -126,6 +189,28 @@ def dcn_v2_conv(input, offset, mask, weight, bias, stride, padding, dilation, de
         pk = _packed(weight, bias, st, 1, cin_p if cin_p != Cin else None, dev)
         y = _dcn_launch(xd, om, True, pk, Ho, Wo)
         return y.permute(0, 3, 1, 2).contiguous()
+
+
+def _wants_grad(*tensors):
+    return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
+
+
+def dcn_v2_conv(input, offset, mask, weight, bias, stride, padding, dilation, deformable_groups):
+    """`_DCNv2.apply` (dcn_v2.py:16-52): input [B,Cin,H,W], offset [B,18,Ho,Wo] (channel 2k = dh_k, 2k+1 = dw_k),
+    mask [B,9,Ho,Wo] = the modulation itself (callers pass torch.sigmoid(...), dcn_v2.py:122), weight [Cout,Cin,3,3], bias
+    [Cout] -> [B,Cout,Ho,Wo].  Differentiable in all five tensors when grad mode is on and one of them requires grad (module
+    docstring); otherwise — and for the forward value in either case — the launches below."""
+    from .engine import out_size
+    L.require_cuda(input, 'dcn_v2_conv input')
+    st = _check_geometry(weight, stride, padding, dilation, deformable_groups)
+    B, Cin, H, W = input.shape
+    Ho, Wo = out_size(H, 3, st, 1), out_size(W, 3, st, 1)
+    if tuple(offset.shape) != (B, 18, Ho, Wo) or tuple(mask.shape) != (B, 9, Ho, Wo) or weight.shape[1] != Cin:
+        raise ValueError('dcn_v2_conv: offset %s / mask %s / weight %s do not fit input %s at stride %d'
+                         % (tuple(offset.shape), tuple(mask.shape), tuple(weight.shape), tuple(input.shape), st))
+    if _wants_grad(input, offset, mask, weight, bias):
+        return _DCNv2Function.apply(input, offset, mask, weight, bias, stride, padding, dilation, deformable_groups)
+    return _dcn_forward(input, offset, mask, weight, bias, st)
 
 
 class DCNv2(nn.Module):
@@ -173,9 +258,24 @@ class DCN(DCNv2):
     def forward(self, input):
         """out = conv_offset_mask(input); offset = out[:, :18]; mask = sigmoid(out[:, 18:]); dcn_v2_conv(...) — as two launches
         of the HIP library: the 27-channel 3x3 convolution, then the gather-GEMM reading its NHWC output directly (the sigmoid is
-        applied in the kernel, as in the engine's plans)."""
-        from .engine import out_size
+        applied in the kernel, as in the engine's plans).
+
+        Under grad mode (the input or a parameter requires grad) the autograd graph is the reference's (dcn_v2.py:118-128):
+        conv_offset_mask, chunk, cat and sigmoid are PyTorch operations, the deformable op is `_DCNv2Function`; the VALUE is still
+        that of the two launches, so the module's output does not depend on grad mode.  (The gradient is therefore taken at
+        PyTorch's offsets / modulation, which equal the library's to fp32 round-off.)"""
         L.require_cuda(input, 'DCN input')
+        if _wants_grad(input, *self.parameters()):
+            out = self.conv_offset_mask(input)
+            o1, o2, mask = torch.chunk(out, 3, dim=1)
+            offset = torch.cat((o1, o2), dim=1)
+            mask = torch.sigmoid(mask)
+            return _DCNv2Function.apply(input, offset, mask, self.weight, self.bias, self.stride, self.padding, self.dilation,
+                                        self.deformable_groups, lambda: self._forward_two_launches(input))
+        return self._forward_two_launches(input)
+
+    def _forward_two_launches(self, input):
+        from .engine import out_size
         st = self.stride[0]
         B, Cin, H, W = input.shape
         Ho, Wo = out_size(H, 3, st, 1), out_size(W, 3, st, 1)
