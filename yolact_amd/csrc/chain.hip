@@ -22,17 +22,16 @@
 // operations are unconditional buffer operations (out-of-range offsets for masked rows), so the compiler's vmcnt is exact.
 // Magnitude bounds of y and z are reported like every other launch (ymi_amax_*).  z == nullptr: GEMM 2 is skipped (conv3 alone:
 // the last block of the stage, whose consumer is not a 64-channel 1x1).
-#include "common.h"
+#include "gemm_h2.h"
 #include <type_traits>
-#include "../../include/yolact_amd.h"
 
 int ymi_internal_prof_begin(double flops, int tile, int kind, hipStream_t s);
 void ymi_internal_prof_end(int idx, hipStream_t s);
 
 namespace {
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+using namespace ymi_h2;
+
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int K1 = 64, N1 = 256, N2 = 64, PX = 32, NW = 8;
@@ -102,19 +101,18 @@ __global__ __launch_bounds__(64 * NW) void chain_h2_k(const ChainParams p) {
 #pragma unroll
     for (int e = 0; e < 4; ++e) { sc1[e] = p.sb[16 * q2 + 4 * g + e]; bi1[e] = p.bb ? p.bb[16 * q2 + 4 * g + e] : 0.f; }
   }
-  const float slope_a = p.act_a == YMI_ACT_RELU ? 0.f : (p.act_a == YMI_ACT_LEAKY01 ? 0.1f : 1.f);
-  const float slope_b = p.act_b == YMI_ACT_RELU ? 0.f : (p.act_b == YMI_ACT_LEAKY01 ? 0.1f : 1.f);
+  const float slope_a = ymi_act_slope(p.act_a);
+  const float slope_b = ymi_act_slope(p.act_b);
 
   const int ntiles = (p.M + PX - 1) / PX;
   // loads of a tile: this thread's 16 bytes of t (pixel t >> 4 of 32, channels 4 (t & 15) ..), this lane's residual vectors (pixel
   // 16 i + lr, channels 32 wave + 16 j + 4 g ..).  Buffer loads / stores with an out-of-range offset for rows past M (and tiles
   // past the last): zeros back, nothing written, and NO branch — with conditional memory operations the compiler cannot count what
   // is outstanding and falls back to vmcnt(0) between iterations, i.e. it waits for the stores of y it has just issued
-  constexpr unsigned OOB = 0x80000000u;
-  const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc((void *)p.x, 0, (int)((unsigned)p.M * (unsigned)p.ldx * 4u), 0x00020000);
-  const __amdgpu_buffer_rsrc_t rrs = __builtin_amdgcn_make_buffer_rsrc((void *)(p.res ? p.res : p.x), 0, p.res ? (int)((unsigned)p.M * (unsigned)p.res_ld * 4u) : 0, 0x00020000);
-  const __amdgpu_buffer_rsrc_t yrs = __builtin_amdgcn_make_buffer_rsrc((void *)p.y, 0, (int)((unsigned)p.M * (unsigned)p.ldy * 4u), 0x00020000);
-  const __amdgpu_buffer_rsrc_t zrs = __builtin_amdgcn_make_buffer_rsrc((void *)(p.z ? p.z : p.y), 0, p.z ? (int)((unsigned)p.M * (unsigned)p.ldz * 4u) : 0, 0x00020000);
+  const __amdgpu_buffer_rsrc_t xrs = buf_rsrc(p.x, (unsigned)p.M * (unsigned)p.ldx * 4u);
+  const __amdgpu_buffer_rsrc_t rrs = buf_rsrc(p.res ? p.res : p.x, p.res ? (int)((unsigned)p.M * (unsigned)p.res_ld * 4u) : 0);
+  const __amdgpu_buffer_rsrc_t yrs = buf_rsrc(p.y, (unsigned)p.M * (unsigned)p.ldy * 4u);
+  const __amdgpu_buffer_rsrc_t zrs = buf_rsrc(p.z ? p.z : p.y, p.z ? (int)((unsigned)p.M * (unsigned)p.ldz * 4u) : 0);
   const int xp = t >> 4, xc = t & 15;
   auto load_x = [&](int tile) {
     const int m = tile * PX + xp;
@@ -133,7 +131,6 @@ __global__ __launch_bounds__(64 * NW) void chain_h2_k(const ChainParams p) {
 
   // LDS-only barrier: __syncthreads() would also wait for the global loads of the NEXT iteration (vmcnt(0)), i.e. expose one memory
   // round trip per tile
-#define CHAIN_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
   // One iteration = 32 pixels, ONE barrier, software-pipelined over two tiles: after the barrier of iteration k the waves run
   // GEMM 2 + epilogue 2 of tile k - 1 (operands in buffer (k - 1) & 1, published by that barrier) and GEMM 1 + epilogue 1 of tile k
   // (t tile in buffer k & 1, written before the barrier) — two independent instruction streams for the scheduler, and half the
@@ -169,7 +166,7 @@ __global__ __launch_bounds__(64 * NW) void chain_h2_k(const ChainParams p) {
     }
     xv = load_x(tile + grid);                           // next iteration's operands: in flight until its P1 / P3
     load_res(tile + grid, rn);
-    CHAIN_BARRIER();
+    YMI_BARRIER();
     if (two) {
       // P4 (tile k - 1): GEMM 2 for pixels 16 i2 + lr, z channels 16 q2 ..: the K = 256 sum one 32-channel slice (one producing
       // wave, one scale) at a time
@@ -273,7 +270,6 @@ __global__ __launch_bounds__(64 * NW) void chain_h2_k(const ChainParams p) {
     iteration(tile, std::integral_constant<int, 0>{}, ra, rb);
     iteration(tile + grid, std::integral_constant<int, 1>{}, rb, ra);
   }
-#undef CHAIN_BARRIER
   if (p.y_amax) ymi_amax_finish(apre_y, am_y);
   if (two && p.z_amax) ymi_amax_finish(apre_z, am_z);
 #endif

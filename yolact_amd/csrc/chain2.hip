@@ -28,22 +28,19 @@
 //     accumulation's own rounding): DESIGN 3.15;
 //   * one counted s_waitcnt vmcnt + s_barrier per chunk step (24 MFMAs per wave), residual loads of a slice issued at its first step.
 // Magnitude bounds of y and z are reported like every other launch (ymi_amax_*).
-#include "common.h"
+#include "gemm_h2.h"
 #include <stdlib.h>
 #include <type_traits>
 #include <utility>
-#include "../../include/yolact_amd.h"
 
 int ymi_internal_prof_begin(double flops, int tile, int kind, hipStream_t s);
 void ymi_internal_prof_end(int idx, hipStream_t s);
 
 namespace {
 
-typedef __attribute__((address_space(3))) void *lds_ptr_t;
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+using namespace ymi_h2;
+
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-constexpr unsigned OOB = 0x80000000u;
 
 struct Chain2Params {
   const float *x, *res, *x_amax, *res_amax;
@@ -88,12 +85,12 @@ __global__ __launch_bounds__(256, 1) void chain2_k(const Chain2Params p) {
   const ymi_amax_pre apre_y = ymi_amax_prefetch(p.y_amax);
   const ymi_amax_pre apre_z = ymi_amax_prefetch(p.z_amax);
 
-  const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc((void *)p.x, 0, (int)((unsigned)p.M * (unsigned)p.ldx * 4u), 0x00020000);
-  const __amdgpu_buffer_rsrc_t rrs = __builtin_amdgcn_make_buffer_rsrc((void *)(p.res ? p.res : p.x), 0, p.res ? (int)((unsigned)p.M * (unsigned)p.res_ld * 4u) : 0, 0x00020000);
-  const __amdgpu_buffer_rsrc_t yrs = __builtin_amdgcn_make_buffer_rsrc((void *)p.y, 0, (int)((unsigned)p.M * (unsigned)p.ldy * 4u), 0x00020000);
-  const __amdgpu_buffer_rsrc_t zrs = __builtin_amdgcn_make_buffer_rsrc((void *)p.z, 0, (int)((unsigned)p.M * (unsigned)p.ldz * 4u), 0x00020000);
-  const __amdgpu_buffer_rsrc_t wars = __builtin_amdgcn_make_buffer_rsrc((void *)p.wa, 0, (int)(2 * p.wa_plane), 0x00020000);
-  const __amdgpu_buffer_rsrc_t wbrs = __builtin_amdgcn_make_buffer_rsrc((void *)p.wb, 0, (int)(2 * p.wb_plane), 0x00020000);
+  const __amdgpu_buffer_rsrc_t xrs = buf_rsrc(p.x, (unsigned)p.M * (unsigned)p.ldx * 4u);
+  const __amdgpu_buffer_rsrc_t rrs = buf_rsrc(p.res ? p.res : p.x, p.res ? (int)((unsigned)p.M * (unsigned)p.res_ld * 4u) : 0);
+  const __amdgpu_buffer_rsrc_t yrs = buf_rsrc(p.y, (unsigned)p.M * (unsigned)p.ldy * 4u);
+  const __amdgpu_buffer_rsrc_t zrs = buf_rsrc(p.z, (unsigned)p.M * (unsigned)p.ldz * 4u);
+  const __amdgpu_buffer_rsrc_t wars = buf_rsrc(p.wa, 2 * p.wa_plane);
+  const __amdgpu_buffer_rsrc_t wbrs = buf_rsrc(p.wb, 2 * p.wb_plane);
 
   // ---- filter chunks: 128 rows x 64 k x 2 planes.  LDS image of a unit: [sub = k / 32][plane][128 rows][64 bytes], 16-byte slot s
   // of row r at s ^ ((r >> 2) & 3) (the plane image of csrc/dcn.hip).  Piece q of 32 = (sub, plane, 16-row group); wave w issues
@@ -124,18 +121,18 @@ __global__ __launch_bounds__(256, 1) void chain2_k(const Chain2Params p) {
         __builtin_amdgcn_raw_ptr_buffer_load_lds(wbrs, (lds_ptr_t)(dst + dma_l[i]), 16, (sl < NS && p.z) ? dma_b[i] : OOB, so, 0, 0);
     }
   };
-#define C2_WAIT_VM(N) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory")
-#define C2_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
 #ifdef YMI_DIAGNOSTICS
   unsigned long long tr_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   const bool tracing = p.trace != nullptr;
   tr_[0] = __builtin_amdgcn_s_memtime();
   // a step's tail: [a] counted wait for the next chunk [b] barrier [c]; tr_[2] += b - a (memory), tr_[3] += c - b (other waves)
-#define C2_STEP_END(N) do { if (tracing) { const unsigned long long a_ = __builtin_amdgcn_s_memtime(); C2_WAIT_VM(N); \
-    const unsigned long long b_ = __builtin_amdgcn_s_memtime(); C2_BARRIER(); tr_[2] += b_ - a_; tr_[3] += __builtin_amdgcn_s_memtime() - b_; } \
-    else { C2_WAIT_VM(N); C2_BARRIER(); } } while (0)
+#define C2_STEP_END(N) \
+    do { if (tracing) { const unsigned long long a_ = __builtin_amdgcn_s_memtime(); YMI_WAIT_VM(N); \
+    const unsigned long long b_ = __builtin_amdgcn_s_memtime(); YMI_BARRIER(); tr_[2] += b_ - a_; tr_[3] += __builtin_amdgcn_s_memtime() - b_; } \
+    else { YMI_WAIT_VM(N); YMI_BARRIER(); } } while (0)
 #else
-#define C2_STEP_END(N) do { C2_WAIT_VM(N); C2_BARRIER(); } while (0)
+#define C2_STEP_END(N) \
+    do { YMI_WAIT_VM(N); YMI_BARRIER(); } while (0)
 #endif
 
   issue_chunk(0, 0, 0);
@@ -171,8 +168,8 @@ __global__ __launch_bounds__(256, 1) void chain2_k(const Chain2Params p) {
         }
     }
   }
-  C2_WAIT_VM(0);
-  C2_BARRIER();                           // chunks 0 and 1 landed, constants written
+  YMI_WAIT_VM(0);
+  YMI_BARRIER();                           // chunks 0 and 1 landed, constants written
 #ifdef YMI_DIAGNOSTICS
   tr_[1] = __builtin_amdgcn_s_memtime();
 #endif
@@ -192,8 +189,8 @@ __global__ __launch_bounds__(256, 1) void chain2_k(const Chain2Params p) {
     for (int j = 0; j < 2; ++j)
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc2[h][j][r] = 0.f;
-  const float slope_a = p.act_a == YMI_ACT_RELU ? 0.f : (p.act_a == YMI_ACT_LEAKY01 ? 0.1f : 1.f);
-  const float slope_b = p.act_b == YMI_ACT_RELU ? 0.f : (p.act_b == YMI_ACT_LEAKY01 ? 0.1f : 1.f);
+  const float slope_a = ymi_act_slope(p.act_a);
+  const float slope_b = ymi_act_slope(p.act_b);
   const int mrow = m0 + 32 * wm + lr;     // this lane's pixel
   const bool row_ok = mrow < p.M;
   float am_y = 0.f, am_z = 0.f;
@@ -271,7 +268,7 @@ __global__ __launch_bounds__(256, 1) void chain2_k(const Chain2Params p) {
         *reinterpret_cast<f16x4 *>(lds + a2_addr(ct, 1, 32 * wm + lr, g) + 8 * hh) = l4;
       }
     }
-    C2_BARRIER();                         // the y slice is in LDS
+    YMI_BARRIER();                         // the y slice is in LDS
 #ifdef YMI_DIAGNOSTICS
     if (tracing) tr_[4] += __builtin_amdgcn_s_memtime() - e_t0;
 #endif
@@ -306,8 +303,6 @@ __global__ __launch_bounds__(256, 1) void chain2_k(const Chain2Params p) {
   tr_[5] = __builtin_amdgcn_s_memtime();
 #endif
 #undef C2_STEP_END
-#undef C2_WAIT_VM
-#undef C2_BARRIER
   // ---- epilogue 2: z -----------------------------------------------------------------------------------------------------------------
   if (p.z) {
 #pragma unroll

@@ -26,18 +26,15 @@
 //
 // Epilogue (fused): folded-BN scale/bias, residual add (plain or bilinear-upsampled source = FPN top-down path),
 // activation, scatter to up to 3 output segments with independent strides.
-#include "common.h"
+#include "gemm_h2.h"
 #include <stdlib.h>
 #include <mutex>
 #include <type_traits>
-#include "../../include/yolact_amd.h"
+#include "upsample_math.h"
 
 namespace {
+using namespace ymi_h2;
 
-constexpr int BK = 32;
-constexpr unsigned OOB = 0x80000000u;  // buffer offset >= num_records (< 2^31, validated) -> the load returns zeros
-
-typedef __attribute__((address_space(3))) void *lds_ptr_t;
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
@@ -74,30 +71,6 @@ __device__ __forceinline__ Split3 split8(const f32x4 x0, const f32x4 x1) {
 }
 
 
-// ---- PREC = 3 / 4: fp32-class products on the fp16 matrix pipe ("fp16x2") ----------------------------------------------
-// x * s = h + l, two fp16 pieces by ROUND TO NEAREST (v_cvt_pk_f16_f32): h = fp16(x s), l = fp16(x s - h) with x s - h exact
-// in fp32.  11 + 11 significant bits + two signs represent about two thirds of all fp32 values exactly and the rest to one fp32 ulp,
-// unbiased.  s = a power of two per tensor (ymi_h2_scale: the producer's magnitude bound -> [2^13, 2^14)), so h never
-// overflows and stays a normal fp16 for 27 binades below the tensor's maximum.  a*b = hh + hl + lh (+ ll dropped,
-// <= 2^-22 |ab|): 3 MFMAs (v_mfma_f32_32x32x16_f16, exact products, fp32 accumulate) instead of bf16x3's 6, and the split
-// is 3 VALU per element with no byte permutes.  tools/split_probe.hip: 574 TFLOP/s fp32-equivalent on random data (bf16x3
-// 313, exact fp32 154), error against fp64 2.6e-7 of sum|ab| (bf16x3 3.3e-7, fp32 MFMA 5.2e-7).
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-struct Split2 { f16x8 h, l; };
-
-__device__ __forceinline__ Split2 split8h(const f32x4 x0, const f32x4 x1, const float s) {
-  const float x[8] = {x0[0], x0[1], x0[2], x0[3], x1[0], x1[1], x1[2], x1[3]};
-  Split2 o;
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    const float t = x[e] * s;
-    const _Float16 h = (_Float16)t;
-    o.h[e] = h;
-    o.l[e] = (_Float16)(t - (float)h);
-  }
-  return o;
-}
-
 struct KParams {
   ymi_conv_desc d;
   int M, HoWo, tiles_n, nk;
@@ -127,17 +100,6 @@ __device__ __forceinline__ float act_apply(float v, int act) {
     case YMI_ACT_SIGMOID: return 1.f / (1.f + expf(-v));
     default: return v;
   }
-}
-
-// torch's area_pixel_compute_source_index for align_corners=False (fp32 arithmetic on purpose,
-// see SURVEY appendix A5): src = max(scale*(dst+0.5)-0.5, 0)
-__device__ __forceinline__ void bilin_coord(int dst, float scale, int in_size, int &i0, int &i1, float &l1) {
-  float src = scale * ((float)dst + 0.5f) - 0.5f;
-  src = src < 0.f ? 0.f : src;
-  i0 = (int)src;
-  if (i0 > in_size - 1) i0 = in_size - 1;
-  i1 = i0 + ((i0 < in_size - 1) ? 1 : 0);
-  l1 = src - (float)i0;
 }
 
 // General epilogue (multi-segment scatter, unaligned rows, bilinear FPN residual, tanh / sigmoid): one row per loop
@@ -195,8 +157,8 @@ __device__ __forceinline__ void epilogue_general_rows(const KParams &p, const fl
     } else if (d.res_mode == YMI_RES_BILINEAR) {
       const int oy = pix / d.Wo, ox = pix - oy * d.Wo;
       int y0, y1, x0, x1; float ly, lx;
-      bilin_coord(oy, rscale_h, d.res_H, y0, y1, ly);
-      bilin_coord(ox, rscale_w, d.res_W, x0, x1, lx);
+      up_coord(oy, rscale_h, d.res_H, y0, y1, ly);
+      up_coord(ox, rscale_w, d.res_W, x0, x1, lx);
       const float *rb_ = d.res + (size_t)b * d.res_H * d.res_W * d.res_ld + n;
       const float *p00 = rb_ + (size_t)(y0 * d.res_W + x0) * d.res_ld, *p01 = rb_ + (size_t)(y0 * d.res_W + x1) * d.res_ld;
       const float *p10 = rb_ + (size_t)(y1 * d.res_W + x0) * d.res_ld, *p11 = rb_ + (size_t)(y1 * d.res_W + x1) * d.res_ld;
@@ -332,11 +294,11 @@ void conv_igemm_f32(const KParams p) {
 
   const int grp = blockIdx.y;    // group of a grouped GEMM (the 16 Winograd components); 0 otherwise
   const __amdgpu_buffer_rsrc_t xrs = APL
-      ? __builtin_amdgcn_make_buffer_rsrc((void *)((const char *)p.a2 + (size_t)grp * p.a2_gs), 0, (int)(2 * p.a2_plane), 0x00020000)
-      : __builtin_amdgcn_make_buffer_rsrc((void *)(d.x + (size_t)grp * p.x_gs), 0, (int)p.x_bytes, 0x00020000);
+      ? buf_rsrc((const char *)p.a2 + (size_t)grp * p.a2_gs, 2 * p.a2_plane)
+      : buf_rsrc(d.x + (size_t)grp * p.x_gs, p.x_bytes);
   const __amdgpu_buffer_rsrc_t wrs = BPL
-      ? __builtin_amdgcn_make_buffer_rsrc((void *)((const char *)p.w3 + (size_t)grp * p.w3_gs), 0, (int)(NPL * p.w3_plane), 0x00020000)
-      : __builtin_amdgcn_make_buffer_rsrc((void *)(d.w + (size_t)grp * p.w_gs), 0, (int)p.w_bytes, 0x00020000);
+      ? buf_rsrc((const char *)p.w3 + (size_t)grp * p.w3_gs, NPL * p.w3_plane)
+      : buf_rsrc(d.w + (size_t)grp * p.w_gs, p.w_bytes);
   // fp16x2: the power-of-two scale of the activation operand, from the producer's magnitude bound (ymi_h2_scale)
   float sA = 1.f, invA = 1.f;
   if (H2) {
@@ -822,8 +784,6 @@ void conv_igemm_f32(const KParams p) {
   // ---- main loop ---------------------------------------------------------------------------
   // s_waitcnt vmcnt(N) only (expcnt / lgkmcnt fields at "no wait"): gfx9 encoding vmcnt[3:0] | expcnt[6:4] |
   // lgkmcnt[11:8] | vmcnt_hi[15:14].  The asm memory clobber keeps the compiler from moving LDS accesses across.
-#define YMI_WAIT_VM(N) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory")
-#define YMI_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
   const int nsteps = (p.nk + WK - 1) / WK;
   if (p.trace) tr_loop = __builtin_readcyclecounter();
   // bf16x3 tiles without an intra-block K split: the loop is peeled into "every step stages the next one" + the final
@@ -959,8 +919,6 @@ void conv_igemm_f32(const KParams p) {
       nxt = (nxt + 1 == NS) ? 0 : nxt + 1;
     }
   }
-#undef YMI_WAIT_VM
-#undef YMI_BARRIER
 
   // ---- epilogue ----------------------------------------------------------------------------
   // Accumulators -> LDS tile [WK][BM][BN+4] -> each thread owns 4 consecutive output channels of a row, so
@@ -998,7 +956,7 @@ void conv_igemm_f32(const KParams p) {
                        (RES_PREFETCH && d.res_mode == YMI_RES_ADD && (d.res_ld & 3) == 0 && ((((uintptr_t)d.res) & 15) == 0)));
     if (fast) {
       // act(x) = max(x, slope * x): slope 0 -> ReLU, 0.1 -> LeakyReLU(0.1), 1 -> identity (exact: one mul + one max)
-      const float slope = g0.act == YMI_ACT_RELU ? 0.f : (g0.act == YMI_ACT_LEAKY01 ? 0.1f : 1.f);
+      const float slope = ymi_act_slope(g0.act);
       const bool has_res = d.res_mode == YMI_RES_ADD, after = d.res_after_act != 0;
       f32x4 o[RPT];
 #pragma unroll
@@ -1057,12 +1015,6 @@ int g_prof_n = 0, g_prof_alloc = 0, g_prof_on = 0;
 std::mutex g_prof_mu;   // the opt-in profiling records are process-global: threaded callers (eval.py's evalvideo pool) may
                         // launch concurrently, so slot allocation is serialised; with profiling off nothing is locked
 
-// The workgroup dispatcher does not balance a grid that fits in one residency round: it packs up to `occupancy`
-// blocks on a CU while others hold fewer (a 616-block layer ran as if its busiest CU held 4+ blocks, not 3).  When
-// the grid is at most occ*256 blocks we therefore cap residency at k = ceil(grid / 256) blocks per CU by padding
-// the block's LDS allocation with unused dynamic LDS, so no CU can take more than its share.
-constexpr int LDS_PER_CU = 160 * 1024, NUM_CU = 256;
-
 template <int WM, int WN, int WK, int TM, int TN, int NS, bool ALL_LOADERS, int PREC>
 int launch_cfg(const KParams &kp, int loader, hipStream_t s, int groups) {
   constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
@@ -1073,19 +1025,12 @@ int launch_cfg(const KParams &kp, int loader, hipStream_t s, int groups) {
   p.tiles_n = (p.d.Cout + BN - 1) / BN;
   const int grid = tiles_m * p.tiles_n;
   if (p.trace && (grid > g_trace_cap || groups > 1)) p.trace = nullptr;
-  int dyn = 0;
-  {
-    int occ = LDS_PER_CU / static_lds;                     // LDS-limited residency (VGPRs allow >= this for every fp32 tile)
-    if (PREC >= 1) {
-      constexpr int occ_regs = conv_occupancy<WM, WN, WK, TM, TN, NS, 0, PREC>();
-      occ = occ < occ_regs ? occ : occ_regs;
-    }
-    const int k = (grid * groups + NUM_CU - 1) / NUM_CU;    // blocks per CU if perfectly spread
-    if (k < occ && !(p.abl & 8)) {
-      const int want = LDS_PER_CU / (k + 1) + 1024;         // > 160K/(k+1)  =>  at most k blocks fit
-      if (want > static_lds && want <= LDS_PER_CU / k) dyn = want - static_lds;
-    }
+  int occ = LDS_PER_CU / static_lds;                       // LDS-limited residency (VGPRs allow >= this for every fp32 tile)
+  if (PREC >= 1) {
+    constexpr int occ_regs = conv_occupancy<WM, WN, WK, TM, TN, NS, 0, PREC>();
+    occ = occ < occ_regs ? occ : occ_regs;
   }
+  const int dyn = (p.abl & 8) ? 0 : residency_cap_lds(static_lds, occ, grid * groups);
   const bool pointwise = p.d.kh == 1 && p.d.kw == 1 && p.d.pad == 0;
   if constexpr (PREC == 4) {             // pre-split A planes exist for the pointwise loader only (the grouped Winograd GEMMs)
     if (loader != 0 || !pointwise) return YMI_EARG;
@@ -1369,7 +1314,7 @@ __global__ __launch_bounds__(256) void splitk_fixup_k(const float *__restrict__ 
     if (bias) bi = *reinterpret_cast<const f32x4 *>(bias + n);
     if (res) rv = *reinterpret_cast<const f32x4 *>(res + m * res_ld + n);
     v = v * sc + bi;
-    const float slope = act == YMI_ACT_RELU ? 0.f : (act == YMI_ACT_LEAKY01 ? 0.1f : 1.f);
+    const float slope = ymi_act_slope(act);
     if (!res_after_act) v += rv;
 #pragma unroll
     for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], slope * v[e]);

@@ -24,10 +24,9 @@
 //     end of K are out-of-bounds buffer loads, i.e. zeros without a memory access) so its vmcnt is a constant.
 // K order, LDS images, fragment layout, MFMA order (h*l, l*h, h*h) and the fast-path epilogue are those of the fp16x2 tiles of
 // conv_igemm.hip, so the filter planes / scale_h2 of engine.Packed.h2() are used unchanged.
-#include "common.h"
+#include "gemm_h2.h"
 #include <stdlib.h>
 #include <type_traits>
-#include "../../include/yolact_amd.h"
 
 int ymi_internal_prof_begin(double flops, int tile, int kind, hipStream_t s);
 void ymi_internal_prof_end(int idx, hipStream_t s);
@@ -39,16 +38,10 @@ void ymi_internal_prof_end(int idx, hipStream_t s);
 #endif
 
 namespace {
+using namespace ymi_h2;
 
-constexpr int BK = 32;
-constexpr unsigned OOB = 0x80000000u;   // buffer offset >= num_records: the load returns zeros
-
-typedef __attribute__((address_space(3))) void *lds_ptr_t;
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x3 __attribute__((ext_vector_type(3)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-struct Split2 { f16x8 h, l; };
 
 struct DcnParams {
   const float *x, *offmask, *scale_h2, *bias, *x_amax;
@@ -134,9 +127,9 @@ void pipe_h2_k(const DcnParams p) {
   const int tile_n = logical % p.tiles_n, tile_m = logical / p.tiles_n;
   const int m0 = tile_m * BM, n0 = tile_n * BN;
 
-  const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc((void *)p.x, 0, (int)p.x_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t ors = __builtin_amdgcn_make_buffer_rsrc((void *)p.offmask, 0, (int)p.om_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc((void *)p.w_h2, 0, (int)(2 * p.w_plane), 0x00020000);
+  const __amdgpu_buffer_rsrc_t xrs = buf_rsrc(p.x, p.x_bytes);
+  const __amdgpu_buffer_rsrc_t ors = buf_rsrc(p.offmask, p.om_bytes);
+  const __amdgpu_buffer_rsrc_t wrs = buf_rsrc(p.w_h2, 2 * p.w_plane);
 
   float sA, invA;
   ymi_h2_scale(ymi_amax_read(p.x_amax), sA, invA);
@@ -298,7 +291,7 @@ void pipe_h2_k(const DcnParams p) {
 #endif
     f32x4 v;
     if constexpr (PLAIN) {
-      v = ring[S][i][0] * sA;
+      v = ring[S][i][0];
     } else {
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
@@ -306,16 +299,11 @@ void pipe_h2_k(const DcnParams p) {
         a = __builtin_fmaf(ringw[S][i][1], ring[S][i][1][e], a);
         a = __builtin_fmaf(ringw[S][i][2], ring[S][i][2][e], a);
         a = __builtin_fmaf(ringw[S][i][3], ring[S][i][3][e], a);
-        v[e] = (a * ringw[S][i][4]) * sA;
+        v[e] = a * ringw[S][i][4];
       }
     }
     f16x4 h4, l4;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const _Float16 h = (_Float16)v[e];
-      h4[e] = h;
-      l4[e] = (_Float16)(v[e] - (float)h);
-    }
+    split4h(v, sA, h4, l4);
     char *dst = reinterpret_cast<char *>(As) + a_st[i];
     *reinterpret_cast<f16x4 *>(dst) = h4;
     *reinterpret_cast<f16x4 *>(dst + BM * 64) = l4;
@@ -355,9 +343,6 @@ void pipe_h2_k(const DcnParams p) {
       pb[j].l = *reinterpret_cast<const f16x8 *>(Bp + j * 32 * 16 + BN * 16);
     }
   };
-
-#define YMI_WAIT_VM(N) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory")
-#define YMI_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
 
   // One K step: the MFMAs of chunk st, and between them the pieces of the producer side — combine row q of chunk st+1 (ring
   // slot SLOT), request the same row of chunk st+3 into the registers just freed, one filter DMA of chunk st+3.  EVERY step does
@@ -460,8 +445,6 @@ void pipe_h2_k(const DcnParams p) {
   YMI_WAIT_VM(0);               // the run-ahead filter DMAs target LDS the epilogue is about to reuse
   YMI_BARRIER();
   YMI_STAMP(6);
-#undef YMI_WAIT_VM
-#undef YMI_BARRIER
 
   // ---- epilogue: accumulators -> LDS tile -> 16-byte stores (the fast path of conv_igemm.hip) -------------------------------
   // folded-BN scale (times the filter row's inverse scale) and bias: requested before the transposition, consumed (scale * the
@@ -504,7 +487,7 @@ void pipe_h2_k(const DcnParams p) {
   sc = sc * invA;               // exact (a power of two); (v * invA) * sc == v * (invA * sc)
   __syncthreads();
   YMI_STAMP(7);                 // accumulators transposed through LDS (and scale / bias / residual loads back)
-  const float slope = p.act == YMI_ACT_RELU ? 0.f : (p.act == YMI_ACT_LEAKY01 ? 0.1f : 1.f);
+  const float slope = ymi_act_slope(p.act);
   float am = 0.f;
   f32x4 o[RPT];
 #pragma unroll
@@ -536,12 +519,7 @@ void pipe_h2_k(const DcnParams p) {
       unsigned long long *o = p.trace + 16 * (size_t)(blockIdx.x + gridDim.x * blockIdx.y);
 #pragma unroll
       for (int i = 0; i < 10; ++i) o[i] = tr_[i];
-      o[10] = tr_rt0;
-      o[11] = __builtin_amdgcn_s_memrealtime();
-      o[12] = (unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | (0 << 6) | 4);                                   // HW_REG_HW_ID
-      o[13] = (unsigned long long)(__builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 20) & 7u);                            // XCC_ID
-      o[14] = (unsigned long long)my_nk;
-      o[15] = 1;
+      trace_tail(o, tr_rt0, my_nk);
     }
   }
 #endif
@@ -554,24 +532,11 @@ int launch_dcn_k(DcnParams p, hipStream_t s) {
   constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
   p.tiles_n = (p.Cout + BN - 1) / BN;
   const int grid = ((p.M + BM - 1) / BM) * p.tiles_n;
-  // The workgroup dispatcher does not balance a grid that fits in one residency round: it packs up to `occupancy` blocks on a CU
-  // while others hold none (csrc/conv_igemm.hip launch_cfg).  When the grid is at most occ * 256 blocks, cap the residency at
-  // k = ceil(grid / 256) blocks per CU by padding the block's LDS allocation with unused dynamic LDS.
-  int dyn = 0;
-  {
-    constexpr int LDS_PER_CU = 160 * 1024, static_lds = dcn_lds_floats<WM, WN, TM, TN, RING>() * 4;
-    const int occ = dcn_occupancy<WM, WN, TM, TN, RING, PLAIN>(), k = (grid * ((p.nk + p.nk_split - 1) / p.nk_split) + 255) / 256;
-#ifdef YMI_DIAGNOSTICS
-    const bool cap_on = !(p.abl & 64);
-#else
-    const bool cap_on = true;
-#endif
-    if (k < occ && cap_on) {
-      const int want = LDS_PER_CU / (k + 1) + 1024;
-      if (want > static_lds && want <= LDS_PER_CU / k) dyn = want - static_lds;
-    }
-  }
   const int splits = (p.nk + p.nk_split - 1) / p.nk_split;
+  int dyn = residency_cap_lds(dcn_lds_floats<WM, WN, TM, TN, RING>() * 4, dcn_occupancy<WM, WN, TM, TN, RING, PLAIN>(), grid * splits);
+#ifdef YMI_DIAGNOSTICS
+  if (p.abl & 64) dyn = 0;
+#endif
   hipLaunchKernelGGL((pipe_h2_k<WM, WN, TM, TN, RING, PLAIN>), dim3(grid, splits), dim3(64 * WM * WN), dyn, s, p);
   return ymi_launch_status();
 }

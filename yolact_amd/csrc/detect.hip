@@ -14,7 +14,7 @@
 // cycles per block (loads 82k -> 2.6k, IoU 50k -> 22k), K3 119 -> 36 us at batch 1.
 // Tie rule: the reference sorts with the unstable torch.sort; we define stable order (lowest index first),
 // SURVEY §7 hard part 3(iv).  All float math mirrors the reference's op order; build with -ffp-contract=off.
-#include "common.h"
+#include "detect_common.h"
 #include <stdlib.h>
 #include "../../include/yolact_amd.h"
 
@@ -31,27 +31,6 @@ constexpr int SORT_N = 256;      // bitonic capacity (top_k, max_det <= 256)
 // diagnostics (`make DIAG=1`, env YMI_DETECT_TRACE = device address of a u64 buffer, 16 slots per block): phase time stamps of
 // K2 / K3 by thread 0 (tools/detect_probe.py).  Product builds pass nullptr: one scalar branch per stamp.
 #define YMI_STAMP(i) do { if (trace && threadIdx.x == 0) trace[(size_t)tblk * 16 + (i)] = __builtin_readcyclecounter(); } while (0)
-
-__device__ __forceinline__ unsigned f2key(float f) {
-  // order-preserving float -> uint (larger float => larger key); never 0 for finite inputs
-  unsigned u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-// decode(loc, prior) exactly as box_utils.py:304-310 evaluates it (left to right, fp32):
-//   c = p.xy + (loc.xy * 0.1) * p.wh ; s = p.wh * exp(loc.wh * 0.2) ; xy1 = c - s/2 ; xy2 = s + xy1
-__device__ __forceinline__ f32x4 decode_box(const float *loc, const float *pr) {
-  const float cx = pr[0] + (loc[0] * 0.1f) * pr[2];
-  const float cy = pr[1] + (loc[1] * 0.1f) * pr[3];
-  const float w = pr[2] * expf(loc[2] * 0.2f);
-  const float h = pr[3] * expf(loc[3] * 0.2f);
-  f32x4 b;
-  b[0] = cx - w / 2.f;
-  b[1] = cy - h / 2.f;
-  b[2] = w + b[0];
-  b[3] = h + b[1];
-  return b;
-}
 
 // ------------------------------------------------------------------------------------------------
 // K1: softmax + keep.  Block = 64 priors x C classes staged in LDS (row stride C, C odd => conflict free).

@@ -20,7 +20,7 @@
 // the division is IEEE (correctly rounded).
 // Tie rule (the reference's argsort / torch.sort are unstable, so its order of exactly tied scores is not defined): score desc,
 // then class asc, then prior asc.
-#include "common.h"
+#include "detect_common.h"
 #include "../../include/yolact_amd.h"
 
 namespace {
@@ -30,27 +30,6 @@ constexpr int KLDS = 4096;       // candidate keys per class held in LDS (32 KiB
 constexpr int SLDS = 2048;       // survivor boxes cached in LDS (32 KiB); later survivors are read back from the box array
 constexpr int MLDS = 8192;       // G3: per-image survivor keys sorted in LDS (64 KiB); more are sorted in place in the workspace
 constexpr int CAP_MAX = 256;     // max_det limit (as ymi_detect_f32)
-
-__device__ __forceinline__ unsigned f2key(float f) {
-  // order-preserving float -> uint (larger float => larger key); never 0 for finite inputs
-  unsigned u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float key2f(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
-
-// box_utils.py:304-310, left to right in fp32 (as detect.hip's decode_box)
-__device__ __forceinline__ f32x4 decode_box(const float *loc, const float *pr) {
-  const float cx = pr[0] + (loc[0] * 0.1f) * pr[2];
-  const float cy = pr[1] + (loc[1] * 0.1f) * pr[3];
-  const float w = pr[2] * expf(loc[2] * 0.2f);
-  const float h = pr[3] * expf(loc[3] * 0.2f);
-  f32x4 b;
-  b[0] = cx - w / 2.f;
-  b[1] = cy - h / 2.f;
-  b[2] = w + b[0];
-  b[3] = h + b[1];
-  return b;
-}
 
 // cython_nms.pyx's max / min (first operand on ties) and its overlap test; `a` is the higher-ranked box
 __device__ __forceinline__ float cmax(float a, float b) { return a >= b ? a : b; }

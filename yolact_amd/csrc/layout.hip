@@ -1,5 +1,6 @@
 // Bandwidth kernels around the conv engine: layout change, max-pool, bilinear resize (NHWC, float4 lanes).
 #include "common.h"
+#include "upsample_math.h"
 #include "../../include/yolact_amd.h"
 
 namespace {
@@ -70,15 +71,6 @@ __global__ __launch_bounds__(256) void maxpool3x3s2_k(const float *__restrict__ 
   }
 }
 
-__device__ __forceinline__ void bl_coord(int dst, float scale, int in_size, int &i0, int &i1, float &l1) {
-  float src = scale * ((float)dst + 0.5f) - 0.5f;
-  src = src < 0.f ? 0.f : src;
-  i0 = (int)src;
-  if (i0 > in_size - 1) i0 = in_size - 1;
-  i1 = i0 + ((i0 < in_size - 1) ? 1 : 0);
-  l1 = src - (float)i0;
-}
-
 // F.interpolate(bilinear, align_corners=False) on NHWC; thread per (out pixel, 4 channels).
 __global__ __launch_bounds__(256) void bilinear_nhwc_k(const float *__restrict__ x, float *__restrict__ y,
                                                         int Hi, int Wi, int C4, int Ho, int Wo, float sh, float sw,
@@ -88,8 +80,8 @@ __global__ __launch_bounds__(256) void bilinear_nhwc_k(const float *__restrict__
     const int c4 = (int)(i - pu * (unsigned)C4), ox = (int)(pu - ru * (unsigned)Wo), oy = (int)(ru - bu * (unsigned)Ho);
     const long b = bu;
     int y0, y1, x0, x1; float ly, lx;
-    bl_coord(oy, sh, Hi, y0, y1, ly);
-    bl_coord(ox, sw, Wi, x0, x1, lx);
+    up_coord(oy, sh, Hi, y0, y1, ly);
+    up_coord(ox, sw, Wi, x0, x1, lx);
     const float *img = x + (b * Hi * Wi * C4 + c4) * 4;
     const f32x4 v00 = *reinterpret_cast<const f32x4 *>(img + (long)(y0 * Wi + x0) * C4 * 4);
     const f32x4 v01 = *reinterpret_cast<const f32x4 *>(img + (long)(y0 * Wi + x1) * C4 * 4);
@@ -119,8 +111,8 @@ __global__ __launch_bounds__(256) void bilinear_add_k(const float *__restrict__ 
     const int c4 = (int)(i - pu * (unsigned)C4), ox = (int)(pu - ru * (unsigned)Wo), oy = (int)(ru - bu * (unsigned)Ho);
     const long b = bu;
     int y0, y1, x0, x1; float ly, lx;
-    bl_coord(oy, sh, Hi, y0, y1, ly);
-    bl_coord(ox, sw, Wi, x0, x1, lx);
+    up_coord(oy, sh, Hi, y0, y1, ly);
+    up_coord(ox, sw, Wi, x0, x1, lx);
     const float *img = x + (b * Hi * Wi * C4 + c4) * 4;
     const f32x4 v00 = *reinterpret_cast<const f32x4 *>(img + (long)(y0 * Wi + x0) * C4 * 4);
     const f32x4 v01 = *reinterpret_cast<const f32x4 *>(img + (long)(y0 * Wi + x1) * C4 * 4);

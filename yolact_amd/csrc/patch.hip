@@ -24,18 +24,17 @@
 // 8.5 % of masked rows / columns of 138 = 8 x 17.25.  The tuner takes the kernel where it wins.
 // Arithmetic: the fp16x2 scheme of the engine (tensor scale from x_amax, h*l + l*h + h*h on the fp16 pipe, fp32 accumulate), K order
 // tap-major like engine.Packed — the filter planes of Packed.h2() are used unchanged.
-#include "common.h"
+#include "gemm_h2.h"
 #include <stdlib.h>
 #include <type_traits>
-#include "../../include/yolact_amd.h"
 
 int ymi_internal_prof_begin(double flops, int tile, int kind, hipStream_t s);
 void ymi_internal_prof_end(int idx, hipStream_t s);
 
 namespace {
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+using namespace ymi_h2;
+
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int C = 64, NW = 4, NT = 64 * NW;
@@ -57,8 +56,6 @@ struct PatchParams {
   unsigned w_plane, x_bytes, y_bytes;
 };
 
-struct Frag { f16x8 h, l; };
-
 // Four waves, ONE per SIMD (up to 512 registers each): wave q owns output channels 16 q .. 16 q + 15 — 144 VGPRs of filter fragments —
 // and ALL eight rows of the tile: eight independent accumulators, so consecutive MFMAs never depend on each other, and room for a
 // second set of activation fragments: the LDS reads of K chunk s + 1 are issued before the 24 MFMAs of chunk s (explicit double
@@ -69,7 +66,6 @@ __global__ __launch_bounds__(NT, 1) void patch3x3_c64_k(const PatchParams p) {
   __shared__ __attribute__((aligned(16))) char lds[2 * BUF];
   const int t = threadIdx.x, lane = t & 63, q = __builtin_amdgcn_readfirstlane(t >> 6);
   const int lr = lane & 15, g = lane >> 4;
-  constexpr unsigned OOB = 0x80000000u;
   float sA, invA;
   ymi_h2_scale(ymi_amax_read(p.x_amax), sA, invA);
   const ymi_amax_pre apre = ymi_amax_prefetch(p.y_amax);
@@ -88,10 +84,10 @@ __global__ __launch_bounds__(NT, 1) void patch3x3_c64_k(const PatchParams p) {
     sc[e] = p.scale_h2[16 * q + 4 * g + e] * invA;     // folded BN scale / filter-row scale, times the exact 1 / sA
     if (p.bias) bi[e] = p.bias[16 * q + 4 * g + e];
   }
-  const float slope = p.act == YMI_ACT_RELU ? 0.f : (p.act == YMI_ACT_LEAKY01 ? 0.1f : 1.f);
+  const float slope = ymi_act_slope(p.act);
 
-  const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc((void *)p.x, 0, (int)p.x_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t yrs = __builtin_amdgcn_make_buffer_rsrc((void *)p.y, 0, (int)p.y_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t xrs = buf_rsrc(p.x, p.x_bytes);
+  const __amdgpu_buffer_rsrc_t yrs = buf_rsrc(p.y, p.y_bytes);
   const int per_img = p.tiles_x * p.tiles_y;
 
   // patch loads: thread t takes float4 number t + NT * i of the patch (pixel (t + NT i) / 16, channels 4 ((t + NT i) % 16) ..);
@@ -116,21 +112,14 @@ __global__ __launch_bounds__(NT, 1) void patch3x3_c64_k(const PatchParams p) {
     for (int i = 0; i < NLOAD; ++i) {
       const int idx = t + NT * i, px = idx >> 4, cg = idx & 15;
       if (px < PPX) {
-        const f32x4 s = v[i] * sA;
         f16x4 h4, l4;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const _Float16 h = (_Float16)s[e];
-          h4[e] = h;
-          l4[e] = (_Float16)(s[e] - (float)h);
-        }
+        split4h(v[i], sA, h4, l4);
         char *dst = buf + px * RS + cg * 8;
         *reinterpret_cast<f16x4 *>(dst) = h4;
         *reinterpret_cast<f16x4 *>(dst + PLANE) = l4;
       }
     }
   };
-#define PATCH_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
 
   float am = 0.f;
   const int grid = (int)gridDim.x;
@@ -138,7 +127,7 @@ __global__ __launch_bounds__(NT, 1) void patch3x3_c64_k(const PatchParams p) {
   int tile = blockIdx.x;
   request(tile, ld);
   publish(ld, lds);
-  PATCH_BARRIER();
+  YMI_BARRIER();
   for (int k = 0; tile < p.ntiles; tile += grid, ++k) {
     const char *const cur = lds + (k & 1) * BUF;
     char *const nxt = lds + ((k + 1) & 1) * BUF;          // last read one iteration ago: free for the whole of this one
@@ -205,9 +194,8 @@ __global__ __launch_bounds__(NT, 1) void patch3x3_c64_k(const PatchParams p) {
       }
     }
     publish(ld, nxt);                                    // the next tile's patch: its buffer was last read one iteration ago
-    PATCH_BARRIER();
+    YMI_BARRIER();
   }
-#undef PATCH_BARRIER
   if (p.y_amax) ymi_amax_finish(apre, am);
 #endif
 }
@@ -225,17 +213,15 @@ __global__ __launch_bounds__(PC_NT) void patch3x3_c64_pc_k(const PatchParams p) 
   __shared__ __attribute__((aligned(16))) char lds[2 * BUF];
   const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
   const int lr = lane & 15, g = lane >> 4;
-  constexpr unsigned OOB = 0x80000000u;
   float sA, invA;
   ymi_h2_scale(ymi_amax_read(p.x_amax), sA, invA);
   const ymi_amax_pre apre = ymi_amax_prefetch(p.y_amax);
   const int per_img = p.tiles_x * p.tiles_y;
   const int grid = (int)gridDim.x;
-#define PATCH_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
 
   if (wave >= 4) {
     // =============================== producers: 256 threads, patch of tile k + 1 -> LDS buffer (k + 1) & 1 ===========================
-    const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc((void *)p.x, 0, (int)p.x_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t xrs = buf_rsrc(p.x, p.x_bytes);
     const int tp = t - 256;
     auto request = [&](int tile, f32x4 (&v)[PC_NLOAD]) {
       const bool live = tile < p.ntiles;
@@ -257,14 +243,8 @@ __global__ __launch_bounds__(PC_NT) void patch3x3_c64_pc_k(const PatchParams p) 
       for (int i = 0; i < PC_NLOAD; ++i) {
         const int idx = tp + 256 * i, px = idx >> 4, cg = idx & 15;
         if (px < PPX) {
-          const f32x4 sv = v[i] * sA;
           f16x4 h4, l4;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const _Float16 h = (_Float16)sv[e];
-            h4[e] = h;
-            l4[e] = (_Float16)(sv[e] - (float)h);
-          }
+          split4h(v[i], sA, h4, l4);
           char *dst = buf + px * RS + cg * 8;
           *reinterpret_cast<f16x4 *>(dst) = h4;
           *reinterpret_cast<f16x4 *>(dst + PLANE) = l4;
@@ -277,15 +257,15 @@ __global__ __launch_bounds__(PC_NT) void patch3x3_c64_pc_k(const PatchParams p) 
     request(tile, va);
     request(tile + grid, vb);
     publish(va, lds);
-    PATCH_BARRIER();
+    YMI_BARRIER();
     for (int k = 0; tile < p.ntiles; tile += 2 * grid, k += 2) {
       request(tile + 2 * grid, va);
       publish(vb, lds + ((k + 1) & 1) * BUF);            // tile + grid
-      PATCH_BARRIER();
+      YMI_BARRIER();
       if (tile + grid < p.ntiles) {
         request(tile + 3 * grid, vb);
         publish(va, lds + (k & 1) * BUF);                // tile + 2 grid
-        PATCH_BARRIER();
+        YMI_BARRIER();
       }
     }
     return;
@@ -299,8 +279,8 @@ __global__ __launch_bounds__(PC_NT) void patch3x3_c64_pc_k(const PatchParams p) 
     wh[c] = *reinterpret_cast<const f16x8 *>(src);
     wl[c] = *reinterpret_cast<const f16x8 *>(src + p.w_plane);
   }
-  const __amdgpu_buffer_rsrc_t yrs = __builtin_amdgcn_make_buffer_rsrc((void *)p.y, 0, (int)p.y_bytes, 0x00020000);
-  const float slope = p.act == YMI_ACT_RELU ? 0.f : (p.act == YMI_ACT_LEAKY01 ? 0.1f : 1.f);
+  const __amdgpu_buffer_rsrc_t yrs = buf_rsrc(p.y, p.y_bytes);
+  const float slope = ymi_act_slope(p.act);
   f32x4 sc, bi = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
@@ -309,7 +289,7 @@ __global__ __launch_bounds__(PC_NT) void patch3x3_c64_pc_k(const PatchParams p) 
   }
   float am = 0.f;
   int tile = blockIdx.x;
-  PATCH_BARRIER();
+  YMI_BARRIER();
   for (int k = 0; tile < p.ntiles; tile += grid, ++k) {
     const char *const cur = lds + (k & 1) * BUF;
     const char *const lane_base = cur + lr * RS + g * 16;
@@ -381,9 +361,8 @@ __global__ __launch_bounds__(PC_NT) void patch3x3_c64_pc_k(const PatchParams p) 
         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), yrs, off, 0, 0);
       }
     }
-    PATCH_BARRIER();
+    YMI_BARRIER();
   }
-#undef PATCH_BARRIER
   if (p.y_amax) ymi_amax_finish(apre, am);
 #endif
 }

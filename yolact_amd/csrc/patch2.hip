@@ -20,21 +20,18 @@
 // engine.Packed: the filter planes / scale_h2 of Packed.h2() are used unchanged.  Same products as every fp16x2 tile (h*l, l*h, h*h,
 // fp32 accumulate); the K summation order per accumulator is (chunk, tap) instead of (tap, chunk): results agree with the other
 // kernels to fp32 rounding, not bit for bit.
-#include "common.h"
+#include "gemm_h2.h"
 #include <stdlib.h>
 #include <type_traits>
-#include "../../include/yolact_amd.h"
 
 int ymi_internal_prof_begin(double flops, int tile, int kind, hipStream_t s);
 void ymi_internal_prof_end(int idx, hipStream_t s);
 
 namespace {
 
-typedef __attribute__((address_space(3))) void *lds_ptr_t;
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+using namespace ymi_h2;
+
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-constexpr unsigned OOB = 0x80000000u;
 
 constexpr int BN = 128;                    // output channels per block
 constexpr int MAXP = 336;                  // patch pixels an LDS buffer holds ((TH + 2) * (TW + 2) <= MAXP)
@@ -92,8 +89,6 @@ __global__ __launch_bounds__(512, 2) void patch2_k(const Patch2Params p) {
   const ymi_amax_pre apre = ymi_amax_prefetch(sg.amax);
 
   const int nch = p.Cin >> 5, nsteps = 9 * nch;
-#define P2_WAIT_VM(N) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory")
-#define P2_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
 
   // epilogue constants of the block's 128 channels -> LDS (scale_h2 / sA, bias)
   if (t < BN) {
@@ -107,8 +102,8 @@ __global__ __launch_bounds__(512, 2) void patch2_k(const Patch2Params p) {
   if (producer) {
     // =========================================== PRODUCERS ========================================================================
     const int pt = t - 256, pw = wave - 4;
-    const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc((void *)p.x, 0, (int)p.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc((void *)p.w_h2, 0, (int)(2 * p.w_plane), 0x00020000);
+    const __amdgpu_buffer_rsrc_t xrs = buf_rsrc(p.x, p.x_bytes);
+    const __amdgpu_buffer_rsrc_t wrs = buf_rsrc(p.w_h2, 2 * p.w_plane);
     // patch: float4 number pt + 256 i = (patch pixel, 4-channel group cg of the chunk's 32)
     unsigned poff[NLP];
     int pdst[NLP];
@@ -168,13 +163,13 @@ __global__ __launch_bounds__(512, 2) void patch2_k(const Patch2Params p) {
     patch_request(0);
     w_request(0, 0);
     w_request(1, 1);
-    P2_WAIT_VM(2 * NDMA);
+    YMI_WAIT_VM(2 * NDMA);
     patch_publish(lds + OFF_P);
-    P2_WAIT_VM(0);
+    YMI_WAIT_VM(0);
 #ifdef YMI_DIAGNOSTICS
     tr_[1] = __builtin_amdgcn_s_memtime();
 #endif
-    P2_BARRIER();
+    YMI_BARRIER();
     // chunk by chunk, the nine taps unrolled: the patch loads of tap 0 and their use at tap 3 are straight-line code, so the compiler
     // counts what is outstanding instead of falling back to vmcnt(0) (which would wait for the filter DMAs just issued)
     int wu = 2;                                         // unit of step s + 2
@@ -188,11 +183,11 @@ __global__ __launch_bounds__(512, 2) void patch2_k(const Patch2Params p) {
 #ifdef YMI_DIAGNOSTICS
         const unsigned long long a_ = tracing ? __builtin_amdgcn_s_memtime() : 0ull;
 #endif
-        if (tap <= 1) P2_WAIT_VM(NDMA + NLP); else P2_WAIT_VM(NDMA);         // the next step's filters have landed
+        if (tap <= 1) YMI_WAIT_VM(NDMA + NLP); else YMI_WAIT_VM(NDMA);         // the next step's filters have landed
 #ifdef YMI_DIAGNOSTICS
         const unsigned long long b_ = tracing ? __builtin_amdgcn_s_memtime() : 0ull;
 #endif
-        P2_BARRIER();
+        YMI_BARRIER();
 #ifdef YMI_DIAGNOSTICS
         if (tracing) { tr_[2] += b_ - a_; tr_[3] += __builtin_amdgcn_s_memtime() - b_; }
 #endif
@@ -226,7 +221,7 @@ __global__ __launch_bounds__(512, 2) void patch2_k(const Patch2Params p) {
 #ifdef YMI_DIAGNOSTICS
     tr_[1] = __builtin_amdgcn_s_memtime();
 #endif
-    P2_BARRIER();
+    YMI_BARRIER();
     // Software pipeline over GROUPS = (k step s2, pair of pixel tiles): the pixel fragments of group g + 1 are requested before the
     // MFMAs of group g — also ACROSS the step barrier: the patch is static for the whole chunk (and the next chunk's was published at
     // tap 3), so only the four filter fragments of a step have to be read behind its barrier (first version: every group was
@@ -296,7 +291,7 @@ __global__ __launch_bounds__(512, 2) void patch2_k(const Patch2Params p) {
 #ifdef YMI_DIAGNOSTICS
         const unsigned long long a_ = tracing ? __builtin_amdgcn_s_memtime() : 0ull;
 #endif
-        P2_BARRIER();
+        YMI_BARRIER();
 #ifdef YMI_DIAGNOSTICS
         if (tracing) tr_[3] += __builtin_amdgcn_s_memtime() - a_;
 #endif
@@ -309,9 +304,9 @@ __global__ __launch_bounds__(512, 2) void patch2_k(const Patch2Params p) {
     // ---- epilogue (consumers): scale / bias / activation, float4 stores of 4 consecutive channels of one pixel ---------------------
     {
       const float *cs = reinterpret_cast<const float *>(lds + OFF_C);
-      const float slope = sg.act == YMI_ACT_RELU ? 0.f : (sg.act == YMI_ACT_LEAKY01 ? 0.1f : 1.f);
+      const float slope = ymi_act_slope(sg.act);
       const unsigned ybytes = (unsigned)((size_t)p.B * p.H * p.W * sg.ld * 4);
-      const __amdgpu_buffer_rsrc_t yrs = __builtin_amdgcn_make_buffer_rsrc((void *)sg.ptr, 0, (int)ybytes, 0x00020000);
+      const __amdgpu_buffer_rsrc_t yrs = buf_rsrc(sg.ptr, ybytes);
 #pragma unroll
       for (int j = 0; j < NPJ; ++j) {
         const int q = 32 * (wp * NPJ + j) + lr;
@@ -339,8 +334,6 @@ __global__ __launch_bounds__(512, 2) void patch2_k(const Patch2Params p) {
       }
     }
   }
-#undef P2_WAIT_VM
-#undef P2_BARRIER
 
   if (sg.amax) ymi_amax_finish(apre, am);
 #ifdef YMI_DIAGNOSTICS

@@ -19,10 +19,9 @@
 // load).  K order, LDS images, fragment layout, MFMA order (h*l, l*h, h*h) and the epilogue are pipe_h2_k's, so the filter planes /
 // scale_h2 of engine.Packed.h2() are used unchanged and the results of a layer agree with the pipelined tile's to the last bit
 // (same products, same summation order per accumulator).
-#include "common.h"
+#include "gemm_h2.h"
 #include <stdlib.h>
 #include <type_traits>
-#include "../../include/yolact_amd.h"
 
 int ymi_internal_prof_begin(double flops, int tile, int kind, hipStream_t s);
 void ymi_internal_prof_end(int idx, hipStream_t s);
@@ -31,14 +30,7 @@ int ymi_internal_splitk_fixup(const float *part, long gstride, int S, long M, in
                               hipStream_t s);
 
 namespace {
-
-constexpr int BK = 32;
-constexpr unsigned OOB = 0x80000000u;   // buffer offset >= num_records: the load returns zeros
-
-typedef __attribute__((address_space(3))) void *lds_ptr_t;
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-struct Split2 { f16x8 h, l; };
+using namespace ymi_h2;
 
 struct PcParams {
   const float *x, *scale_h2, *bias, *x_amax;
@@ -113,9 +105,6 @@ void pc_conv_k(const PcParams p) {
   const int kc0 = blockIdx.y * p.nk_split;
   const int nk = (p.nk - kc0) < p.nk_split ? (p.nk - kc0) : p.nk_split;   // chunks of this block's K range
 
-#define PC_WAIT_VM(N) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory")
-#define PC_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
-
   f32x16 acc[TM][TN];
 #pragma unroll
   for (int i = 0; i < TM; ++i)
@@ -128,8 +117,8 @@ void pc_conv_k(const PcParams p) {
     // =========================================== PRODUCERS ========================================================================
     const int pt = t - 64 * NCW, pw = wave - NCW;
     const int kq = pt & 7, r0 = pt >> 3;
-    const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc((void *)p.x, 0, (int)p.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc((void *)p.w_h2, 0, (int)(2 * p.w_plane), 0x00020000);
+    const __amdgpu_buffer_rsrc_t xrs = buf_rsrc(p.x, p.x_bytes);
+    const __amdgpu_buffer_rsrc_t wrs = buf_rsrc(p.w_h2, 2 * p.w_plane);
     // rows r0 + RPP * i of the tile, channels 4 kq .. 4 kq + 3 of the chunk
     int g_iy0[RA], g_ix0[RA], g_ib[RA], a_st[RA];
     bool g_ok[RA];
@@ -201,14 +190,8 @@ void pc_conv_k(const PcParams p) {
       constexpr int S = decltype(slot_c)::value;
 #pragma unroll
       for (int i = 0; i < RA; ++i) {
-        const f32x4 v = ring[S][i] * sA;
         f16x4 h4, l4;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const _Float16 h = (_Float16)v[e];
-          h4[e] = h;
-          l4[e] = (_Float16)(v[e] - (float)h);
-        }
+        split4h(ring[S][i], sA, h4, l4);
         char *dst = reinterpret_cast<char *>(As) + a_st[i];
         *reinterpret_cast<f16x4 *>(dst) = h4;
         *reinterpret_cast<f16x4 *>(dst + BM * 64) = l4;
@@ -219,13 +202,13 @@ void pc_conv_k(const PcParams p) {
     [&]<int... J>(std::integer_sequence<int, J...>) {
       ((request_b(J, J), request_a(std::integral_constant<int, J>{})), ...);          // B(j), A(j) for j = 0 .. R - 1
     }(std::make_integer_sequence<int, R>{});
-    PC_WAIT_VM((R - 1) * NVM);                          // B(0), A(0) have landed
+    YMI_WAIT_VM((R - 1) * NVM);                          // B(0), A(0) have landed
     combine(std::integral_constant<int, 0>{}, Abase);
     request_b(R, R);
     request_a(std::integral_constant<int, 0>{});        // A(R) -> slot 0
-    PC_WAIT_VM((R - 1) * NVM);                          // B(1), A(1) have landed
+    YMI_WAIT_VM((R - 1) * NVM);                          // B(1), A(1) have landed
     PC_STAMP(1);
-    PC_BARRIER();
+    YMI_BARRIER();
     PC_STAMP(2);
     // step c: combine A(c + 1) (landed: last step's wait), request B(c + R + 1) and A(c + R + 1), wait for B(c + 2) and A(c + 2)
     int bnx = R + 1;                                    // stage of chunk c + R + 1
@@ -237,16 +220,16 @@ void pc_conv_k(const PcParams p) {
 #ifdef YMI_DIAGNOSTICS
       if (tracing) {                                    // where a producer step goes: issue + conversion | memory wait | barrier wait
         const unsigned long long a = __builtin_amdgcn_s_memtime();
-        PC_WAIT_VM((R - 1) * NVM);
+        YMI_WAIT_VM((R - 1) * NVM);
         const unsigned long long b = __builtin_amdgcn_s_memtime();
-        PC_BARRIER();
+        YMI_BARRIER();
         const unsigned long long e = __builtin_amdgcn_s_memtime();
         tr_[5] += b - a; tr_[6] += e - b;
         return;
       }
 #endif
-      PC_WAIT_VM((R - 1) * NVM);
-      PC_BARRIER();
+      YMI_WAIT_VM((R - 1) * NVM);
+      YMI_BARRIER();
     };
     int c = 0;
     for (; c + R <= nk; c += R) {                       // c % R == 0 here: step c + i combines slot (i + 1) % R
@@ -297,7 +280,7 @@ void pc_conv_k(const PcParams p) {
     using K0 = std::integral_constant<int, 0>;
     using K1 = std::integral_constant<int, 1>;
     PC_STAMP(1);
-    PC_BARRIER();                                       // chunk 0: A planes written, filter planes landed
+    YMI_BARRIER();                                       // chunk 0: A planes written, filter planes landed
     PC_STAMP(2);
     if (p.flags & 1) __builtin_amdgcn_s_setprio(1);
     int bst = 0;
@@ -311,21 +294,19 @@ void pc_conv_k(const PcParams p) {
 #ifdef YMI_DIAGNOSTICS
       if (tracing) {                                    // time a consumer spends at the step barrier (= waiting for the producers)
         const unsigned long long a = __builtin_amdgcn_s_memtime();
-        PC_BARRIER();
+        YMI_BARRIER();
         tr_[6] += __builtin_amdgcn_s_memtime() - a;
         continue;
       }
 #endif
-      PC_BARRIER();
+      YMI_BARRIER();
     }
     if (p.flags & 1) __builtin_amdgcn_s_setprio(0);
     PC_STAMP(3);
   }
-  PC_WAIT_VM(0);                // (producers: the run-ahead filter DMAs target LDS the epilogue is about to reuse)
-  PC_BARRIER();
+  YMI_WAIT_VM(0);                // (producers: the run-ahead filter DMAs target LDS the epilogue is about to reuse)
+  YMI_BARRIER();
   PC_STAMP(4);
-#undef PC_WAIT_VM
-#undef PC_BARRIER
 
   // ---- epilogue: accumulators -> LDS tile -> 16-byte stores by all eight waves (pipe_h2_k's) -------------------------------------
   constexpr int C4 = BN / 4, RSTEP = NT / C4, RPT = BM / RSTEP;
@@ -366,7 +347,7 @@ void pc_conv_k(const PcParams p) {
   }
   sc = sc * invA;               // exact (a power of two)
   __syncthreads();
-  const float slope = p.act == YMI_ACT_RELU ? 0.f : (p.act == YMI_ACT_LEAKY01 ? 0.1f : 1.f);
+  const float slope = ymi_act_slope(p.act);
   float am = 0.f;
   f32x4 o[RPT];
 #pragma unroll
@@ -397,12 +378,7 @@ void pc_conv_k(const PcParams p) {
       unsigned long long *o_ = p.trace + 32 * (size_t)(blockIdx.x + gridDim.x * blockIdx.y) + (wave == 0 ? 0 : 16);
 #pragma unroll
       for (int i = 0; i < 8; ++i) o_[i] = tr_[i];
-      o_[10] = tr_rt0;
-      o_[11] = __builtin_amdgcn_s_memrealtime();
-      o_[12] = (unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | (0 << 6) | 4);
-      o_[13] = (unsigned long long)(__builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 20) & 7u);
-      o_[14] = (unsigned long long)nk;
-      o_[15] = 1;
+      trace_tail(o_, tr_rt0, nk);
     }
   }
 #endif
@@ -416,17 +392,8 @@ int launch_pc(PcParams p, hipStream_t s) {
   p.tiles_n = (p.Cout + BN - 1) / BN;
   const int grid = ((p.M + BM - 1) / BM) * p.tiles_n;
   const int splits = (p.nk + p.nk_split - 1) / p.nk_split;
-  // The dispatcher does not balance a grid that fits in one residency round (csrc/dcn.hip launch_dcn_k): when the whole grid is at
-  // most 256 k blocks, cap the residency at k blocks per CU by padding the block's LDS allocation with unused dynamic LDS.
-  int dyn = 0;
-  {
-    constexpr int LDS_PER_CU = 160 * 1024, static_lds = pc_lds_floats<CM, CN, TM, TN, R>() * 4;
-    const int occ = LDS_PER_CU / static_lds, k = (grid * splits + 255) / 256;
-    if (k < occ && !(p.flags & 4)) {
-      const int want = LDS_PER_CU / (k + 1) + 1024;
-      if (want > static_lds && want <= LDS_PER_CU / k) dyn = want - static_lds;
-    }
-  }
+  constexpr int static_lds = pc_lds_floats<CM, CN, TM, TN, R>() * 4;
+  const int dyn = (p.flags & 4) ? 0 : residency_cap_lds(static_lds, LDS_PER_CU / static_lds, grid * splits);
   hipLaunchKernelGGL((pc_conv_k<CM, CN, TM, TN, R>), dim3(grid, splits), dim3(64 * (CM * CN + NPW)), dyn, s, p);
   return ymi_launch_status();
 }

@@ -6,19 +6,10 @@
 // One kernel, one pass: the source is read once (4 taps x 12 bytes per output pixel), the result is written once either
 // as the reference's NCHW [N,3,oh,ow] or directly as the engine's NHWC4 input (skipping ymi_nchw_to_nhwc4_f32).
 #include "common.h"
+#include "upsample_math.h"
 #include "../../include/yolact_amd.h"
 
 namespace {
-
-__device__ __forceinline__ void src_coord(int dst, float scale, int in_size, int &i0, int &i1, float &l1) {
-  // torch's area_pixel_compute_source_index, align_corners=False, fp32
-  float src = scale * ((float)dst + 0.5f) - 0.5f;
-  src = src < 0.f ? 0.f : src;
-  i0 = (int)src;
-  if (i0 > in_size - 1) i0 = in_size - 1;
-  i1 = i0 + ((i0 < in_size - 1) ? 1 : 0);
-  l1 = src - (float)i0;
-}
 
 struct FbtParams {
   const float *img;
@@ -38,8 +29,8 @@ __global__ __launch_bounds__(256) void fast_base_transform_k(const FbtParams p) 
     const int y = (int)(r % p.oh);
     const long n = r / p.oh;
     int y0, y1, x0, x1; float ly, lx;
-    src_coord(y, p.sh, p.H, y0, y1, ly);
-    src_coord(x, p.sw, p.W, x0, x1, lx);
+    up_coord(y, p.sh, p.H, y0, y1, ly);
+    up_coord(x, p.sw, p.W, x0, x1, lx);
     const float *b = p.img + n * (long)p.H * p.W * 3;
     const float *p00 = b + ((long)y0 * p.W + x0) * 3, *p01 = b + ((long)y0 * p.W + x1) * 3;
     const float *p10 = b + ((long)y1 * p.W + x0) * 3, *p11 = b + ((long)y1 * p.W + x1) * 3;

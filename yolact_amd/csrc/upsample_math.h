@@ -4,6 +4,9 @@
 // (-ffp-contract=off in the Makefile).
 #pragma once
 
+// torch's area_pixel_compute_source_index for align_corners=False (fp32 arithmetic on purpose): src = max(scale*(dst+0.5)-0.5, 0).
+// Also the source coordinates of the FPN residual (conv_igemm.hip), the NHWC bilinear resize (layout.hip) and FastBaseTransform
+// (preprocess.hip).
 __device__ __forceinline__ void up_coord(int dst, float scale, int in_size, int &i0, int &i1, float &l1) {
   float src = scale * ((float)dst + 0.5f) - 0.5f;
   src = src < 0.f ? 0.f : src;

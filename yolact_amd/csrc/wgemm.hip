@@ -16,21 +16,19 @@
 //   * orientation U V^T: a lane ends with 4 x 4 consecutive columns of ONE row of M: float4 stores straight from the accumulators.
 // Same products and the same K order as the tile it replaces (h*l, l*h, h*h per 16-deep step, chunks ascending): M is bit-identical.
 // Round 7: where a component's filters fit the register file the launch takes wgemm_us_k below (U stationary) instead of wgemm_k.
-#include "common.h"
+#include "gemm_h2.h"
 #include <stdio.h>
 #include <stdlib.h>
 #include <type_traits>
-#include "../../include/yolact_amd.h"
 
 int ymi_internal_prof_begin(double flops, int tile, int kind, hipStream_t s);
 void ymi_internal_prof_end(int idx, hipStream_t s);
 
 namespace {
 
-typedef __attribute__((address_space(3))) void *lds_ptr_t;
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+using namespace ymi_h2;
+
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-constexpr unsigned OOB = 0x80000000u;
 
 constexpr int BM = 128, BN = 256;
 constexpr int A_BYTES = 2 * BM * 64, B_BYTES = 2 * BN * 64, STAGE = A_BYTES + B_BYTES, NST = 3;     // 16 KB + 32 KB per 32-deep chunk
@@ -66,8 +64,6 @@ __global__ __launch_bounds__(512, 2) void wgemm_k(const WgParams p) {
   const bool tracing = p.trace != nullptr;
   tr_[0] = __builtin_amdgcn_s_memtime();
 #endif
-#define WG_WAIT_VM(N) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory")
-#define WG_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
   // item -> (component, row tile, column block): the column blocks of a row tile are consecutive items (they share V)
   auto decode = [&](int it, int &g, int &tm, int &tn) {
     tn = it % p.tiles_n;
@@ -103,9 +99,9 @@ __global__ __launch_bounds__(512, 2) void wgemm_k(const WgParams p) {
       const bool live = idx < my_items;
       int g = 0, tm = 0, tn = 0;
       decode(live ? b0 + idx * nb : 0, g, tm, tn);
-      vrs = __builtin_amdgcn_make_buffer_rsrc((void *)(p.v + (size_t)g * p.v_gs), 0, live ? (int)p.v_gs : 0, 0x00020000);
-      urs = __builtin_amdgcn_make_buffer_rsrc((void *)(p.u + (size_t)g * p.u_gs), 0, live ? (int)p.u_gs : 0, 0x00020000);
-      srs = __builtin_amdgcn_make_buffer_rsrc((void *)(p.uinv + (size_t)g * p.cout_pad), 0, live ? p.cout_pad * 4 : 0, 0x00020000);
+      vrs = buf_rsrc(p.v + (size_t)g * p.v_gs, live ? (int)p.v_gs : 0);
+      urs = buf_rsrc(p.u + (size_t)g * p.u_gs, live ? (int)p.u_gs : 0);
+      srs = buf_rsrc(p.uinv + (size_t)g * p.cout_pad, live ? p.cout_pad * 4 : 0);
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int row = tm * BM + a_row[i];
@@ -134,11 +130,11 @@ __global__ __launch_bounds__(512, 2) void wgemm_k(const WgParams p) {
     };
     request(0);
     request(1);
-    WG_WAIT_VM(NPC);                       // chunk 0 (and its item's scales) landed
+    YMI_WAIT_VM(NPC);                       // chunk 0 (and its item's scales) landed
 #ifdef YMI_DIAGNOSTICS
     tr_[1] = __builtin_amdgcn_s_memtime();
 #endif
-    WG_BARRIER();
+    YMI_BARRIER();
     int st = 2;
     for (int s = 0; s < nsteps; ++s) {
       request(st);                         // chunk s + 2 into the stage freed by the last barrier (past the last item: out-of-bounds pieces)
@@ -146,16 +142,16 @@ __global__ __launch_bounds__(512, 2) void wgemm_k(const WgParams p) {
 #ifdef YMI_DIAGNOSTICS
       const unsigned long long a_ = tracing ? __builtin_amdgcn_s_memtime() : 0ull;
 #endif
-      WG_WAIT_VM(NPC);                     // chunk s + 1 landed (a scale piece, if any, is older than the 12 pieces that may remain)
+      YMI_WAIT_VM(NPC);                     // chunk s + 1 landed (a scale piece, if any, is older than the 12 pieces that may remain)
 #ifdef YMI_DIAGNOSTICS
       const unsigned long long b_ = tracing ? __builtin_amdgcn_s_memtime() : 0ull;
 #endif
-      WG_BARRIER();
+      YMI_BARRIER();
 #ifdef YMI_DIAGNOSTICS
       if (tracing) { tr_[2] += b_ - a_; tr_[3] += __builtin_amdgcn_s_memtime() - b_; }
 #endif
     }
-    WG_WAIT_VM(0);
+    YMI_WAIT_VM(0);
   } else {
     // =========================================== CONSUMERS ========================================================================
     const int wc = wave & 1, wp = wave >> 1;                              // column half (4 tiles of 32), row half (2 tiles of 32)
@@ -175,7 +171,7 @@ __global__ __launch_bounds__(512, 2) void wgemm_k(const WgParams p) {
 #ifdef YMI_DIAGNOSTICS
     tr_[1] = __builtin_amdgcn_s_memtime();
 #endif
-    WG_BARRIER();
+    YMI_BARRIER();
     __builtin_amdgcn_s_setprio(1);
     int st = 0, kc = 0, idx = 0, sc_par = 0;
     for (int s = 0; s < nsteps; ++s) {
@@ -244,15 +240,13 @@ __global__ __launch_bounds__(512, 2) void wgemm_k(const WgParams p) {
 #ifdef YMI_DIAGNOSTICS
       const unsigned long long a_ = tracing ? __builtin_amdgcn_s_memtime() : 0ull;
 #endif
-      WG_BARRIER();
+      YMI_BARRIER();
 #ifdef YMI_DIAGNOSTICS
       if (tracing) tr_[3] += __builtin_amdgcn_s_memtime() - a_;
 #endif
     }
     __builtin_amdgcn_s_setprio(0);
   }
-#undef WG_WAIT_VM
-#undef WG_BARRIER
 #ifdef YMI_DIAGNOSTICS
   if (tracing) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -311,8 +305,6 @@ __global__ __launch_bounds__(256) void wgemm_us_k(const WgParams p) {
   const bool tracing = p.trace != nullptr;
   tr_[0] = __builtin_amdgcn_s_memtime();
 #endif
-#define WG_WAIT_VM(N) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory")
-#define WG_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
   // ---- V requests: piece wave + 4 i = (plane, 16-row group of the tile's 128 rows), the lane's 16-byte k slot swizzled as in wgemm_k
   int a_row[4], a_dst[4];
   unsigned a_ko[4], a_vo[4], a_vn[4];      // a_vo: this lane's offsets for the tile being requested, a_vn: for the tile after it
@@ -322,7 +314,7 @@ __global__ __launch_bounds__(256) void wgemm_us_k(const WgParams p) {
     const int row = rg * 16 + (lane >> 2), lsl = (lane & 3) ^ ((row >> 2) & 3);
     a_row[i] = row; a_ko[i] = (unsigned)plane * p.v_plane + 16u * lsl; a_dst[i] = plane * (BM * 64) + rg * 1024;
   }
-  const __amdgpu_buffer_rsrc_t vrs = __builtin_amdgcn_make_buffer_rsrc((void *)(p.v + (size_t)g * p.v_gs), 0, (int)p.v_gs, 0x00020000);
+  const __amdgpu_buffer_rsrc_t vrs = buf_rsrc(p.v + (size_t)g * p.v_gs, p.v_gs);
   auto tile_offsets = [&](int tm, unsigned (&vo)[4]) {                    // past the block's run or past T: out-of-bounds pieces (no access)
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -349,7 +341,7 @@ __global__ __launch_bounds__(256) void wgemm_us_k(const WgParams p) {
   // registers; from the second tile on only V moves.  (Loading all of U ahead of the first MFMA cost 20 000 - 27 000 cycles per block,
   // straight from global in fragment order as well as through LDS two chunks deep: a third of a 69^2 launch.)
   f16x8 u[2][2][2 * NK];                   // [column tile][plane][k step]: rows tn BN + 64 wave + 32 i + lr, k = 16 ks + 8 hh .. + 7
-  const __amdgpu_buffer_rsrc_t urs = __builtin_amdgcn_make_buffer_rsrc((void *)(p.u + (size_t)g * p.u_gs), 0, (int)p.u_gs, 0x00020000);
+  const __amdgpu_buffer_rsrc_t urs = buf_rsrc(p.u + (size_t)g * p.u_gs, p.u_gs);
   int b_dst[8];
   unsigned b_vo[8];                        // piece wave + 4 i = (plane, 16-row group of the 256 rows)
 #pragma unroll
@@ -382,11 +374,11 @@ __global__ __launch_bounds__(256) void wgemm_us_k(const WgParams p) {
   const int vo0 = lr * 64 + 16 * ((0 + hh) ^ psw), vo1 = lr * 64 + 16 * ((2 + hh) ^ psw);   // V row 32 j + lr: + 2048 j; l plane: + BM * 64
   const float *sc = reinterpret_cast<const float *>(lds + US_OFF_SC);
   float *mg = p.m + (size_t)g * p.m_gs;
-  WG_WAIT_VM(0);                           // chunks 0 and 1 of V and U landed
+  YMI_WAIT_VM(0);                           // chunks 0 and 1 of V and U landed
 #ifdef YMI_DIAGNOSTICS
   tr_[1] = __builtin_amdgcn_s_memtime();
 #endif
-  WG_BARRIER();
+  YMI_BARRIER();
   __builtin_amdgcn_s_setprio(1);
   // A chunk = 4 groups (k step s2, pair of row tiles jp) of 12 MFMAs on two fragment buffers.  One wave per SIMD: nothing else hides what this
   // wave waits for, so the order is pinned (sched_barrier): the fragments of group n + 1 and ONE DMA piece of chunk + 2 are issued ahead of
@@ -446,11 +438,11 @@ __global__ __launch_bounds__(256) void wgemm_us_k(const WgParams p) {
       const unsigned long long a_ = tracing ? __builtin_amdgcn_s_memtime() : 0ull;
 #endif
       // chunk + 1 landed (and every M store older than the request above): all but the pieces of chunk + 2 just issued
-      if (ureq) WG_WAIT_VM(US_NPC + 8); else WG_WAIT_VM(US_NPC);
+      if (ureq) YMI_WAIT_VM(US_NPC + 8); else YMI_WAIT_VM(US_NPC);
 #ifdef YMI_DIAGNOSTICS
       const unsigned long long b_ = tracing ? __builtin_amdgcn_s_memtime() : 0ull;
 #endif
-      WG_BARRIER();
+      YMI_BARRIER();
 #ifdef YMI_DIAGNOSTICS
       if (tracing) { tr_[2] += b_ - a_; tr_[3] += __builtin_amdgcn_s_memtime() - b_; }
 #endif
@@ -484,9 +476,7 @@ __global__ __launch_bounds__(256) void wgemm_us_k(const WgParams p) {
   tile(std::true_type{}, tm0);
   for (int tm = tm0 + 1; tm < tm1; ++tm) tile(std::false_type{}, tm);
   __builtin_amdgcn_s_setprio(0);
-  WG_WAIT_VM(0);                           // the two out-of-bounds requests past the run
-#undef WG_WAIT_VM
-#undef WG_BARRIER
+  YMI_WAIT_VM(0);                           // the two out-of-bounds requests past the run
 #undef WG_PIN
 #ifdef YMI_DIAGNOSTICS
   if (tracing) {

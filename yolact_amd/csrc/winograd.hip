@@ -9,8 +9,7 @@
 // so the only extra rounding is a handful of fp32 additions: measured error vs the direct kernel <= 2e-6 relative
 // (tests/test_gpu_kernels.py::test_winograd_matches_direct), far inside the 1e-4 parity budget.
 // The execution plan times this path against the direct kernel per layer and keeps the faster one.
-#include "common.h"
-#include "../../include/yolact_amd.h"
+#include "gemm_h2.h"
 
 int ymi_internal_grouped_gemm(const ymi_conv_desc *d, int groups, long x_gs, long w_gs, long y_gs, double prof_flops,
                               int prof_kind, hipStream_t s, const void *a2 = nullptr, unsigned a2_plane = 0, long a2_gs = 0,
@@ -125,7 +124,7 @@ __global__ __launch_bounds__(256) void wino_out_k(const float *__restrict__ Mm, 
     f32x4 sc = {1.f, 1.f, 1.f, 1.f}, bi = {0.f, 0.f, 0.f, 0.f};
     if (scale) sc = *reinterpret_cast<const f32x4 *>(scale + n4 * 4);
     if (bias) bi = *reinterpret_cast<const f32x4 *>(bias + n4 * 4);
-    const float slope = act == YMI_ACT_RELU ? 0.f : (act == YMI_ACT_LEAKY01 ? 0.1f : 1.f);
+    const float slope = ymi_act_slope(act);
     // Every value (scale, bias, activation) BEFORE the first store (round 5, from the ISA): a load result first used inside a
     // conditional store block made the compiler wait with vmcnt(0) in EVERY such block, i.e. for the previous block's store — one
     // memory round trip per pixel.  Measured on the plan's launches: 8.4 -> 7.6 us here, 27.8 -> 25.0 us (69 x 69 x 256, batch 8) and
@@ -222,7 +221,7 @@ __device__ __forceinline__ void seg_amax_commit(float *y_amax, int nseg, const y
 __device__ __forceinline__ float seg_vec_store(const SegVec &sv, f32x4 v, long b, long pix) {
   v = v * sv.sc + sv.bi;
   if (sv.act <= YMI_ACT_LEAKY01) {      // none / ReLU / LeakyReLU: max(x, slope x)
-    const float slope = sv.act == YMI_ACT_RELU ? 0.f : (sv.act == YMI_ACT_LEAKY01 ? 0.1f : 1.f);
+    const float slope = ymi_act_slope(sv.act);
 #pragma unroll
     for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], slope * v[e]);
   } else {
@@ -324,7 +323,7 @@ __device__ __forceinline__ void bt6(const f32x4 v0, const f32x4 v1, const f32x4 
 
 // one thread = one 6x6 input patch (tile) x 4 channels.  x [B,H,W,C] NHWC, V [36][T][C]  (PLANES: fp16x2 planes [36][2][T][C];
 // |B^T d B| <= 100 max|d|: every row of B^T has an absolute sum of at most 10)
-// torch's area_pixel_compute_source_index for align_corners = False, exactly as csrc/layout.hip bl_coord evaluates it
+// up_coord (upsample_math.h) at the fixed scale 0.5, reduced to the weight: the caller derives the source rows from the tile itself
 __device__ __forceinline__ void up2_coord(int dst, int in_size, float &l1) {
   float src = 0.5f * ((float)dst + 0.5f) - 0.5f;
   src = src < 0.f ? 0.f : src;
@@ -336,7 +335,7 @@ __device__ __forceinline__ void up2_coord(int dst, int in_size, float &l1) {
 // UPS: the layer's input is the 2x bilinear upsampling (+ ReLU) of xl [B,H/2,W/2,C]: the 6 x 6 patch of a tile (hi-res rows
 // 4 ty - 1 .. 4 ty + 4) only touches the 4 x 4 low-res window starting at (2 ty - 1, 2 tx - 1): hi-res offset r uses window rows
 // r >> 1 and (r >> 1) + 1 (window addresses clamped to the image: where the reference clamps i0 / i1 the weights it derives are
-// such that the duplicated row reproduces its arithmetic), with the weights of bl_coord and the operation order of
+// such that the duplicated row reproduces its arithmetic), with the weights of up_coord and the operation order of
 // bilinear_nhwc_k: hy * (hx * v00 + lx * v01) + ly * (hx * v10 + lx * v11).  16 loads instead of 36, no upsampled tensor in HBM.
 template <bool PLANES, bool UPS = false>
 __global__ __launch_bounds__(256) void wino43_in_k(const float *__restrict__ x, float *__restrict__ V, int H, int W, int C4,
@@ -459,7 +458,7 @@ __global__ __launch_bounds__(256) void wino43_out_k(const float *__restrict__ Mm
     f32x4 sc = {1.f, 1.f, 1.f, 1.f}, bi = {0.f, 0.f, 0.f, 0.f};
     if (scale) sc = *reinterpret_cast<const f32x4 *>(scale + n4 * 4);
     if (bias) bi = *reinterpret_cast<const f32x4 *>(bias + n4 * 4);
-    const float slope = act == YMI_ACT_RELU ? 0.f : (act == YMI_ACT_LEAKY01 ? 0.1f : 1.f);
+    const float slope = ymi_act_slope(act);
 #pragma unroll
     for (int iy = 0; iy < 4; ++iy)           // values first, stores last (see wino_out_k)
 #pragma unroll
@@ -517,8 +516,8 @@ __global__ __launch_bounds__(256) void wino43_out_proj_k(const float *__restrict
   f32x4 sc = {1.f, 1.f, 1.f, 1.f}, bi = {0.f, 0.f, 0.f, 0.f};
   if (scale) sc = *reinterpret_cast<const f32x4 *>(scale + lane * 4);
   if (bias) bi = *reinterpret_cast<const f32x4 *>(bias + lane * 4);
-  const float slope = act == YMI_ACT_RELU ? 0.f : (act == YMI_ACT_LEAKY01 ? 0.1f : 1.f);
-  const float slope2 = pp.act == YMI_ACT_RELU ? 0.f : (pp.act == YMI_ACT_LEAKY01 ? 0.1f : 1.f);
+  const float slope = ymi_act_slope(act);
+  const float slope2 = ymi_act_slope(pp.act);
   float am = 0.f;
   for (long tl = (long)blockIdx.x * 4 + wave; tl < T; tl += (long)gridDim.x * 4) {
     const unsigned tu = (unsigned)tl, ru = tu / (unsigned)tw, bu = ru / (unsigned)th;

@@ -20,9 +20,8 @@
 // which launch, ramp, tail and the split-K second pass are most; the tuner picks per shape.
 // Arithmetic: the fp16x2 scheme of the other tiles (x * s = h + l, s a power of two from the tensor's magnitude bound; products
 // h*l, l*h, h*h; fp32 accumulation), same filter planes, same scale_h2.
-#include "common.h"
+#include "gemm_h2.h"
 #include <type_traits>
-#include "../../include/yolact_amd.h"
 
 int ymi_internal_prof_begin(double flops, int tile, int kind, hipStream_t s);
 void ymi_internal_prof_end(int idx, hipStream_t s);
@@ -31,15 +30,11 @@ int ymi_internal_splitk_fixup(const float *part, long gstride, int S, long M, in
                               hipStream_t s);
 
 namespace {
+using namespace ymi_h2;
 
-constexpr int BK = 32;
-constexpr unsigned OOB = 0x80000000u;   // buffer offset >= num_records: the load returns zeros
 constexpr int WS_LDS_MAX = 64 * 1024;   // filter bytes of a block's K range: two blocks per CU at the maximum
 
-typedef __attribute__((address_space(3))) void *lds_ptr_t;
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-struct Split2 { f16x8 h, l; };
 
 struct WsParams {
   const float *x, *scale_h2, *bias, *x_amax;
@@ -65,8 +60,8 @@ void ws_h2_k(const WsParams p) {
   const int tile_m = ymi_xcd_remap(blockIdx.x, gridDim.x);
   const int m_wave = (tile_m * NW + wave) * (MT * 16);
 
-  const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc((void *)p.x, 0, (int)p.x_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc((void *)p.w_h2, 0, (int)(2 * p.w_plane), 0x00020000);
+  const __amdgpu_buffer_rsrc_t xrs = buf_rsrc(p.x, p.x_bytes);
+  const __amdgpu_buffer_rsrc_t wrs = buf_rsrc(p.w_h2, 2 * p.w_plane);
 
   float sA, invA;
   ymi_h2_scale(ymi_amax_read(p.x_amax), sA, invA);
@@ -152,7 +147,7 @@ void ws_h2_k(const WsParams p) {
   request(std::integral_constant<int, 0>{});
   if constexpr (D > 1) request(std::integral_constant<int, 1>{});
   if constexpr (D > 2) request(std::integral_constant<int, 2>{});
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * MT * D) : "memory");
+  YMI_WAIT_VM(2 * MT * D);
   __syncthreads();
   if (m_wave >= p.M) return;                            // a wave past the last row (ragged last block): nothing to multiply
 
@@ -163,15 +158,7 @@ void ws_h2_k(const WsParams p) {
 #pragma unroll
     for (int i = 0; i < MT; ++i) {
 #pragma unroll
-      for (int q = 0; q < 2; ++q) {
-        const f32x4 v = ring[S][i][q] * sA;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const _Float16 h = (_Float16)v[e];
-          fa[i].h[4 * q + e] = h;
-          fa[i].l[4 * q + e] = (_Float16)(v[e] - (float)h);
-        }
-      }
+      for (int q = 0; q < 2; ++q) split4h(ring[S][i][q], sA, fa[i].h, fa[i].l, 4 * q);
     }
     request(slot_c);                                    // chunk st + D into the registers just freed
     const int kc = st < my_nk ? st : my_nk - 1;         // (a padding step multiplies zeros by the last chunk's filters)
@@ -201,7 +188,7 @@ void ws_h2_k(const WsParams p) {
   }
 
   // ---- epilogue: lane holds channels 16 j + 4 g .. + 3 of pixel lr of row tile i ---------------------------------------------
-  const float slope = p.act == YMI_ACT_RELU ? 0.f : (p.act == YMI_ACT_LEAKY01 ? 0.1f : 1.f);
+  const float slope = ymi_act_slope(p.act);
   float am = 0.f;
   float *ybase = p.y + (size_t)blockIdx.y * p.y_gs;
 #pragma unroll

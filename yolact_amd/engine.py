@@ -471,6 +471,18 @@ class _OpList(list):
         self._bump(); list.extend(self, it)
 
 
+def _split_k_ids(tid, blocks, nk, Cout):
+    """tid + 256 * S for the chunk-aligned K splits S worth measuring on a grid of `blocks` blocks that alone leaves CUs idle: ranges
+    of at least 4 chunks, none empty, 128 .. 1100 blocks in all."""
+    out = []
+    if blocks < 400 and Cout % 4 == 0:
+        for S in (2, 3, 4, 5, 6, 8, 9, 12, 16):
+            per = -(-nk // S)                             # chunks per range (the last range may be shorter, never empty)
+            if per >= 4 and per * (S - 1) < nk and 128 <= blocks * S <= 1100:
+                out.append(tid + 256 * S)
+    return out
+
+
 class Plan:
     def __init__(self, net, B, H, W, device, dry_two_streams=False):
         """`dry_two_streams`: emit the two-stream op list (fork / join markers, per-stream arenas) without creating HIP
@@ -1619,12 +1631,7 @@ class Plan:
                 continue                                  # (32-column tiles: the Cout <= 32 layers, and nothing else for those)
             tid = t | L.TILE_H2 | L.TILE_DCNP
             out.append(tid)
-            blocks = -(-M // bm) * -(-d.Cout // bn)
-            if blocks < 400 and d.Cout % 4 == 0:
-                for S in (2, 3, 4, 5, 6, 8, 9, 12, 16):
-                    per = -(-nk // S)                     # chunks per range (the last range may be shorter, never empty)
-                    if per >= 4 and per * (S - 1) < nk and 128 <= blocks * S <= 1100:
-                        out.append(tid + 256 * S)
+            out += _split_k_ids(tid, -(-M // bm) * -(-d.Cout // bn), nk, d.Cout)
         return out
 
     @staticmethod
@@ -1664,12 +1671,7 @@ class Plan:
                 continue
             tid = t | L.TILE_H2 | L.TILE_DCNP
             out.append(tid)
-            blocks = -(-M // bm) * -(-d.Cout // bn)
-            if blocks < 400 and d.Cout % 4 == 0:
-                for S in (2, 3, 4, 5, 6, 8, 9, 12, 16):
-                    per = -(-nk // S)
-                    if per >= 4 and per * (S - 1) < nk and 128 <= blocks * S <= 1100:
-                        out.append(tid + 256 * S)
+            out += _split_k_ids(tid, -(-M // bm) * -(-d.Cout // bn), nk, d.Cout)
         return out
 
     @staticmethod
