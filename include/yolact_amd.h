@@ -561,6 +561,42 @@ typedef struct ymi_dcn_bwd_desc {
 } ymi_dcn_bwd_desc;
 int ymi_dcn_v2_backward_f32(const ymi_dcn_bwd_desc *d, void *stream);
 
+/* -- lincomb mask loss 'M' with gradients (layers/modules/multibox_loss.py:499-627,650; csrc/mask_loss.hip; additive at ABI 9) --
+ * The mask term of MultiBoxLoss for the switches both shipped base configs train with (mask_proto_crop,
+ * mask_proto_normalize_emulate_roi_pooling, binarised downsampled GT, sigmoid), for a whole batch in one call:
+ *     x = sum_k proto[b,r,c,k] coef[j,k],  p = sigmoid(x),  q = inside_j(r,c) ? p : 0        (crop window: box_utils.py:328-373, padding 1)
+ *     l = -(t max(log q, -100) + (1 - t) max(log(1 - q), -100)),  L_j = sum_{r,c} l
+ *     roi_norm: L_j = L_j / ((b2 - b0) mw) / ((b3 - b1) mh) * (crop ? mh mw : 1)
+ *     loss = alpha / mh / mw * sum_j weight_j L_j
+ * and, where asked, d loss / d proto and d loss / d coef (dl/dx = inside ? p - t : 0) from the same pass: no tensor of mh*mw*N
+ * elements exists.  Every element of every output is written by the call (zeros for images without instances); N = 0 is legal
+ * (loss 0, d_proto 0).  No floating-point atomics: the same inputs give the same bits.  For |x| > ~17, where the reference's fp32
+ * sigmoid saturates, l = min(softplus, 100) and dl/dx = p - t (finite).
+ * YMI_ESHAPE: K != 32, mh*mw >= 2^26, N >= 2^24, proto / d_proto / ws not 16-byte aligned; YMI_EARG: B outside 1..65535, mh / mw < 1,
+ * N < 0, G < 1 with N > 0, crop / roi_norm not 0 / 1; YMI_ENULL: proto, img_off or loss NULL, or (N > 0) coef, box, gt, gt_idx,
+ * weight or ws NULL.  No error path launches anything. */
+typedef struct ymi_mask_loss_desc {
+  const float *proto;      /* [B,mh,mw,K] NHWC, the protonet's output layout */
+  const float *coef;       /* [N,K] coefficient rows of the positives, image by image */
+  const float *box;        /* [N,4] relative point form (x1, y1, x2, y2): the rows of gt_box_t */
+  const uint8_t *gt;       /* [G,mh,mw] 0 / non-zero: the downsampled, binarised GT masks of the batch */
+  const int32_t *gt_idx;   /* [N] row of gt of each instance (clamped to 0..G-1) */
+  const int32_t *img_off;  /* [B+1] instances of image b are [img_off[b], img_off[b+1]).  PRECONDITION (device data, not checked):
+                            * img_off[0] = 0, img_off[B] = N, non-decreasing — an instance no image covers has no partial sums, and
+                            * loss, loss_inst and d_coef would then be summed from unwritten workspace (no access is out of bounds) */
+  const float *weight;     /* [N] old_num_pos / num_pos of the instance's image (multibox_loss.py:624-625) */
+  float *loss;             /* [1] */
+  float *loss_inst;        /* [N] L_j (after roi_norm, before weight); may be NULL */
+  float *d_proto;          /* [B,mh,mw,K]; may be NULL */
+  float *d_coef;           /* [N,K]; may be NULL */
+  void *ws;                /* ymi_workspace_bytes(YMI_WS_MASK_LOSS, desc) bytes, 16-byte aligned */
+  int32_t B, mh, mw, K, N, G;
+  int32_t crop, roi_norm;  /* 0 / 1: cfg.mask_proto_crop, cfg.mask_proto_normalize_emulate_roi_pooling */
+  float alpha;             /* cfg.mask_alpha */
+  int32_t _pad0;
+} ymi_mask_loss_desc;
+int ymi_mask_loss_f32(const ymi_mask_loss_desc *d, void *stream);
+
 /* -- ResNet stem in one launch (backbone.py:126-133 + the layout change of yolact.py:564) ---------------------------------
  * x [B,3,H,W] NCHW fp32 (the normalised image) -> conv 7x7 / 2 / pad 3 (3 -> 64) + folded BN + ReLU -> max-pool 3x3 / 2 / pad 1
  * -> y [B,Hp,Wp,64] NHWC fp32, Hp = ((H - 1) / 2 + 1 - 1) / 2 + 1.  The 64-channel stem output stays in LDS (csrc/stem.hip).
@@ -659,8 +695,10 @@ enum {
   YMI_WS_DETECT_GREEDY = 13,    /* desc: ymi_detect_desc -> ymi_detect_greedy_ws.ws: boxes [B,P,4] floats, survivor keys / priors
                                  * [B,(C-1)*max_det] 8 + 4 bytes, large-K candidate keys [B,C-1,P] 8 bytes; each part 256-byte aligned */
   YMI_WS_JPEG_ENC = 14,         /* desc: ymi_jpeg_enc_desc, h / w / subsampling read -> ymi_jpeg_enc_desc.ws */
-  YMI_WS_JPEG_ENC_OUT = 15      /* desc: ymi_jpeg_enc_desc, same fields -> least ymi_jpeg_enc_desc.out_capacity: an upper bound of
+  YMI_WS_JPEG_ENC_OUT = 15,     /* desc: ymi_jpeg_enc_desc, same fields -> least ymi_jpeg_enc_desc.out_capacity: an upper bound of
                                  * the stuffed scan + EOI for ANY pixels (416 bytes per coded 8x8 block + 2) */
+  YMI_WS_MASK_LOSS = 16         /* desc: ymi_mask_loss_desc, mh / mw / N read -> ymi_mask_loss_desc.ws: per-tile partial sums of
+                                 * d_coef and L_j, ceil(mh*mw / 256) * N * 33 + N floats (+ 256 bytes: never empty) */
 };
 typedef struct { int32_t A, B; int64_t n; } ymi_mask_iou_shape;
 typedef struct { int32_t N, h, w, cap; } ymi_rle_shape;      /* cap <= 0: the safe capacity h*w + 1 */

@@ -112,6 +112,15 @@ class DcnBwdDesc(C.Structure):
                 ('ldo', C.c_int32), ('mask_is_prob', C.c_int32), ('om_layout', C.c_int32), ('_pad0', C.c_int32)]
 
 
+class MaskLossDesc(C.Structure):
+    """include/yolact_amd.h ymi_mask_loss_desc."""
+    _fields_ = [('proto', C.c_void_p), ('coef', C.c_void_p), ('box', C.c_void_p), ('gt', C.c_void_p), ('gt_idx', C.c_void_p),
+                ('img_off', C.c_void_p), ('weight', C.c_void_p),
+                ('loss', C.c_void_p), ('loss_inst', C.c_void_p), ('d_proto', C.c_void_p), ('d_coef', C.c_void_p), ('ws', C.c_void_p),
+                ('B', C.c_int32), ('mh', C.c_int32), ('mw', C.c_int32), ('K', C.c_int32), ('N', C.c_int32), ('G', C.c_int32),
+                ('crop', C.c_int32), ('roi_norm', C.c_int32), ('alpha', C.c_float), ('_pad0', C.c_int32)]
+
+
 class DetectDesc(C.Structure):
     _fields_ = [('conf', C.c_void_p), ('loc', C.c_void_p), ('coef', C.c_void_p), ('priors', C.c_void_p),
                 ('B', C.c_int32), ('P', C.c_int32), ('C', C.c_int32), ('D', C.c_int32),
@@ -201,7 +210,8 @@ class RleShape(C.Structure):
 
 # ymi_workspace_bytes selectors (include/yolact_amd.h YMI_WS_*)
 (WS_WINO_V, WS_WINO_M, WS_SPLITK, WS_MASK_IOU, WS_JPEG_COEFS, WS_JPEG_PLANES, WS_DETECT_SCORES_T, WS_DETECT_PER_PRIOR,
- WS_DETECT_CAND, WS_DETECT_REC, WS_AMAX_SLOT, WS_RLE_COUNTS, WS_DETECT_GREEDY, WS_JPEG_ENC, WS_JPEG_ENC_OUT) = range(1, 16)
+ WS_DETECT_CAND, WS_DETECT_REC, WS_AMAX_SLOT, WS_RLE_COUNTS, WS_DETECT_GREEDY, WS_JPEG_ENC, WS_JPEG_ENC_OUT,
+ WS_MASK_LOSS) = range(1, 17)
 
 EFORMAT, EUNSUPPORTED = -4, -5
 
@@ -232,6 +242,7 @@ SYMBOLS = [
     ('ymi_boxes_to_pixels', C.c_int, [_P, _P, _I, _I, _I, _P]),
     ('ymi_dcn_v2_forward_f32', C.c_int, [C.POINTER(DcnDesc), _P]),
     ('ymi_dcn_v2_backward_f32', C.c_int, [C.POINTER(DcnBwdDesc), _P]),
+    ('ymi_mask_loss_f32', C.c_int, [C.POINTER(MaskLossDesc), _P]),
     ('ymi_composite_masks_u8', C.c_int, [_P, _P, _P, _I, _I, _I, _F, _P, _P]),
     ('ymi_mask_iou_f32', C.c_int, [_P, _P, _I, _I, C.c_long, _I, _P, _P, _P]),
     ('ymi_jaccard_f32', C.c_int, [_P, _P, _I, _I, _I, _P, _P]),

@@ -1,7 +1,7 @@
 """Configuration for the YOLACT inference hot path.
 
-Only the fields that `Yolact.forward`, `Detect` and `postprocess` READ are modelled
-here (reference: data/config.py:61-100 `Config`, :417-648 `coco_base_config`,
+Only the fields that `Yolact.forward`, `Detect`, `postprocess` and `lincomb_mask_loss` READ
+are modelled here (reference: data/config.py:61-100 `Config`, :417-648 `coco_base_config`,
 :656-806 shipped model configs, :810-825 `cfg`/`set_cfg`).  Training, dataset and
 augmentation fields are out of scope for this tier.
 
@@ -77,6 +77,11 @@ _common = Cfg(
     use_semantic_segmentation_loss=True, freeze_bn=False,
     use_maskiou=False, maskiou_net=[], rescore_mask=False, rescore_bbox=False,
     fpn=_fpn, max_size=550,
+    # the mask term of the training loss (layers/mask_loss.py; data/config.py coco_base_config / yolact_base_config)
+    mask_alpha=6.125, masks_to_train=100, mask_proto_crop=True, mask_proto_normalize_emulate_roi_pooling=True,
+    mask_proto_binarize_downsampled_gt=True, mask_proto_crop_with_pred_box=False, mask_proto_remove_empty_masks=False,
+    mask_proto_reweight_mask_loss=False, mask_proto_normalize_mask_loss_by_sqrt_area=False, mask_proto_double_loss=False,
+    mask_proto_coeff_diversity_loss=False,
 )
 
 _R50 = ([3, 4, 6, 3],)
@@ -98,7 +103,7 @@ CONFIGS = {
         backbone=_backbone('ResNet101', 'resnet', _R101, [1, 2, 3],
                            [[int(s[0] / 550 * 400)] for s in _base_scales], True))),
     'yolact_im700_config': _common.copy(dict(
-        name='yolact_im700', max_size=700,
+        name='yolact_im700', max_size=700, masks_to_train=300,
         backbone=_backbone('ResNet101', 'resnet', _R101, [1, 2, 3],
                            [[int(s[0] / 550 * 700)] for s in _base_scales], True))),
 }
