@@ -597,6 +597,51 @@ typedef struct ymi_mask_loss_desc {
 } ymi_mask_loss_desc;
 int ymi_mask_loss_f32(const ymi_mask_loss_desc *d, void *stream);
 
+/* -- MultiBoxLoss target assignment and the box loss 'B' (layers/box_utils.py:159-265 match / encode, layers/modules/
+ * multibox_loss.py:84-145; csrc/match.hip; additive at ABI 9) ------------------------------------------------------------------
+ * For use_prediction_matching = use_change_matching = use_yolo_regressors = False, a whole batch in one call and four launches:
+ * every prior takes the GT of the largest jaccard overlap (fp32, the reference's operation order, no FMA contraction, IEEE
+ * division: the bits of torch's CPU jaccard), then the reference's greedy loop forces each GT onto its best free prior
+ * (overlap 2), then conf = label + 1, -1 below pos_thresh, 0 below neg_thresh, -1 for a non-positive whose crowd ratio
+ * inter / area(prior) exceeds crowd_thresh (skipped for images without crowds and for crowd_thresh >= 1).  Every arg-max keeps
+ * the LOWEST index among equal values.  Thresholds are compared in fp32.  loc_t = encode(gt_box_t, priors), variances 0.1 / 0.2.
+ * With loc_data: loss = bbox_alpha * sum over positives of smooth_l1(loc_data - loc_t) (beta 1), and d_loc = bbox_alpha *
+ * clamp(loc_data - loc_t, -1, 1) at positives, +0.0f elsewhere.  No atomics: the same inputs give the same bits.
+ * The offsets are given twice: on the device for the kernels and on the host for this function, which checks the host copy (the
+ * kernels clamp what they read, so that a device copy that differs cannot make an access out of bounds).
+ * YMI_EARG: B outside 1..65535, P < 1, G < 1, Gc < 0, offsets that do not start at 0, end at G (Gc) or decrease, an image with
+ * no GT or with more GTs than P, d_loc or loss without loc_data; YMI_ESHAPE: P, G or Gc >= 2^24, priors / truth / crowd /
+ * loc_data / loc_t / gt_box_t / d_loc / ws not 16-byte aligned; YMI_ENULL: a required pointer NULL (crowd, crowd_off and
+ * crowd_off_host only with Gc > 0).  No error path launches anything. */
+typedef struct ymi_match_desc {
+  const float *priors;            /* [P,4] centre-size form (cx, cy, w, h) */
+  const float *truth;             /* [G,4] point form, the batch's non-crowd GT boxes image by image */
+  const int32_t *label;           /* [G] class of each GT (conf_t = label + 1) */
+  const int32_t *gt_off;          /* DEVICE [B+1]: the GTs of image b are [gt_off[b], gt_off[b+1]) */
+  const int32_t *gt_off_host;     /* HOST   [B+1]: the same values */
+  const float *crowd;             /* [Gc,4] point form crowd boxes; NULL when Gc = 0 */
+  const int32_t *crowd_off;       /* DEVICE [B+1]; NULL when Gc = 0 */
+  const int32_t *crowd_off_host;  /* HOST   [B+1]; NULL when Gc = 0 */
+  const float *loc_data;          /* [B,P,4] predicted regressions; may be NULL (no loss, no d_loc) */
+  float *loc_t;                   /* [B,P,4] */
+  float *gt_box_t;                /* [B,P,4] truth[idx_t] */
+  int32_t *conf_t;                /* [B,P] class + 1, 0 background, -1 neutral */
+  int32_t *idx_t;                 /* [B,P] matched GT, counted within the image */
+  uint8_t *pos;                   /* [B,P] conf_t > 0 */
+  int32_t *num_pos;               /* [B] */
+  float *d_loc;                   /* [B,P,4]; may be NULL */
+  float *loss;                    /* [1]; may be NULL */
+  void *ws;                       /* ymi_workspace_bytes(YMI_WS_MATCH, desc) bytes, 16-byte aligned */
+  int32_t B, P, G, Gc;
+  float pos_thresh, neg_thresh, crowd_thresh, bbox_alpha;
+} ymi_match_desc;
+int ymi_match_f32(const ymi_match_desc *d, void *stream);
+/* The box loss of given targets: loc_data, loc_t [B,P,4], pos [B,P] 0 / non-zero -> loss [1] and (may be NULL) d_loc [B,P,4], the
+ * loss half of ymi_match_f32 with the same partial sums, hence the same bits.  ws: ymi_workspace_bytes(YMI_WS_BOX_LOSS, desc)
+ * bytes for a ymi_match_desc with B and P set.  Errors as above. */
+int ymi_box_loss_f32(const float *loc_data, const float *loc_t, const uint8_t *pos, int B, int P, float bbox_alpha, float *loss,
+                     float *d_loc, void *ws, void *stream);
+
 /* -- ResNet stem in one launch (backbone.py:126-133 + the layout change of yolact.py:564) ---------------------------------
  * x [B,3,H,W] NCHW fp32 (the normalised image) -> conv 7x7 / 2 / pad 3 (3 -> 64) + folded BN + ReLU -> max-pool 3x3 / 2 / pad 1
  * -> y [B,Hp,Wp,64] NHWC fp32, Hp = ((H - 1) / 2 + 1 - 1) / 2 + 1.  The 64-channel stem output stays in LDS (csrc/stem.hip).
@@ -697,8 +742,12 @@ enum {
   YMI_WS_JPEG_ENC = 14,         /* desc: ymi_jpeg_enc_desc, h / w / subsampling read -> ymi_jpeg_enc_desc.ws */
   YMI_WS_JPEG_ENC_OUT = 15,     /* desc: ymi_jpeg_enc_desc, same fields -> least ymi_jpeg_enc_desc.out_capacity: an upper bound of
                                  * the stuffed scan + EOI for ANY pixels (416 bytes per coded 8x8 block + 2) */
-  YMI_WS_MASK_LOSS = 16         /* desc: ymi_mask_loss_desc, mh / mw / N read -> ymi_mask_loss_desc.ws: per-tile partial sums of
+  YMI_WS_MASK_LOSS = 16,        /* desc: ymi_mask_loss_desc, mh / mw / N read -> ymi_mask_loss_desc.ws: per-tile partial sums of
                                  * d_coef and L_j, ceil(mh*mw / 256) * N * 33 + N floats (+ 256 bytes: never empty) */
+  YMI_WS_MATCH = 17,            /* desc: ymi_match_desc, B / P / G read -> ymi_match_desc.ws: per tile and GT the best (overlap,
+                                 * prior), per image and prior the best (overlap, GT), crowd ratio and forced GT, row state, per-tile
+                                 * counts and sums: 4 * (2 T G + 4 B P + 2 G + 2 B T) bytes, T = ceil(P / 256), each part padded to 16 */
+  YMI_WS_BOX_LOSS = 18          /* desc: ymi_match_desc, B / P read -> ymi_box_loss_f32's ws: 2 * 4 B T bytes, each part padded to 16 */
 };
 typedef struct { int32_t A, B; int64_t n; } ymi_mask_iou_shape;
 typedef struct { int32_t N, h, w, cap; } ymi_rle_shape;      /* cap <= 0: the safe capacity h*w + 1 */

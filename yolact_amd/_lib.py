@@ -121,6 +121,17 @@ class MaskLossDesc(C.Structure):
                 ('crop', C.c_int32), ('roi_norm', C.c_int32), ('alpha', C.c_float), ('_pad0', C.c_int32)]
 
 
+class MatchDesc(C.Structure):
+    """include/yolact_amd.h ymi_match_desc."""
+    _fields_ = [('priors', C.c_void_p), ('truth', C.c_void_p), ('label', C.c_void_p), ('gt_off', C.c_void_p),
+                ('gt_off_host', C.c_void_p), ('crowd', C.c_void_p), ('crowd_off', C.c_void_p), ('crowd_off_host', C.c_void_p),
+                ('loc_data', C.c_void_p), ('loc_t', C.c_void_p), ('gt_box_t', C.c_void_p), ('conf_t', C.c_void_p),
+                ('idx_t', C.c_void_p), ('pos', C.c_void_p), ('num_pos', C.c_void_p), ('d_loc', C.c_void_p), ('loss', C.c_void_p),
+                ('ws', C.c_void_p),
+                ('B', C.c_int32), ('P', C.c_int32), ('G', C.c_int32), ('Gc', C.c_int32),
+                ('pos_thresh', C.c_float), ('neg_thresh', C.c_float), ('crowd_thresh', C.c_float), ('bbox_alpha', C.c_float)]
+
+
 class DetectDesc(C.Structure):
     _fields_ = [('conf', C.c_void_p), ('loc', C.c_void_p), ('coef', C.c_void_p), ('priors', C.c_void_p),
                 ('B', C.c_int32), ('P', C.c_int32), ('C', C.c_int32), ('D', C.c_int32),
@@ -211,7 +222,7 @@ class RleShape(C.Structure):
 # ymi_workspace_bytes selectors (include/yolact_amd.h YMI_WS_*)
 (WS_WINO_V, WS_WINO_M, WS_SPLITK, WS_MASK_IOU, WS_JPEG_COEFS, WS_JPEG_PLANES, WS_DETECT_SCORES_T, WS_DETECT_PER_PRIOR,
  WS_DETECT_CAND, WS_DETECT_REC, WS_AMAX_SLOT, WS_RLE_COUNTS, WS_DETECT_GREEDY, WS_JPEG_ENC, WS_JPEG_ENC_OUT,
- WS_MASK_LOSS) = range(1, 17)
+ WS_MASK_LOSS, WS_MATCH, WS_BOX_LOSS) = range(1, 19)
 
 EFORMAT, EUNSUPPORTED = -4, -5
 
@@ -243,6 +254,8 @@ SYMBOLS = [
     ('ymi_dcn_v2_forward_f32', C.c_int, [C.POINTER(DcnDesc), _P]),
     ('ymi_dcn_v2_backward_f32', C.c_int, [C.POINTER(DcnBwdDesc), _P]),
     ('ymi_mask_loss_f32', C.c_int, [C.POINTER(MaskLossDesc), _P]),
+    ('ymi_match_f32', C.c_int, [C.POINTER(MatchDesc), _P]),
+    ('ymi_box_loss_f32', C.c_int, [_P, _P, _P, _I, _I, _F, _P, _P, _P, _P]),
     ('ymi_composite_masks_u8', C.c_int, [_P, _P, _P, _I, _I, _I, _F, _P, _P]),
     ('ymi_mask_iou_f32', C.c_int, [_P, _P, _I, _I, C.c_long, _I, _P, _P, _P]),
     ('ymi_jaccard_f32', C.c_int, [_P, _P, _I, _I, _I, _P, _P]),

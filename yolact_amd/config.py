@@ -82,6 +82,9 @@ _common = Cfg(
     mask_proto_binarize_downsampled_gt=True, mask_proto_crop_with_pred_box=False, mask_proto_remove_empty_masks=False,
     mask_proto_reweight_mask_loss=False, mask_proto_normalize_mask_loss_by_sqrt_area=False, mask_proto_double_loss=False,
     mask_proto_coeff_diversity_loss=False,
+    # target assignment and the box term (layers/match.py; data/config.py:443,553,600,620,698-701)
+    positive_iou_threshold=0.5, negative_iou_threshold=0.4, crowd_iou_threshold=0.7, bbox_alpha=1.5, train_boxes=True,
+    use_prediction_matching=False, use_change_matching=False,
 )
 
 _R50 = ([3, 4, 6, 3],)

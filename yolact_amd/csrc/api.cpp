@@ -7,6 +7,8 @@ extern "C" {
 int64_t ymi_detect_greedy_layout(const ymi_detect_desc *d, int64_t off[4]);   // csrc/detect_greedy.hip
 int64_t ymi_jpeg_enc_layout(int h, int w, int sub, int64_t off[8], int64_t *out_bound);   // csrc/jpeg_enc_host.cpp
 int64_t ymi_mask_loss_ws_bytes(const ymi_mask_loss_desc *d);                  // csrc/mask_loss.hip
+int64_t ymi_match_ws_bytes(const ymi_match_desc *d);                          // csrc/match.hip
+int64_t ymi_box_loss_ws_bytes(const ymi_match_desc *d);                       // csrc/match.hip
 
 int ymi_abi_version(void) { return YMI_ABI_VERSION; }
 
@@ -76,6 +78,8 @@ int64_t ymi_workspace_bytes(int what, const void *desc) {
       return total < 0 ? total : (what == YMI_WS_JPEG_ENC ? total : bound);
     }
     case YMI_WS_MASK_LOSS: return ymi_mask_loss_ws_bytes((const ymi_mask_loss_desc *)desc);
+    case YMI_WS_MATCH: return ymi_match_ws_bytes((const ymi_match_desc *)desc);
+    case YMI_WS_BOX_LOSS: return ymi_box_loss_ws_bytes((const ymi_match_desc *)desc);
     case YMI_WS_RLE_COUNTS: {
       const ymi_rle_shape *d = (const ymi_rle_shape *)desc;
       if (d->N < 0 || d->h < 1 || d->w < 1) return -1;

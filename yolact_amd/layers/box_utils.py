@@ -1,5 +1,5 @@
 """The box helpers eval.py imports from layers.box_utils (eval.py:4): jaccard, center_size, mask_iou, plus
-crop / sanitize_coordinates.  These run in eval.py's metric code, downstream of the hot path,
+crop / sanitize_coordinates, and the training side's encode / match (box_utils.py:159-265).  These run in eval.py's metric code, downstream of the hot path,
 on whatever device the caller's tensors live; they are thin torch expressions with the reference's op order
 (box_utils.py:20-113, :327-373) — plumbing, not the accelerated path.
 """
@@ -114,3 +114,32 @@ def crop(masks, boxes, padding: int = 1):
     rows = torch.arange(h, device=masks.device, dtype=x1.dtype).view(-1, 1, 1)
     inside = (cols >= x1.view(1, 1, -1)) & (cols < x2.view(1, 1, -1)) & (rows >= y1.view(1, 1, -1)) & (rows < y2.view(1, 1, -1))
     return masks * inside.float()
+
+
+def encode(matched, priors, use_yolo_regressors: bool = False):
+    """box_utils.py:230-265 in plain torch: matched [P,4] point form, priors [P,4] centre-size -> the regression targets."""
+    if use_yolo_regressors:
+        boxes = center_size(matched)
+        return torch.cat((boxes[:, :2] - priors[:, :2], torch.log(boxes[:, 2:] / priors[:, 2:])), 1)
+    variances = [0.1, 0.2]
+    g_cxcy = (matched[:, :2] + matched[:, 2:]) / 2 - priors[:, :2]
+    g_cxcy = g_cxcy / (variances[0] * priors[:, 2:])
+    g_wh = (matched[:, 2:] - matched[:, :2]) / priors[:, 2:]
+    g_wh = torch.log(g_wh) / variances[1]
+    return torch.cat([g_cxcy, g_wh], 1)
+
+
+def match(pos_thresh, neg_thresh, truths, priors, labels, crowd_boxes, loc_t, conf_t, idx_t, idx, loc_data):
+    """box_utils.py:159-227 with the reference's signature: fills loc_t[idx], conf_t[idx] and idx_t[idx] in place.  A one-image
+    call of the kernels behind layers.match.match_targets (csrc/match.hip); loc_data is not read (no prediction matching)."""
+    from ..config import active_cfg
+    from . import match as M
+    cfg = active_cfg()
+    M.check_switches(cfg)
+    has_crowd = crowd_boxes is not None and crowd_boxes.size(0) > 0
+    out = M._launch(priors, truths, labels, [0, truths.size(0)], crowd_boxes if has_crowd else None,
+                    [0, crowd_boxes.size(0)] if has_crowd else None, None, float(pos_thresh), float(neg_thresh),
+                    float(cfg.crowd_iou_threshold), float(cfg.bbox_alpha))
+    loc_t[idx] = out['loc_t'][0].to(loc_t.dtype)
+    conf_t[idx] = out['conf_t'][0].to(conf_t.dtype)
+    idx_t[idx] = out['idx_t'][0].to(idx_t.dtype)
