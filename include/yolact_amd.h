@@ -642,6 +642,60 @@ int ymi_match_f32(const ymi_match_desc *d, void *stream);
 int ymi_box_loss_f32(const float *loc_data, const float *loc_t, const uint8_t *pos, int B, int P, float bbox_alpha, float *loss,
                      float *d_loc, void *ws, void *stream);
 
+/* -- the class loss 'C' with online hard example mining (layers/modules/multibox_loss.py:242-296 ohem_conf_loss, for
+ * ohem_use_most_confident = use_class_balanced_conf = False; csrc/class_loss.hip; additive at ABI 9) ---------------------------
+ * A whole batch in one call and four launches, loss and gradient together:
+ *     lse = logsumexp(conf[b,i,:]) with the ROW's own maximum subtracted (the reference subtracts the batch's maximum, which is
+ *           the same function but underflows to log 0 for a row far below it)
+ *     key = lse - conf[b,i,0] for conf_t == 0, and 0 for positives (conf_t > 0) and neutrals (conf_t < 0)
+ *     n_b = min(negpos_ratio * num_pos_b, P - 1); the n_b largest keys of image b are marked, EQUAL KEYS IN PRIOR ORDER (the lowest
+ *           index wins; the reference's unstable sort leaves ties undefined); neg = marked and conf_t == 0 - a marked positive or
+ *           neutral is dropped and not replaced (:261-265)
+ *     loss = conf_alpha * sum over pos | neg of (lse - conf[b,i,conf_t])
+ *     d_conf = conf_alpha * (softmax(conf[b,i,:]) - onehot(conf_t)) on the rows of pos | neg, +0.0f on every other row
+ * The selection carries no gradient.  Every element of every output is written by the call.  No floating-point atomics: the same
+ * inputs give the same bits.  A conf_t outside -1 .. C-1 is compared before it indexes: it reads nothing and makes loss NaN.
+ * YMI_EARG: B outside 1..65535, P < 2, C outside 2..256, negpos_ratio < 0; YMI_ESHAPE: B*P*C >= 2^31, conf / d_conf / ws not
+ * 16-byte aligned; YMI_ENULL: conf, conf_t, loss, neg, num_neg or ws NULL.  No error path launches anything. */
+typedef struct ymi_class_loss_desc {
+  const float *conf;       /* [B,P,C] logits */
+  const int32_t *conf_t;   /* [B,P] class + 1, 0 background, -1 neutral (ymi_match_desc.conf_t) */
+  float *loss;             /* [1] */
+  uint8_t *neg;            /* [B,P] 0 / 1: the mined negatives */
+  int32_t *num_neg;        /* [B] */
+  float *d_conf;           /* [B,P,C]; may be NULL */
+  void *ws;                /* ymi_workspace_bytes(YMI_WS_CLASS_LOSS, desc) bytes, 16-byte aligned */
+  int32_t B, P, C;
+  int32_t negpos_ratio;    /* MultiBoxLoss's negpos_ratio (3) */
+  float conf_alpha;        /* cfg.conf_alpha */
+  int32_t _pad0;
+} ymi_class_loss_desc;
+int ymi_class_loss_f32(const ymi_class_loss_desc *d, void *stream);
+
+/* -- the semantic segmentation loss 'S' (layers/modules/multibox_loss.py:218-239; csrc/segm_loss.hip; additive at ABI 9) -------
+ * A whole batch in one call and two launches: the target of channel c at a pixel is the OR of the image's GT masks whose label is
+ * c (no target tensor exists: a thread keeps its pixel's K <= 128 classes as a bitset), then
+ *     loss = alpha / (mh mw) * sum over b, c, pixels of max(x, 0) - x t + log1p(exp(-|x|))        (BCE with logits)
+ *     d_segm = alpha / (mh mw) * (sigmoid(x) - t)
+ * An image without objects is valid (target 0), and so is G = 0.  A label outside 0 .. K-1 sets no bit and makes loss NaN.  No
+ * atomics: the same inputs give the same bits.  The offsets are given on the device and on the host as in ymi_match_desc.
+ * YMI_EARG: B outside 1..65535, K outside 1..128, mh / mw < 1, G < 0, offsets that do not start at 0, end at G or decrease;
+ * YMI_ESHAPE: B*K*mh*mw >= 2^31 (for B = K = 1: mh*mw > 2^31 - 256), segm / d_segm / ws not 16-byte aligned; YMI_ENULL: segm, gt_off, gt_off_host, loss or ws NULL,
+ * or (G > 0) gt or label NULL.  No error path launches anything. */
+typedef struct ymi_segm_loss_desc {
+  const float *segm;            /* [B,K,mh,mw] NCHW logits, the layout semantic_seg_conv produces */
+  const uint8_t *gt;            /* [G,mh,mw] 0 / non-zero: the downsampled, binarised GT masks of the batch, image by image */
+  const int32_t *label;         /* [G] class of each mask, 0..K-1 */
+  const int32_t *gt_off;        /* DEVICE [B+1]: the masks of image b are [gt_off[b], gt_off[b+1]) */
+  const int32_t *gt_off_host;   /* HOST   [B+1]: the same values */
+  float *loss;                  /* [1] */
+  float *d_segm;                /* [B,K,mh,mw]; may be NULL */
+  void *ws;                     /* ymi_workspace_bytes(YMI_WS_SEGM_LOSS, desc) bytes, 16-byte aligned */
+  int32_t B, K, mh, mw, G;
+  float alpha;                  /* cfg.semantic_segmentation_alpha */
+} ymi_segm_loss_desc;
+int ymi_segm_loss_f32(const ymi_segm_loss_desc *d, void *stream);
+
 /* -- ResNet stem in one launch (backbone.py:126-133 + the layout change of yolact.py:564) ---------------------------------
  * x [B,3,H,W] NCHW fp32 (the normalised image) -> conv 7x7 / 2 / pad 3 (3 -> 64) + folded BN + ReLU -> max-pool 3x3 / 2 / pad 1
  * -> y [B,Hp,Wp,64] NHWC fp32, Hp = ((H - 1) / 2 + 1 - 1) / 2 + 1.  The 64-channel stem output stays in LDS (csrc/stem.hip).
@@ -747,7 +801,12 @@ enum {
   YMI_WS_MATCH = 17,            /* desc: ymi_match_desc, B / P / G read -> ymi_match_desc.ws: per tile and GT the best (overlap,
                                  * prior), per image and prior the best (overlap, GT), crowd ratio and forced GT, row state, per-tile
                                  * counts and sums: 4 * (2 T G + 4 B P + 2 G + 2 B T) bytes, T = ceil(P / 256), each part padded to 16 */
-  YMI_WS_BOX_LOSS = 18          /* desc: ymi_match_desc, B / P read -> ymi_box_loss_f32's ws: 2 * 4 B T bytes, each part padded to 16 */
+  YMI_WS_BOX_LOSS = 18,         /* desc: ymi_match_desc, B / P read -> ymi_box_loss_f32's ws: 2 * 4 B T bytes, each part padded to 16 */
+  YMI_WS_CLASS_LOSS = 19,       /* desc: ymi_class_loss_desc, B / P / C read -> ymi_class_loss_desc.ws: per prior the mining key and lse,
+                                 * per tile the positives and the loss partial: 4 * (2 B P + 2 B T) bytes, T = ceil(P / R),
+                                 * R = min(128, 10752 / (C | 1)) rows per tile, each part padded to 16 */
+  YMI_WS_SEGM_LOSS = 20         /* desc: ymi_segm_loss_desc, B / mh / mw read -> ymi_segm_loss_desc.ws: 4 B ceil(mh*mw / 256) bytes,
+                                 * padded to 16 */
 };
 typedef struct { int32_t A, B; int64_t n; } ymi_mask_iou_shape;
 typedef struct { int32_t N, h, w, cap; } ymi_rle_shape;      /* cap <= 0: the safe capacity h*w + 1 */

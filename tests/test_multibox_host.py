@@ -1,0 +1,103 @@
+"""MultiBoxLoss on the CPU: the oracles of the four terms, composed in tests/multibox_ref.py, are pinned to what the reference's
+own forward() computed (the `fwd` case of tests/golden/multibox.npz: crowds, neutrals, no randperm drawn); the module's surface is
+checked as far as that goes without a GPU.
+
+Golden bar: the four losses and the gradients of their sum in loc, conf, mask, proto and segm: relative error <= 1e-6 (both sides
+are fp32 on the CPU).
+"""
+import os
+import sys
+
+import pytest
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import class_loss_ref as CR  # noqa: E402
+import multibox_ref as R  # noqa: E402
+import yolact_amd  # noqa: E402
+from yolact_amd.layers.modules import MultiBoxLoss  # noqa: E402
+import yolact_amd.layers.modules.multibox_loss as MB  # noqa: E402
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+META, G = CR.load_golden()
+GOLDEN_BAR = 1e-6
+
+
+@pytest.fixture(scope='module')
+def composed():
+    return R.multibox_ref(*R.golden_forward(G, META), dtype=torch.float32)
+
+
+def test_the_forward_case_has_crowds_neutrals_and_an_open_cut(composed):
+    losses, grads, ex = composed
+    assert META['num_crowds'] == [1, 0] and torch.equal(ex['conf_t'], G['fwd_conf_t'].long())
+    assert (ex['conf_t'] < 0).any() and ex['num_pos'].min() >= 1 and ex['num_pos'].max() < 100
+    assert min(CR.cut_gaps(ex['key'].double(), ex['n'])) >= META['gap']
+
+
+def test_composed_oracles_equal_the_reference_forward(composed):
+    losses, grads, ex = composed
+    errs = {k: CR.rel_err(losses[k].view(1), G['fwd_' + k]) for k in 'BMCS'}
+    errs.update({'d_' + k: CR.rel_err(grads[k], G['fwd_d_' + k]) for k in R.NAMES})
+    print('  '.join('%s %.2e' % kv for kv in errs.items()))
+    assert max(errs.values()) <= GOLDEN_BAR, errs
+    sel = ex['neg'] | (ex['conf_t'] > 0)
+    assert not G['fwd_d_conf'][~sel].any() and G['fwd_d_conf'][sel].any(1).all()
+
+
+def test_golden_rejects_s_divided_by_num_pos():
+    losses, grads, ex = R.multibox_ref(*R.golden_forward(G, META), dtype=torch.float32, s_norm='num_pos')
+    assert CR.rel_err(losses['S'].view(1), G['fwd_S']) > 1e-2
+    assert CR.rel_err(losses['C'].view(1), G['fwd_C']) <= GOLDEN_BAR
+
+
+def test_raises_for_yolact_plus_base_config(monkeypatch):
+    cfg = yolact_amd.CONFIGS['yolact_plus_base_config'].copy()
+    monkeypatch.setattr(MB, 'active_cfg', lambda: cfg)
+    preds, targets, masks, ncs = R.golden_forward(G, META)
+    crit = MultiBoxLoss(81, 0.5, 0.4, 3)
+    with pytest.raises(NotImplementedError, match='use_maskiou'):
+        crit(None, preds, targets, masks, ncs)
+
+
+@pytest.mark.parametrize('field,value', [('use_maskiou', True), ('mask_proto_loss', 'l1'), ('mask_proto_loss', 'disj'),
+                                         ('use_class_existence_loss', True), ('train_masks', False), ('mask_type', 0),
+                                         ('use_instance_coeff', True), ('use_focal_loss', True), ('ohem_use_most_confident', True),
+                                         ('use_prediction_matching', True), ('mask_proto_double_loss', True)])
+def test_every_unsupported_switch_names_its_field(monkeypatch, field, value):
+    cfg = yolact_amd.CONFIGS['yolact_base_config'].copy({field: value})
+    with pytest.raises(NotImplementedError, match=field):
+        MB.check_switches(cfg)
+    monkeypatch.setattr(MB, 'active_cfg', lambda: cfg)
+    preds, targets, masks, ncs = R.golden_forward(G, META)
+    with pytest.raises(NotImplementedError, match=field):
+        MultiBoxLoss(81, 0.5, 0.4, 3)(None, preds, targets, masks, ncs)
+
+
+def test_every_shipped_base_config_passes_the_switches_and_carries_the_reference_values():
+    """data/config.py:468,599."""
+    for name, cfg in yolact_amd.CONFIGS.items():
+        assert cfg.mask_proto_loss is None and cfg.train_masks is True, name
+        if 'plus' not in name:
+            MB.check_switches(cfg)
+
+
+def test_cpu_tensors_raise(monkeypatch):
+    cfg = yolact_amd.CONFIGS['yolact_base_config'].copy()
+    monkeypatch.setattr(MB, 'active_cfg', lambda: cfg)
+    preds, targets, masks, ncs = R.golden_forward(G, META)
+    with pytest.raises(RuntimeError):
+        MultiBoxLoss(81, 0.5, 0.4, 3)(None, preds, targets, masks, ncs)
+
+
+def test_train_keeps_raising_and_the_shim_re_exports_the_module():
+    """`from layers.modules import MultiBoxLoss` through shim/, in a process of its own: this one's modules stay as they are."""
+    import subprocess
+    code = ('import sys; sys.path[:0] = [%r, %r]\n'
+            'from layers.modules import MultiBoxLoss as shimmed\n'
+            'from yolact_amd.layers.modules import MultiBoxLoss\n'
+            'assert shimmed is MultiBoxLoss\n' % (os.path.join(ROOT, 'shim'), ROOT))
+    subprocess.run([sys.executable, '-c', code], check=True, cwd=ROOT)
+    from yolact_amd.yolact import Yolact
+    with pytest.raises(NotImplementedError):
+        Yolact.train(object.__new__(Yolact))

@@ -132,6 +132,21 @@ class MatchDesc(C.Structure):
                 ('pos_thresh', C.c_float), ('neg_thresh', C.c_float), ('crowd_thresh', C.c_float), ('bbox_alpha', C.c_float)]
 
 
+class ClassLossDesc(C.Structure):
+    """include/yolact_amd.h ymi_class_loss_desc."""
+    _fields_ = [('conf', C.c_void_p), ('conf_t', C.c_void_p), ('loss', C.c_void_p), ('neg', C.c_void_p), ('num_neg', C.c_void_p),
+                ('d_conf', C.c_void_p), ('ws', C.c_void_p),
+                ('B', C.c_int32), ('P', C.c_int32), ('C', C.c_int32), ('negpos_ratio', C.c_int32), ('conf_alpha', C.c_float),
+                ('_pad0', C.c_int32)]
+
+
+class SegmLossDesc(C.Structure):
+    """include/yolact_amd.h ymi_segm_loss_desc."""
+    _fields_ = [('segm', C.c_void_p), ('gt', C.c_void_p), ('label', C.c_void_p), ('gt_off', C.c_void_p), ('gt_off_host', C.c_void_p),
+                ('loss', C.c_void_p), ('d_segm', C.c_void_p), ('ws', C.c_void_p),
+                ('B', C.c_int32), ('K', C.c_int32), ('mh', C.c_int32), ('mw', C.c_int32), ('G', C.c_int32), ('alpha', C.c_float)]
+
+
 class DetectDesc(C.Structure):
     _fields_ = [('conf', C.c_void_p), ('loc', C.c_void_p), ('coef', C.c_void_p), ('priors', C.c_void_p),
                 ('B', C.c_int32), ('P', C.c_int32), ('C', C.c_int32), ('D', C.c_int32),
@@ -222,7 +237,7 @@ class RleShape(C.Structure):
 # ymi_workspace_bytes selectors (include/yolact_amd.h YMI_WS_*)
 (WS_WINO_V, WS_WINO_M, WS_SPLITK, WS_MASK_IOU, WS_JPEG_COEFS, WS_JPEG_PLANES, WS_DETECT_SCORES_T, WS_DETECT_PER_PRIOR,
  WS_DETECT_CAND, WS_DETECT_REC, WS_AMAX_SLOT, WS_RLE_COUNTS, WS_DETECT_GREEDY, WS_JPEG_ENC, WS_JPEG_ENC_OUT,
- WS_MASK_LOSS, WS_MATCH, WS_BOX_LOSS) = range(1, 19)
+ WS_MASK_LOSS, WS_MATCH, WS_BOX_LOSS, WS_CLASS_LOSS, WS_SEGM_LOSS) = range(1, 21)
 
 EFORMAT, EUNSUPPORTED = -4, -5
 
@@ -256,6 +271,8 @@ SYMBOLS = [
     ('ymi_mask_loss_f32', C.c_int, [C.POINTER(MaskLossDesc), _P]),
     ('ymi_match_f32', C.c_int, [C.POINTER(MatchDesc), _P]),
     ('ymi_box_loss_f32', C.c_int, [_P, _P, _P, _I, _I, _F, _P, _P, _P, _P]),
+    ('ymi_class_loss_f32', C.c_int, [C.POINTER(ClassLossDesc), _P]),
+    ('ymi_segm_loss_f32', C.c_int, [C.POINTER(SegmLossDesc), _P]),
     ('ymi_composite_masks_u8', C.c_int, [_P, _P, _P, _I, _I, _I, _F, _P, _P]),
     ('ymi_mask_iou_f32', C.c_int, [_P, _P, _I, _I, C.c_long, _I, _P, _P, _P]),
     ('ymi_jaccard_f32', C.c_int, [_P, _P, _I, _I, _I, _P, _P]),

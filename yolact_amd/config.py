@@ -85,6 +85,10 @@ _common = Cfg(
     # target assignment and the box term (layers/match.py; data/config.py:443,553,600,620,698-701)
     positive_iou_threshold=0.5, negative_iou_threshold=0.4, crowd_iou_threshold=0.7, bbox_alpha=1.5, train_boxes=True,
     use_prediction_matching=False, use_change_matching=False,
+    # the class and segmentation terms and what MultiBoxLoss refuses (layers/class_loss.py, layers/segm_loss.py,
+    # layers/modules/multibox_loss.py; data/config.py:442,468,517,528,545,574,599)
+    conf_alpha=1, ohem_negpos_ratio=3, ohem_use_most_confident=False, use_class_balanced_conf=False,
+    semantic_segmentation_alpha=1, mask_proto_loss=None, train_masks=True,
 )
 
 _R50 = ([3, 4, 6, 3],)

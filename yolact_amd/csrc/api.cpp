@@ -9,6 +9,8 @@ int64_t ymi_jpeg_enc_layout(int h, int w, int sub, int64_t off[8], int64_t *out_
 int64_t ymi_mask_loss_ws_bytes(const ymi_mask_loss_desc *d);                  // csrc/mask_loss.hip
 int64_t ymi_match_ws_bytes(const ymi_match_desc *d);                          // csrc/match.hip
 int64_t ymi_box_loss_ws_bytes(const ymi_match_desc *d);                       // csrc/match.hip
+int64_t ymi_class_loss_ws_bytes(const ymi_class_loss_desc *d);                // csrc/class_loss.hip
+int64_t ymi_segm_loss_ws_bytes(const ymi_segm_loss_desc *d);                  // csrc/segm_loss.hip
 
 int ymi_abi_version(void) { return YMI_ABI_VERSION; }
 
@@ -80,6 +82,8 @@ int64_t ymi_workspace_bytes(int what, const void *desc) {
     case YMI_WS_MASK_LOSS: return ymi_mask_loss_ws_bytes((const ymi_mask_loss_desc *)desc);
     case YMI_WS_MATCH: return ymi_match_ws_bytes((const ymi_match_desc *)desc);
     case YMI_WS_BOX_LOSS: return ymi_box_loss_ws_bytes((const ymi_match_desc *)desc);
+    case YMI_WS_CLASS_LOSS: return ymi_class_loss_ws_bytes((const ymi_class_loss_desc *)desc);
+    case YMI_WS_SEGM_LOSS: return ymi_segm_loss_ws_bytes((const ymi_segm_loss_desc *)desc);
     case YMI_WS_RLE_COUNTS: {
       const ymi_rle_shape *d = (const ymi_rle_shape *)desc;
       if (d->N < 0 || d->h < 1 || d->w < 1) return -1;

@@ -1,7 +1,7 @@
 """MultiBoxLoss target assignment and the box loss 'B' on the HIP kernels (layers/box_utils.py:159-265 match / encode,
 layers/modules/multibox_loss.py:84-145; csrc/match.hip).
 
-    match_targets(priors, targets, num_crowds, loc_data=None)
+    match_targets(priors, targets, num_crowds, loc_data=None, pos_threshold=None, neg_threshold=None)
         -> dict(loc_t [B,P,4], conf_t [B,P] long, idx_t [B,P] long, gt_box_t [B,P,4], pos [B,P] bool, num_pos [B] long)
         the loop of multibox_loss.py:100-126 for the whole batch in one call of ymi_match_f32: `targets` is the reference's list of
         [n,5] tensors (x1, y1, x2, y2, label) with the crowd annotations last, `num_crowds` its list of crowd counts.  With
@@ -94,8 +94,9 @@ def _launch(priors, truth, label, gt_off, crowd, crowd_off, loc_data, pos_thresh
         return out
 
 
-def match_targets(priors, targets, num_crowds, loc_data=None):
-    """See the module docstring.  One launch sequence for the batch; nothing is read back to the host."""
+def match_targets(priors, targets, num_crowds, loc_data=None, pos_threshold=None, neg_threshold=None):
+    """See the module docstring.  One launch sequence for the batch; nothing is read back to the host.  pos_threshold /
+    neg_threshold override cfg.positive_iou_threshold / cfg.negative_iou_threshold (MultiBoxLoss passes its constructor's)."""
     cfg = active_cfg()
     check_switches(cfg)
     L.require_cuda(priors, 'match_targets priors')
@@ -113,7 +114,8 @@ def match_targets(priors, targets, num_crowds, loc_data=None):
         gt_off.append(gt_off[-1] + n)
         crowd_off.append(crowd_off[-1] + nc)
     out = _launch(priors, torch.cat(truths), torch.cat(labels).long(), gt_off, torch.cat(crowds) if crowds else None, crowd_off,
-                  loc_data, float(cfg.positive_iou_threshold), float(cfg.negative_iou_threshold),
+                  loc_data, float(cfg.positive_iou_threshold if pos_threshold is None else pos_threshold),
+                  float(cfg.negative_iou_threshold if neg_threshold is None else neg_threshold),
                   float(cfg.crowd_iou_threshold), float(cfg.bbox_alpha))
     res = dict(loc_t=out['loc_t'], conf_t=out['conf_t'].long(), idx_t=out['idx_t'].long(), gt_box_t=out['gt_box_t'],
                pos=out['pos'].bool(), num_pos=out['num_pos'].long())
