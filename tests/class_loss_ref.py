@@ -8,6 +8,9 @@ select deliberately WRONG variants, which the host test shows the golden file te
 """
 import torch
 
+import helpers
+from helpers import rel_err  # noqa: F401  (the tests and tools reach it as class_loss_ref.rel_err)
+
 
 def ohem_ref(conf, conf_t, ratio=3, alpha=1.0, key='lse', zero_pos=True, mine_neutrals=False, ratio_after_clamp=False):
     """conf [B,P,C], conf_t [B,P] long -> dict(loss 0-dim, neg [B,P] bool, num_neg [B], n [B] (marked per image), d_conf [B,P,C],
@@ -71,18 +74,7 @@ def open_the_cuts(conf, conf_t, ratio=3, gap=1e-3):
     raise AssertionError('could not open the cuts')
 
 
-def rel_err(a, b):
-    """max |a - b| / max |b|."""
-    a, b = a.double().reshape(-1), b.double().reshape(-1)
-    den = b.abs().max().item() if b.numel() else 0.0
-    return (a - b).abs().max().item() / (den if den > 0 else 1.0) if b.numel() else 0.0
-
-
 def load_golden():
     """tests/golden/multibox.npz (tools/make_golden_multibox.py: the reference's own results) -> (meta, dict of tensors)."""
-    import json
-    import os
-    import numpy as np
-    z = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'multibox.npz'))
-    meta = json.loads(bytes(z['meta']).decode())
-    return meta, {k: torch.from_numpy(z[k]) for k in z.files if k != 'meta'}
+    meta, z = helpers.load_golden('multibox')
+    return meta, {k: torch.tensor(v) for k, v in z.items()}

@@ -26,6 +26,28 @@ def load_golden(name):
     return meta, arrays
 
 
+def rel_err(a, b):
+    """max |a - b| / max |b| over the finite entries of b; the non-finite entries (log 0 of a zero-area GT) must be identical."""
+    a, b = a.double().reshape(-1), b.double().reshape(-1)
+    fin = torch.isfinite(b)
+    assert torch.equal(a[~fin], b[~fin]), 'non-finite entries differ'
+    if not fin.any():
+        return 0.0
+    den = b[fin].abs().max().item()
+    return (a[fin] - b[fin]).abs().max().item() / (den if den > 0 else 1.0)
+
+
+def same_bits(a, b, what=''):
+    """Two tensors, or two dicts of tensors with the same keys, hold the same bits (fp32 compared as int32: -0.0 is not +0.0)."""
+    if isinstance(a, dict):
+        assert a.keys() == b.keys()
+        for k in a:
+            same_bits(a[k], b[k], k)
+        return
+    x, y = a.detach().cpu(), b.detach().cpu()
+    assert torch.equal(x.view(torch.int32), y.view(torch.int32)) if x.dtype == torch.float32 else torch.equal(x, y), what
+
+
 def case_cfg(meta):
     cfg = CONFIGS[meta['config']].copy()
     if 'eval_mask_branch' in meta:

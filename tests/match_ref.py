@@ -6,6 +6,9 @@ keyword switches select deliberately WRONG variants, which the host test shows t
 """
 import torch
 
+import helpers
+from helpers import rel_err  # noqa: F401  (the tests and tools reach it as match_ref.rel_err)
+
 BIG = 1 << 40
 
 
@@ -126,31 +129,16 @@ def box_loss_ref(loc_data, loc_t, pos, alpha=1.5):
     return loss, torch.where(m, alpha * d.clamp(-1, 1), zero)
 
 
-def rel_err(a, b):
-    """max |a - b| / max |b| over the finite entries of b; the non-finite entries (log 0 of a zero-area GT) must be identical."""
-    a, b = a.double().reshape(-1), b.double().reshape(-1)
-    fin = torch.isfinite(b)
-    assert torch.equal(a[~fin], b[~fin]), 'non-finite entries differ'
-    if not fin.any():
-        return 0.0
-    den = b[fin].abs().max().item()
-    return (a[fin] - b[fin]).abs().max().item() / (den if den > 0 else 1.0)
-
-
 def load_golden():
     """tests/golden/match.npz (tools/make_golden_match.py: the reference's own results) -> (meta, {case name: dict of tensors});
     'targets' is the list of bundled [n,5] tensors, conf_t / idx_t are long."""
-    import json
-    import os
-    import numpy as np
-    z = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'match.npz'))
-    meta = json.loads(bytes(z['meta']).decode())
+    meta, z = helpers.load_golden('match')
     cases = {}
     for c in meta['cases']:
-        t = {k: torch.from_numpy(z['%s_%s' % (c['name'], k)]) for k in ('priors', 'loc_data', 'loc_t', 'conf_t', 'idx_t', 'gt_box_t',
+        t = {k: torch.tensor(z['%s_%s' % (c['name'], k)]) for k in ('priors', 'loc_data', 'loc_t', 'conf_t', 'idx_t', 'gt_box_t',
                                                                          'B', 'd_loc')}
         t['conf_t'], t['idx_t'] = t['conf_t'].long(), t['idx_t'].long()
-        t['targets'] = [torch.from_numpy(z['%s_targets_%d' % (c['name'], b)]) for b in range(c['B'])]
+        t['targets'] = [torch.tensor(z['%s_targets_%d' % (c['name'], b)]) for b in range(c['B'])]
         t['num_crowds'] = list(c['num_crowds'])
         cases[c['name']] = t
     return meta, cases

@@ -178,4 +178,4 @@ def test_cpu_tensors_raise(monkeypatch):
         CL.ohem_conf_loss(conf.clone().requires_grad_(True), ct)
     with pytest.raises(RuntimeError):
         CL.ohem_terms(conf, ct)
-    assert issubclass(CL._ClassLossFunction, torch.autograd.Function)
+    assert issubclass(CL.LC.LossFunction, torch.autograd.Function)

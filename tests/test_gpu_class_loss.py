@@ -17,6 +17,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import class_loss_ref as R  # noqa: E402
 import match_ref  # noqa: E402
+from helpers import same_bits  # noqa: E402
 import yolact_amd  # noqa: E402
 import yolact_amd.layers.class_loss as CL  # noqa: E402
 
@@ -82,12 +83,6 @@ def check(name, conf, ct, ratio=3, gap=GAP):
     off = out['d_conf'][~(out['neg'] | (ct > 0))]
     assert (off.view(torch.int32) == 0).all()                            # exactly +0.0f off pos | neg (no such row: the clamp case)
     return out, o64
-
-
-def same_bits(a, b):
-    for k in a:
-        x, y = a[k], b[k]
-        assert torch.equal(x.view(torch.int32), y.view(torch.int32)) if x.dtype == torch.float32 else torch.equal(x, y), k
 
 
 def test_labels_of_the_match_golden_with_positives_neutrals_and_three_images():

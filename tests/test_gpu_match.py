@@ -19,6 +19,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import match_ref as R  # noqa: E402
+from helpers import same_bits  # noqa: E402
 import yolact_amd  # noqa: E402
 import yolact_amd.layers.match as M  # noqa: E402
 
@@ -161,10 +162,7 @@ def test_batch_of_32_on_the_550_prior_set_and_reproducibility():
     out = run_gpu(priors, targets, ncs, loc_data)
     check('batch32', out, ref, want, bars)
     again = run_gpu(priors, targets, ncs, loc_data)
-    for k in out:
-        a, b = out[k], again[k]
-        same = torch.equal(a.view(torch.int32), b.view(torch.int32)) if a.dtype == torch.float32 else torch.equal(a, b)
-        assert same, k
+    same_bits(out, again)
 
 
 def test_more_gts_than_the_force_kernel_keeps_in_lds():

@@ -14,6 +14,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import class_loss_ref as CR  # noqa: E402
 import segm_loss_ref as R  # noqa: E402
+from helpers import same_bits  # noqa: E402
 import yolact_amd  # noqa: E402
 import yolact_amd.layers.segm_loss as SL  # noqa: E402
 
@@ -89,7 +90,8 @@ def test_word_edges_overlap_an_empty_image_and_70_objects():
         on = t[0, c].bool()
         assert on.any() and (d[0, c][on] <= 0).all() and (d[0, c][~on] >= 0).all()
     again = SL.segm_terms(segm.to(DEV), gt.to(DEV), label.to(DEV), off, 1.0)
-    assert torch.equal(again[0].cpu().view(torch.int32), loss.view(torch.int32)) and torch.equal(again[1].cpu().view(torch.int32), d.view(torch.int32))
+    same_bits(again[0], loss, 'S')
+    same_bits(again[1], d, 'd_segm')
 
 
 def test_a_batch_without_any_object():

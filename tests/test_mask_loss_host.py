@@ -173,4 +173,4 @@ def test_cpu_tensors_raise(monkeypatch):
                                                                     m['mh'], m['mw'], 100)
     with pytest.raises(RuntimeError):
         ML.mask_loss(t['proto'].requires_grad_(True), coef, box, gt, gt_idx, img_off, weight)
-    assert issubclass(ML._MaskLossFunction, torch.autograd.Function)
+    assert issubclass(ML.LC.LossFunction, torch.autograd.Function)

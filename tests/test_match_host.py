@@ -226,7 +226,7 @@ def test_cpu_tensors_raise(monkeypatch):
     with pytest.raises(RuntimeError):
         BU.match(0.5, 0.4, tg[:, :4], t['priors'], tg[:, 4].long(), None, torch.zeros(1, P, 4), torch.zeros(1, P).long(),
                  torch.zeros(1, P).long(), 0, t['loc_data'][0])
-    assert issubclass(M._BoxLossFunction, torch.autograd.Function)
+    assert issubclass(M.LC.LossFunction, torch.autograd.Function)
 
 
 def test_shim_re_exports_encode_and_match():

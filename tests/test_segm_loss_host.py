@@ -159,4 +159,4 @@ def test_cpu_tensors_raise(monkeypatch):
     with pytest.raises(RuntimeError):
         SL.semantic_segmentation_loss(segm, [G['fwd_masks_0'].float()[:3], G['fwd_masks_1'].float()],
                                       [G['fwd_targets_0'][:3, 4].long(), G['fwd_targets_1'][:, 4].long()])
-    assert issubclass(SL._SegmLossFunction, torch.autograd.Function)
+    assert issubclass(SL.LC.LossFunction, torch.autograd.Function)

@@ -13,7 +13,6 @@ list, so no index is read back from the device.  Recorded, not gated (DESIGN.md 
 import argparse
 import json
 import os
-import statistics
 import sys
 
 import torch
@@ -26,21 +25,7 @@ import segm_loss_ref as SR  # noqa: E402
 import yolact_amd  # noqa: E402
 from yolact_amd.layers import class_loss as CL  # noqa: E402
 from yolact_amd.layers import segm_loss as SL  # noqa: E402
-
-
-def timed(fn, warmup, reps):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        ts.append(a.elapsed_time(b) * 1e3)
-    return statistics.median(ts), min(ts)
+from dcn_bwd_probe import timed  # noqa: E402
 
 
 def main():

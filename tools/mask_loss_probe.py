@@ -11,7 +11,6 @@ composed form keeps several [138,138,100] tensors per image alive for its backwa
 import argparse
 import json
 import os
-import statistics
 import sys
 
 import torch
@@ -19,6 +18,7 @@ import torch.nn.functional as F
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from yolact_amd.layers.mask_loss import mask_loss  # noqa: E402
+from dcn_bwd_probe import timed  # noqa: E402
 
 ALPHA = 6.125
 
@@ -46,21 +46,6 @@ def composed(proto, coef, box, gt, gt_idx, img_off, weight):
         pre = pre.sum(dim=(0, 1)) / ((bx[:, 2] - bx[:, 0]) * mw) / ((bx[:, 3] - bx[:, 1]) * mh) * (mh * mw)
         total = total + torch.sum(pre * weight[j0:j1])
     return total * ALPHA / mh / mw
-
-
-def timed(fn, warmup, reps):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        ts.append(a.elapsed_time(b) * 1e3)
-    return statistics.median(ts), min(ts)
 
 
 def peak_above_inputs(fn):

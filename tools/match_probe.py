@@ -13,7 +13,6 @@ import argparse
 import ctypes as C
 import json
 import os
-import statistics
 import sys
 
 import torch
@@ -25,21 +24,7 @@ import match_ref as R  # noqa: E402
 import yolact_amd  # noqa: E402
 from yolact_amd import _lib as L  # noqa: E402
 from yolact_amd.layers import match as M  # noqa: E402
-
-
-def timed(fn, warmup, reps):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        ts.append(a.elapsed_time(b) * 1e3)
-    return statistics.median(ts), min(ts)
+from dcn_bwd_probe import timed  # noqa: E402
 
 
 def make_targets(g, n, n_crowd):

@@ -18,7 +18,7 @@
 // No floating-point atomics, no cooperative grid, no waiting between blocks: the same inputs give the same bits.  A label is
 // compared with its range before it indexes anything; one outside -1 .. C-1 makes the loss NaN.
 // Bound by memory traffic: launch 1 reads conf once, launch 3 writes d_conf once and re-reads only the selected rows.
-#include "common.h"
+#include "loss_common.h"
 #include "../../include/yolact_amd.h"
 
 #pragma clang fp contract(off)
@@ -83,17 +83,17 @@ __global__ __launch_bounds__(CT) void cl_keys_k(const ClParams p) {
     for (int j = 0; j < p.C; ++j) s += expf(row[j] - m);
     const float lse = m + logf(s);
     float key = lse - row[0];
-    if (!(key >= 0.f)) key = key != key ? __int_as_float(0x7fc00000) : 0.f;   // a NaN row sorts first, as torch.sort puts it
+    if (!(key >= 0.f)) key = key != key ? ymi_qnan() : 0.f;   // a NaN row sorts first, as torch.sort puts it
     const size_t o = (size_t)b * p.P + r0 + t;
     const int ct = p.conf_t[o];
     positive = ct > 0;
     p.ws_lse[o] = lse;
     p.ws_key[o] = ct == 0 ? key : 0.f;                                        // :255-256
   }
-  const int c = __popcll(__ballot(positive));
+  const int c = ymi_wave_count(positive);
   if ((t & 63) == 0) cw[t >> 6] = c;
   __syncthreads();
-  if (t == 0) p.ws_cnt[(size_t)b * p.ntiles + blockIdx.x] = cw[0] + cw[1];
+  if (t == 0) p.ws_cnt[(size_t)b * p.ntiles + blockIdx.x] = ymi_waves_count<CT / 64>(cw);
 }
 
 __global__ __launch_bounds__(ST) void cl_select_k(const ClParams p) {
@@ -109,8 +109,7 @@ __global__ __launch_bounds__(ST) void cl_select_k(const ClParams p) {
   // num_pos: the tile counts strided over the workgroup, a wave butterfly, the waves through LDS (integers: any order, one value)
   int c = 0;
   for (int tl = t; tl < p.ntiles; tl += ST) c += p.ws_cnt[(size_t)b * p.ntiles + tl];
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) c += __shfl_xor(c, d);
+  c = ymi_wave_sum(c);
   if (lane == 0) wtake[wave] = c;
   __syncthreads();
   long num_pos = 0;
@@ -187,15 +186,12 @@ __global__ __launch_bounds__(CT) void cl_grad_k(const ClParams p) {
     const int ct = p.conf_t[o];
     const float lse = p.ws_lse[o];
     int tag = -1;
-    if (ct < -1 || ct >= p.C) { tag = -2; l = __int_as_float(0x7fc00000); }   // before it indexes
+    if (ct < -1 || ct >= p.C) { tag = -2; l = ymi_qnan(); }   // before it indexes
     else if (ct > 0 || (ct == 0 && p.neg[o])) { tag = ct; l = lse - p.conf[o * p.C + ct]; }
     s_lse[t] = lse; s_ct[t] = tag;
   }
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) l += __shfl_xor(l, d);
-  if ((t & 63) == 0) lw[t >> 6] = l;
-  __syncthreads();
-  if (t == 0) p.ws_ls[(size_t)b * p.ntiles + blockIdx.x] = lw[0] + lw[1];
+  const float s = ymi_block_sum<CT / 64>(l, lw);
+  if (t == 0) p.ws_ls[(size_t)b * p.ntiles + blockIdx.x] = s;
   if (!p.d_conf) return;                                                      // uniform
 
   const long e0 = ((long)b * p.P + r0) * p.C, e1 = e0 + (long)nr * p.C;
@@ -208,7 +204,7 @@ __global__ __launch_bounds__(CT) void cl_grad_k(const ClParams p) {
     for (long e = lo; e < hi; ++e) {
       const int tag = s_ct[row];
       if (tag >= 0) g[e - a] = p.alpha * (expf(p.conf[e] - s_lse[row]) - (col == tag ? 1.f : 0.f));
-      else if (tag == -2) g[e - a] = __int_as_float(0x7fc00000);
+      else if (tag == -2) g[e - a] = ymi_qnan();
       if (++col == p.C) { col = 0; ++row; }
     }
     if (lo == a && hi == a + 4) {
@@ -222,18 +218,8 @@ __global__ __launch_bounds__(CT) void cl_grad_k(const ClParams p) {
 
 // one block: loss = alpha * the B * ntiles partials, strided sums then a fixed tree
 __global__ __launch_bounds__(256) void cl_sum_k(const ClParams p) {
-  __shared__ float part[256];
-  const int t = threadIdx.x;
-  float s = 0.f;
-  const long total = (long)p.B * p.ntiles;
-  for (long k = t; k < total; k += 256) s += p.ws_ls[k];
-  part[t] = s;
-  __syncthreads();
-  for (int d = 128; d >= 1; d >>= 1) {
-    if (t < d) part[t] += part[t + d];
-    __syncthreads();
-  }
-  if (t == 0) p.loss[0] = part[0] * p.alpha;
+  const float s = ymi_sum256(p.ws_ls, (long)p.B * p.ntiles);
+  if (threadIdx.x == 0) p.loss[0] = s * p.alpha;
 }
 
 int validate_shape(const ymi_class_loss_desc *d) {
@@ -244,12 +230,10 @@ int validate_shape(const ymi_class_loss_desc *d) {
 }
 
 // byte offsets of key, lse, cnt, ls; returns the total
-int64_t layout(const ymi_class_loss_desc *d, int64_t off[4]) {
+int64_t layout(const ymi_class_loss_desc *d, int64_t (&off)[4]) {
   const int64_t BP = (int64_t)d->B * d->P, BT = (int64_t)d->B * ntiles_of(d->P, d->C);
   const int64_t sizes[4] = {BP, BP, BT, BT};
-  int64_t at = 0;
-  for (int k = 0; k < 4; ++k) { off[k] = at; at += (4 * sizes[k] + 15) / 16 * 16; }
-  return at;
+  return ymi_ws_layout(sizes, off);
 }
 
 }  // namespace
@@ -277,14 +261,9 @@ extern "C" int ymi_class_loss_f32(const ymi_class_loss_desc *d, void *stream) {
   p.ws_key = (float *)(w + off[0]); p.ws_lse = (float *)(w + off[1]);
   p.ws_cnt = (int32_t *)(w + off[2]); p.ws_ls = (float *)(w + off[3]);
 
-  hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(cl_keys_k, dim3(p.ntiles, d->B), dim3(CT), 0, s, p);
-  int rl = ymi_launch_status();
-  if (rl) return rl;
-  hipLaunchKernelGGL(cl_select_k, dim3(d->B), dim3(ST), 0, s, p);
-  if ((rl = ymi_launch_status())) return rl;
-  hipLaunchKernelGGL(cl_grad_k, dim3(p.ntiles, d->B), dim3(CT), 0, s, p);
-  if ((rl = ymi_launch_status())) return rl;
-  hipLaunchKernelGGL(cl_sum_k, dim3(1), dim3(256), 0, s, p);
-  return ymi_launch_status();
+  int rl = ymi_launch(cl_keys_k, dim3(p.ntiles, d->B), dim3(CT), 0, stream, p);
+  if (!rl) rl = ymi_launch(cl_select_k, dim3(d->B), dim3(ST), 0, stream, p);
+  if (!rl) rl = ymi_launch(cl_grad_k, dim3(p.ntiles, d->B), dim3(CT), 0, stream, p);
+  if (!rl) rl = ymi_launch(cl_sum_k, dim3(1), dim3(256), 0, stream, p);
+  return rl;
 }

@@ -20,7 +20,7 @@
 // -max(log q, -100) to fp32 round-off (and closer to the exact value than log(1 - p) of a rounded p).  Beyond |x| ~ 17 the
 // reference's fp32 sigmoid saturates to exactly 0 or 1, its BCE jumps to the clamp 100 and its gradient to 0; this kernel stays on
 // the smooth branch there: l = min(softplus, 100), g = p - t.  Everything stays finite for any finite input.
-#include "common.h"
+#include "loss_common.h"
 #include "../../include/yolact_amd.h"
 
 namespace {
@@ -68,9 +68,9 @@ __global__ __launch_bounds__(256) void mask_loss_k(const MlParams p) {
   const int py = ok ? pix / p.mw : 0, px = ok ? pix - py * p.mw : 0;
   const float fx = (float)px, fy = (float)py;
 
-  int j0 = p.img_off[b], j1 = p.img_off[b + 1];
-  j0 = j0 < 0 ? 0 : (j0 > p.N ? p.N : j0);
-  j1 = j1 < j0 ? j0 : (j1 > p.N ? p.N : j1);
+  int j0, nj;
+  ymi_image_range(p.img_off, b, p.N, j0, nj);
+  const int j1 = j0 + nj;
 
   float P[32], dp[32];
   {
@@ -134,9 +134,7 @@ __global__ __launch_bounds__(256) void mask_loss_k(const MlParams p) {
 #pragma unroll
           for (int k = 0; k < 32; ++k) dp[k] = fmaf(gs, c[k], dp[k]);
         }
-        // sum of l over the wave
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) l += __shfl_xor(l, d);
+        l = ymi_wave_sum(l);
         if (lane == 0) redl[wave * JC + u] = l;
         if (p.want_dc) {
           float v0 = 0.f;
@@ -169,6 +167,7 @@ __global__ __launch_bounds__(256) void mask_loss_k(const MlParams p) {
         const int u = t >> 5, k = t & 31, jj = jj0 + u;
         if (jj < cnt) {
           const size_t row = (size_t)tile * p.N + (c0 + jj);
+          // ymi_waves_sum's order, spelled out: through the helper the compiler pairs these LDS reads differently
           if (p.want_dc)
             p.ws_dc[row * 32 + k] = ((red[(0 * JC + u) * 32 + k] + red[(1 * JC + u) * 32 + k]) + red[(2 * JC + u) * 32 + k]) +
                                     red[(3 * JC + u) * 32 + k];
@@ -212,17 +211,8 @@ __global__ __launch_bounds__(256) void mask_loss_dcoef_k(const MlParams p) {
 
 // one block: loss = sum_j weight_j L_j * alpha / mh / mw, strided partial sums then a fixed tree
 __global__ __launch_bounds__(256) void mask_loss_sum_k(const MlParams p) {
-  __shared__ float part[256];
-  const int t = threadIdx.x;
-  float s = 0.f;
-  for (int j = t; j < p.N; j += 256) s += p.ws_wl[j];
-  part[t] = s;
-  __syncthreads();
-  for (int d = 128; d >= 1; d >>= 1) {
-    if (t < d) part[t] += part[t + d];
-    __syncthreads();
-  }
-  if (t == 0) p.loss[0] = part[0] * p.alpha / (float)p.mh / (float)p.mw;
+  const float s = ymi_sum256(p.ws_wl, p.N);
+  if (threadIdx.x == 0) p.loss[0] = s * p.alpha / (float)p.mh / (float)p.mw;
 }
 
 int validate(const ymi_mask_loss_desc *d) {
@@ -252,7 +242,6 @@ extern "C" int ymi_mask_loss_f32(const ymi_mask_loss_desc *d, void *stream) {
   if (d->N > 0 && (!d->coef || !d->box || !d->gt || !d->gt_idx || !d->weight || !d->ws)) return YMI_ENULL;
   if (((uintptr_t)d->proto | (uintptr_t)d->d_proto | (uintptr_t)d->ws) & 15) return YMI_ESHAPE;
 
-  hipStream_t s = (hipStream_t)stream;
   MlParams p;
   p.proto = d->proto; p.coef = d->coef; p.box = d->box; p.weight = d->weight;
   p.gt = d->gt; p.gt_idx = d->gt_idx; p.img_off = d->img_off;
@@ -268,16 +257,10 @@ extern "C" int ymi_mask_loss_f32(const ymi_mask_loss_desc *d, void *stream) {
   p.cap = n8 < 8 ? 8 : (n8 > CAP_MAX ? CAP_MAX : n8);
   const size_t lds = ((size_t)p.cap * (32 + 4 + 1 + 1) + 4 * JC * 32 + 4 * JC) * sizeof(float);     // <= 52.9 KB
 
-  if (d->N > 0 || d->d_proto) {                      // (N = 0: the launch only writes the zeros of d_proto)
-    hipLaunchKernelGGL(mask_loss_k, dim3(p.ntiles, d->B), dim3(256), lds, s, p);
-    const int rc1 = ymi_launch_status();
-    if (rc1) return rc1;
-  }
-  if (d->N > 0) {
-    hipLaunchKernelGGL(mask_loss_dcoef_k, dim3((int)(((long)d->N * 32 + 255) / 256)), dim3(256), 0, s, p);
-    const int rc2 = ymi_launch_status();
-    if (rc2) return rc2;
-  }
-  hipLaunchKernelGGL(mask_loss_sum_k, dim3(1), dim3(256), 0, s, p);
-  return ymi_launch_status();
+  int rl = YMI_OK;
+  if (d->N > 0 || d->d_proto)                        // (N = 0: the launch only writes the zeros of d_proto)
+    rl = ymi_launch(mask_loss_k, dim3(p.ntiles, d->B), dim3(256), lds, stream, p);
+  if (!rl && d->N > 0) rl = ymi_launch(mask_loss_dcoef_k, dim3((int)(((long)d->N * 32 + 255) / 256)), dim3(256), 0, stream, p);
+  if (!rl) rl = ymi_launch(mask_loss_sum_k, dim3(1), dim3(256), 0, stream, p);
+  return rl;
 }

@@ -19,7 +19,7 @@
 // keeps the LOWEST index among equal values.  No atomics, no cooperative grid: the same inputs give the same bits.
 // Nothing here is bound by arithmetic: launch 1 and 3 by their few hundred KB of traffic and the launch itself, launch 2 by the
 // chain of n_gt dependent workgroup reductions.
-#include "common.h"
+#include "loss_common.h"
 #include "../../include/yolact_amd.h"
 
 #pragma clang fp contract(off)
@@ -91,14 +91,6 @@ __device__ __forceinline__ void wave_argmax(float &v, int &i) {
   }
 }
 
-// the image's GT rows [g0, g0 + n) from device offsets nobody validated on the device: never outside [0, G), never more than P
-__device__ __forceinline__ void image_range(const int32_t *off, int b, int total, int cap, int &g0, int &n) {
-  int a = off[b], e = off[b + 1];
-  a = a < 0 ? 0 : (a > total ? total : a);
-  e = e < a ? a : (e > total ? total : e);
-  g0 = a; n = e - a > cap ? cap : e - a;
-}
-
 __global__ __launch_bounds__(TP) void match_best_k(const MtParams p) {
   __shared__ Box gts[GC];
   __shared__ float gar[GC];
@@ -111,7 +103,7 @@ __global__ __launch_bounds__(TP) void match_best_k(const MtParams p) {
   const Box pb = prior_box(p.priors, ok ? pr : 0);
   const float pa = area(pb);
   int g0, n;
-  image_range(p.gt_off, b, p.G, p.P, g0, n);
+  ymi_image_range(p.gt_off, b, p.G, g0, n, p.P);
 
   float bto = -2.f;                                    // below every overlap: the first GT always replaces it
   int bti = 0;
@@ -146,7 +138,7 @@ __global__ __launch_bounds__(TP) void match_best_k(const MtParams p) {
   if (p.Gc > 0) {
     // jaccard(decoded_priors, crowd_boxes, iscrowd=True).max(1): inter / area of the PRIOR (box_utils.py:79,218-220)
     int c0, nc;
-    image_range(p.crowd_off, b, p.Gc, p.Gc, c0, nc);
+    ymi_image_range(p.crowd_off, b, p.Gc, c0, nc);
     float bco = -1.f;
     for (int c = 0; c < nc; ++c) {
       const Box cb = load_box(p.crowd + (size_t)(c0 + c) * 4);
@@ -175,7 +167,7 @@ __global__ __launch_bounds__(FT) void match_force_k(const MtParams p) {
   __shared__ int wi[FT / 64];
   const int t = threadIdx.x, b = blockIdx.x;
   int g0, n;
-  image_range(p.gt_off, b, p.G, p.P, g0, n);
+  ymi_image_range(p.gt_off, b, p.G, g0, n, p.P);
   // row r: rmax = its largest overlap over the live columns (-1 once the row is retired), rarg = the lowest column that has it
   float *rmax = n <= RCAP ? s_rmax : p.ws_rmax + g0;
   int *rarg = n <= RCAP ? s_rarg : p.ws_rarg + g0;
@@ -239,14 +231,13 @@ __device__ __forceinline__ void tile_partials(const MtParams &p, bool positive, 
   __shared__ int cw[4];
   __shared__ float lw[4];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int c = __popcll(__ballot(positive));
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) l += __shfl_xor(l, d);
+  const int c = ymi_wave_count(positive);
+  l = ymi_wave_sum(l);
   if (lane == 0) { cw[wave] = c; lw[wave] = l; }
   __syncthreads();
   if (threadIdx.x == 0) {
-    p.ws_cnt[(size_t)b * p.ntiles + tile] = (cw[0] + cw[1]) + (cw[2] + cw[3]);
-    p.ws_ls[(size_t)b * p.ntiles + tile] = ((lw[0] + lw[1]) + lw[2]) + lw[3];
+    p.ws_cnt[(size_t)b * p.ntiles + tile] = ymi_waves_count<4>(cw);
+    p.ws_ls[(size_t)b * p.ntiles + tile] = ymi_waves_sum<4>(lw);
   }
 }
 
@@ -255,7 +246,7 @@ __global__ __launch_bounds__(TP) void match_finish_k(const MtParams p) {
   const int pr = tile * TP + t;
   const bool ok = pr < p.P;
   int g0, n;
-  image_range(p.gt_off, b, p.G, p.P, g0, n);
+  ymi_image_range(p.gt_off, b, p.G, g0, n, p.P);
   bool positive = false;
   float l = 0.f;
   if (ok) {
@@ -271,7 +262,7 @@ __global__ __launch_bounds__(TP) void match_finish_k(const MtParams p) {
     if (ov < p.neg_thresh) conf = 0;
     if (p.Gc > 0 && p.crowd_thresh < 1.f) {
       int c0, nc;
-      image_range(p.crowd_off, b, p.Gc, p.Gc, c0, nc);
+      ymi_image_range(p.crowd_off, b, p.Gc, c0, nc);
       if (nc > 0 && conf <= 0 && p.ws_bco[o] > p.crowd_thresh) conf = -1;     // :216-222
     }
     const f32x4 m = *reinterpret_cast<const f32x4 *>(p.truth + (size_t)row * 4);
@@ -318,7 +309,6 @@ __global__ __launch_bounds__(TP) void box_loss_k(const MtParams p) {
 
 // one block: num_pos[b] = its tiles' counts in tile order; loss = alpha * the B * ntiles partials, strided sums then a fixed tree
 __global__ __launch_bounds__(256) void match_sum_k(const MtParams p) {
-  __shared__ float part[256];
   const int t = threadIdx.x;
   if (p.num_pos)
     for (int b = t; b < p.B; b += 256) {
@@ -327,16 +317,8 @@ __global__ __launch_bounds__(256) void match_sum_k(const MtParams p) {
       p.num_pos[b] = c;
     }
   if (!p.loss) return;                                 // uniform
-  float s = 0.f;
-  const long total = (long)p.B * p.ntiles;
-  for (long k = t; k < total; k += 256) s += p.ws_ls[k];
-  part[t] = s;
-  __syncthreads();
-  for (int d = 128; d >= 1; d >>= 1) {
-    if (t < d) part[t] += part[t + d];
-    __syncthreads();
-  }
-  if (t == 0) p.loss[0] = part[0] * p.alpha;
+  const float s = ymi_sum256(p.ws_ls, (long)p.B * p.ntiles);
+  if (t == 0) p.loss[0] = s * p.alpha;
 }
 
 int ntiles_of(int P) { return (P + TP - 1) / TP; }
@@ -348,23 +330,11 @@ int validate_shape(const ymi_match_desc *d) {
   return YMI_OK;
 }
 
-// [off[b], off[b+1]) covers [0, total) image by image; each image holds lo..hi rows
-int validate_offsets(const int32_t *off, int B, int total, int lo, int hi) {
-  if (off[0] != 0 || off[B] != total) return YMI_EARG;
-  for (int b = 0; b < B; ++b) {
-    const long n = (long)off[b + 1] - off[b];
-    if (n < lo || n > hi) return YMI_EARG;
-  }
-  return YMI_OK;
-}
-
 // byte offsets of the workspace parts; returns the total
-int64_t layout(const ymi_match_desc *d, int64_t off[10]) {
+int64_t layout(const ymi_match_desc *d, int64_t (&off)[10]) {
   const int64_t nt = ntiles_of(d->P), G = d->G, BP = (int64_t)d->B * d->P;
   const int64_t sizes[10] = {nt * G, nt * G, BP, BP, BP, BP, G, G, (int64_t)d->B * nt, (int64_t)d->B * nt};
-  int64_t at = 0;
-  for (int k = 0; k < 10; ++k) { off[k] = at; at += (4 * sizes[k] + 15) / 16 * 16; }
-  return at;
+  return ymi_ws_layout(sizes, off);
 }
 
 void bind_ws(MtParams &p, const ymi_match_desc *d, void *ws) {
@@ -392,7 +362,7 @@ extern "C" int64_t ymi_box_loss_ws_bytes(const ymi_match_desc *d) {
   if (!d) return YMI_ENULL;
   if (d->B < 1 || d->B > 65535 || d->P < 1) return YMI_EARG;
   if (d->P >= (1 << 24)) return YMI_ESHAPE;
-  return 2 * ((4 * (int64_t)d->B * ntiles_of(d->P) + 15) / 16 * 16);
+  return 2 * ymi_ws_part((int64_t)d->B * ntiles_of(d->P));
 }
 
 extern "C" int ymi_match_f32(const ymi_match_desc *d, void *stream) {
@@ -406,14 +376,13 @@ extern "C" int ymi_match_f32(const ymi_match_desc *d, void *stream) {
   if (((uintptr_t)d->priors | (uintptr_t)d->truth | (uintptr_t)d->crowd | (uintptr_t)d->loc_data | (uintptr_t)d->loc_t |
        (uintptr_t)d->gt_box_t | (uintptr_t)d->d_loc | (uintptr_t)d->ws) & 15)
     return YMI_ESHAPE;
-  const int rg = validate_offsets(d->gt_off_host, d->B, d->G, 1, d->P);      // 1 <= n_gt <= P in every image
+  const int rg = ymi_validate_offsets(d->gt_off_host, d->B, d->G, 1, d->P);      // 1 <= n_gt <= P in every image
   if (rg) return rg;
   if (d->Gc > 0) {
-    const int rcw = validate_offsets(d->crowd_off_host, d->B, d->Gc, 0, d->Gc);
+    const int rcw = ymi_validate_offsets(d->crowd_off_host, d->B, d->Gc, 0, d->Gc);
     if (rcw) return rcw;
   }
 
-  hipStream_t s = (hipStream_t)stream;
   MtParams p = {};
   p.priors = d->priors; p.truth = d->truth; p.crowd = d->crowd; p.loc_data = d->loc_data;
   p.label = d->label; p.gt_off = d->gt_off; p.crowd_off = d->crowd_off;
@@ -423,15 +392,11 @@ extern "C" int ymi_match_f32(const ymi_match_desc *d, void *stream) {
   p.pos_thresh = d->pos_thresh; p.neg_thresh = d->neg_thresh; p.crowd_thresh = d->crowd_thresh; p.alpha = d->bbox_alpha;
   bind_ws(p, d, d->ws);
 
-  hipLaunchKernelGGL(match_best_k, dim3(p.ntiles, d->B), dim3(TP), 0, s, p);
-  int rl = ymi_launch_status();
-  if (rl) return rl;
-  hipLaunchKernelGGL(match_force_k, dim3(d->B), dim3(FT), 0, s, p);
-  if ((rl = ymi_launch_status())) return rl;
-  hipLaunchKernelGGL(match_finish_k, dim3(p.ntiles, d->B), dim3(TP), 0, s, p);
-  if ((rl = ymi_launch_status())) return rl;
-  hipLaunchKernelGGL(match_sum_k, dim3(1), dim3(256), 0, s, p);
-  return ymi_launch_status();
+  int rl = ymi_launch(match_best_k, dim3(p.ntiles, d->B), dim3(TP), 0, stream, p);
+  if (!rl) rl = ymi_launch(match_force_k, dim3(d->B), dim3(FT), 0, stream, p);
+  if (!rl) rl = ymi_launch(match_finish_k, dim3(p.ntiles, d->B), dim3(TP), 0, stream, p);
+  if (!rl) rl = ymi_launch(match_sum_k, dim3(1), dim3(256), 0, stream, p);
+  return rl;
 }
 
 extern "C" int ymi_box_loss_f32(const float *loc_data, const float *loc_t, const uint8_t *pos, int B, int P, float bbox_alpha,
@@ -444,11 +409,8 @@ extern "C" int ymi_box_loss_f32(const float *loc_data, const float *loc_t, const
   p.loc_data = loc_data; p.loc_t_in = loc_t; p.pos_in = pos; p.loss = loss; p.d_loc = d_loc;
   p.B = B; p.P = P; p.ntiles = ntiles_of(P); p.alpha = bbox_alpha;
   p.ws_cnt = static_cast<int32_t *>(ws);
-  p.ws_ls = reinterpret_cast<float *>(static_cast<char *>(ws) + (4 * (int64_t)B * p.ntiles + 15) / 16 * 16);
-  hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(box_loss_k, dim3(p.ntiles, B), dim3(TP), 0, s, p);
-  const int rl = ymi_launch_status();
-  if (rl) return rl;
-  hipLaunchKernelGGL(match_sum_k, dim3(1), dim3(256), 0, s, p);
-  return ymi_launch_status();
+  p.ws_ls = reinterpret_cast<float *>(static_cast<char *>(ws) + ymi_ws_part((int64_t)B * p.ntiles));
+  int rl = ymi_launch(box_loss_k, dim3(p.ntiles, B), dim3(TP), 0, stream, p);
+  if (!rl) rl = ymi_launch(match_sum_k, dim3(1), dim3(256), 0, stream, p);
+  return rl;
 }

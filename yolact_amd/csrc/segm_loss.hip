@@ -10,7 +10,7 @@
 //
 // No atomics: the same inputs give the same bits.  A label outside 0 .. K-1 sets no bit and makes the loss NaN.
 // Bound by memory traffic: segm is read once and d_segm written once.
-#include "common.h"
+#include "loss_common.h"
 #include "../../include/yolact_amd.h"
 
 #pragma clang fp contract(off)
@@ -35,11 +35,8 @@ __global__ __launch_bounds__(TP) void sg_loss_k(const SgParams p) {
   const int t = threadIdx.x, b = blockIdx.y;
   const int pix = blockIdx.x * TP + t;
   const bool ok = pix < p.HW;
-  // the image's objects from device offsets nobody validated on the device: never outside [0, G)
-  int g0 = p.gt_off[b], g1 = p.gt_off[b + 1];
-  g0 = g0 < 0 ? 0 : (g0 > p.G ? p.G : g0);
-  g1 = g1 < g0 ? g0 : (g1 > p.G ? p.G : g1);
-  const int n = g1 - g0;
+  int g0, n;
+  ymi_image_range(p.gt_off, b, p.G, g0, n);
 
   unsigned w0 = 0u, w1 = 0u, w2 = 0u, w3 = 0u;
   bool bad = false;
@@ -73,28 +70,15 @@ __global__ __launch_bounds__(TP) void sg_loss_k(const SgParams p) {
       }
     }
   }
-  if (bad) l = __int_as_float(0x7fc00000);
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) l += __shfl_xor(l, d);
-  if ((t & 63) == 0) lw[t >> 6] = l;
-  __syncthreads();
-  if (t == 0) p.ws[(size_t)b * p.ntiles + blockIdx.x] = ((lw[0] + lw[1]) + lw[2]) + lw[3];
+  if (bad) l = ymi_qnan();
+  const float s = ymi_block_sum<TP / 64>(l, lw);
+  if (t == 0) p.ws[(size_t)b * p.ntiles + blockIdx.x] = s;
 }
 
 // one block: loss = scale * the B * ntiles partials, strided sums then a fixed tree
 __global__ __launch_bounds__(256) void sg_sum_k(const SgParams p) {
-  __shared__ float part[256];
-  const int t = threadIdx.x;
-  float s = 0.f;
-  const long total = (long)p.B * p.ntiles;
-  for (long k = t; k < total; k += 256) s += p.ws[k];
-  part[t] = s;
-  __syncthreads();
-  for (int d = 128; d >= 1; d >>= 1) {
-    if (t < d) part[t] += part[t + d];
-    __syncthreads();
-  }
-  if (t == 0) p.loss[0] = part[0] * p.scale;
+  const float s = ymi_sum256(p.ws, (long)p.B * p.ntiles);
+  if (threadIdx.x == 0) p.loss[0] = s * p.scale;
 }
 
 int validate_shape(const ymi_segm_loss_desc *d) {
@@ -112,7 +96,7 @@ int ntiles_of(const ymi_segm_loss_desc *d) { return (int)(((int64_t)d->mh * d->m
 extern "C" int64_t ymi_segm_loss_ws_bytes(const ymi_segm_loss_desc *d) {
   const int rc = validate_shape(d);
   if (rc) return rc;
-  return (4 * (int64_t)d->B * ntiles_of(d) + 15) / 16 * 16;
+  return ymi_ws_part((int64_t)d->B * ntiles_of(d));
 }
 
 extern "C" int ymi_segm_loss_f32(const ymi_segm_loss_desc *d, void *stream) {
@@ -121,20 +105,15 @@ extern "C" int ymi_segm_loss_f32(const ymi_segm_loss_desc *d, void *stream) {
   if (!d->segm || !d->gt_off || !d->gt_off_host || !d->loss || !d->ws) return YMI_ENULL;
   if (d->G > 0 && (!d->gt || !d->label)) return YMI_ENULL;
   if (((uintptr_t)d->segm | (uintptr_t)d->d_segm | (uintptr_t)d->ws) & 15) return YMI_ESHAPE;
-  const int32_t *off = d->gt_off_host;
-  if (off[0] != 0 || off[d->B] != d->G) return YMI_EARG;
-  for (int b = 0; b < d->B; ++b)
-    if (off[b + 1] < off[b]) return YMI_EARG;
+  const int ro = ymi_validate_offsets(d->gt_off_host, d->B, d->G, 0, d->G);    // ascending offsets from 0 to G
+  if (ro) return ro;
 
   SgParams p = {};
   p.segm = d->segm; p.gt = d->gt; p.label = d->label; p.gt_off = d->gt_off;
   p.loss = d->loss; p.d_segm = d->d_segm; p.ws = static_cast<float *>(d->ws);
   p.B = d->B; p.K = d->K; p.HW = d->mh * d->mw; p.G = d->G; p.ntiles = ntiles_of(d);
   p.scale = d->alpha / (float)p.HW;
-  hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(sg_loss_k, dim3(p.ntiles, d->B), dim3(TP), 0, s, p);
-  const int rl = ymi_launch_status();
-  if (rl) return rl;
-  hipLaunchKernelGGL(sg_sum_k, dim3(1), dim3(256), 0, s, p);
-  return ymi_launch_status();
+  int rl = ymi_launch(sg_loss_k, dim3(p.ntiles, d->B), dim3(TP), 0, stream, p);
+  if (!rl) rl = ymi_launch(sg_sum_k, dim3(1), dim3(256), 0, stream, p);
+  return rl;
 }

@@ -19,10 +19,10 @@ from __future__ import annotations
 import ctypes as C
 
 import torch
-from torch.autograd.function import once_differentiable
 
 from .. import _lib as L
 from ..config import active_cfg
+from . import _loss_common as LC
 
 # cfg field -> the value the kernels implement (every shipped config: data/config.py:517,528 and the focal / objectness switches)
 SHIPPED_SWITCHES = {
@@ -36,14 +36,11 @@ SHIPPED_SWITCHES = {
 
 def check_switches(cfg):
     """NotImplementedError naming the cfg field for every switch outside what the shipped configs train with."""
-    for field, want in SHIPPED_SWITCHES.items():
-        if bool(getattr(cfg, field)) != want:
-            raise NotImplementedError('yolact_amd ohem_conf_loss: cfg.%s = %r is not supported (the kernels implement %r, what '
-                                      'every shipped config trains with)' % (field, getattr(cfg, field), want))
+    LC.check_shipped_switches(cfg, SHIPPED_SWITCHES, 'ohem_conf_loss')
 
 
 def _launch(conf_data, conf_t, negpos_ratio, conf_alpha, want_grad):
-    """ymi_class_loss_f32 on detached tensors -> (loss [1], neg uint8 [B,P], num_neg int32 [B], d_conf or None)."""
+    """ymi_class_loss_f32 on detached tensors -> (loss [1], d_conf or None, neg uint8 [B,P], num_neg int32 [B])."""
     L.require_cuda(conf_data, 'class_loss conf_data')
     L.require_cuda(conf_t, 'class_loss conf_t')
     if conf_data.dim() != 3 or tuple(conf_t.shape) != tuple(conf_data.shape[:2]):
@@ -51,8 +48,7 @@ def _launch(conf_data, conf_t, negpos_ratio, conf_alpha, want_grad):
     dev = conf_data.device
     B, P, NC = conf_data.shape
     with torch.cuda.device(dev), torch.no_grad():
-        confd = conf_data.detach().to(dtype=torch.float32).contiguous()
-        ctd = conf_t.detach().to(device=dev, dtype=torch.int32).contiguous()
+        confd, ctd = LC.f32(conf_data, dev), LC.i32(conf_t, dev)
         loss = torch.empty(1, dtype=torch.float32, device=dev)
         neg = torch.empty(B, P, dtype=torch.uint8, device=dev)
         num_neg = torch.empty(B, dtype=torch.int32, device=dev)
@@ -61,27 +57,9 @@ def _launch(conf_data, conf_t, negpos_ratio, conf_alpha, want_grad):
         d.conf, d.conf_t, d.loss, d.neg, d.num_neg = confd.data_ptr(), ctd.data_ptr(), loss.data_ptr(), neg.data_ptr(), num_neg.data_ptr()
         d.d_conf = None if dconf is None else dconf.data_ptr()
         d.B, d.P, d.C, d.negpos_ratio, d.conf_alpha = B, P, NC, int(negpos_ratio), float(conf_alpha)
-        nbytes = L.lib().ymi_workspace_bytes(L.WS_CLASS_LOSS, C.byref(d))
-        if nbytes < 0:
-            L.check(int(nbytes), 'ymi_workspace_bytes(YMI_WS_CLASS_LOSS)')
-        ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
-        d.ws = ws.data_ptr()
+        ws = LC.workspace('CLASS_LOSS', d, dev)
         L.check(L.lib().ymi_class_loss_f32(C.byref(d), L.stream_ptr()), 'ymi_class_loss_f32')
-        return loss, neg, num_neg, dconf
-
-
-class _ClassLossFunction(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, conf_data, conf_t, negpos_ratio, conf_alpha):
-        loss, _, _, dconf = _launch(conf_data, conf_t, negpos_ratio, conf_alpha, ctx.needs_input_grad[0])
-        ctx.grad = dconf
-        ctx.dtype = conf_data.dtype
-        return loss.reshape(())
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, g):
-        return (None if ctx.grad is None else (ctx.grad * g).to(ctx.dtype)), None, None, None
+        return loss, dconf, neg, num_neg
 
 
 def _ratio(cfg, negpos_ratio):
@@ -92,12 +70,12 @@ def ohem_conf_loss(conf_data, conf_t, negpos_ratio=None):
     """conf_data [B,P,C], conf_t [B,P] -> cfg.conf_alpha * cross_entropy(sum) over the positives and the mined negatives."""
     cfg = active_cfg()
     check_switches(cfg)
-    return _ClassLossFunction.apply(conf_data, conf_t, _ratio(cfg, negpos_ratio), float(cfg.conf_alpha))
+    return LC.LossFunction.apply(_launch, 1, conf_data, conf_t, _ratio(cfg, negpos_ratio), float(cfg.conf_alpha))
 
 
 def ohem_terms(conf_data, conf_t, negpos_ratio=None):
     """One launch sequence with every output, no autograd: dict(C [1], neg [B,P] bool, num_neg [B] long, d_conf [B,P,C])."""
     cfg = active_cfg()
     check_switches(cfg)
-    loss, neg, num_neg, dconf = _launch(conf_data, conf_t, _ratio(cfg, negpos_ratio), float(cfg.conf_alpha), True)
+    loss, dconf, neg, num_neg = _launch(conf_data, conf_t, _ratio(cfg, negpos_ratio), float(cfg.conf_alpha), True)
     return dict(C=loss, neg=neg.bool(), num_neg=num_neg.long(), d_conf=dconf)

@@ -20,11 +20,10 @@ from __future__ import annotations
 import ctypes as C
 
 import torch
-import torch.nn.functional as F
-from torch.autograd.function import once_differentiable
 
 from .. import _lib as L
 from ..config import act_name, active_cfg
+from . import _loss_common as LC
 
 # cfg field -> the value the kernel implements (both shipped base configs: data/config.py coco_base_config / yolact_base_config)
 SHIPPED_SWITCHES = {
@@ -40,7 +39,7 @@ SHIPPED_SWITCHES = {
 
 
 def _launch(proto, coef, box, gt, gt_idx, img_off, weight, crop, roi_norm, alpha, want_proto, want_coef, want_inst=False):
-    """ymi_mask_loss_f32 on detached fp32 tensors -> (loss [1], loss_inst or None, d_proto or None, d_coef or None)."""
+    """ymi_mask_loss_f32 on detached fp32 tensors -> (loss [1], d_proto or None, d_coef or None, loss_inst or None)."""
     for name, t in (('proto', proto), ('coef', coef), ('box', box), ('gt', gt), ('gt_idx', gt_idx), ('img_off', img_off),
                     ('weight', weight)):
         L.require_cuda(t, 'mask_loss ' + name)
@@ -55,11 +54,8 @@ def _launch(proto, coef, box, gt, gt_idx, img_off, weight, crop, roi_norm, alpha
                             tuple(proto.shape), tuple(coef.shape)))
     dev = proto.device
     with torch.cuda.device(dev), torch.no_grad():
-        f32 = lambda t: t.detach().to(device=dev, dtype=torch.float32).contiguous()
-        i32 = lambda t: t.detach().to(device=dev, dtype=torch.int32).contiguous()
-        protod, coefd, boxd, weightd = f32(proto), f32(coef), f32(box), f32(weight)
-        gtd = gt.detach().to(device=dev).ne(0).to(torch.uint8).contiguous() if gt.dtype != torch.uint8 else gt.detach().contiguous()
-        gidx, ioff = i32(gt_idx), i32(img_off)
+        protod, coefd, boxd, weightd = LC.f32(proto, dev), LC.f32(coef, dev), LC.f32(box, dev), LC.f32(weight, dev)
+        gtd, gidx, ioff = LC.mask_u8(gt, dev), LC.i32(gt_idx, dev), LC.i32(img_off, dev)
         new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
         loss = new(1)
         linst = new(N) if want_inst else None
@@ -73,49 +69,28 @@ def _launch(proto, coef, box, gt, gt_idx, img_off, weight, crop, roi_norm, alpha
             setattr(d, name, None if t is None else t.data_ptr())
         d.B, d.mh, d.mw, d.K, d.N, d.G = B, mh, mw, K, N, gt.shape[0]
         d.crop, d.roi_norm, d.alpha = int(bool(crop)), int(bool(roi_norm)), float(alpha)
-        nbytes = L.lib().ymi_workspace_bytes(L.WS_MASK_LOSS, C.byref(d))
-        if nbytes < 0:
-            L.check(int(nbytes), 'ymi_workspace_bytes(YMI_WS_MASK_LOSS)')
-        ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
-        d.ws = ws.data_ptr()
+        ws = LC.workspace('MASK_LOSS', d, dev)
         L.check(L.lib().ymi_mask_loss_f32(C.byref(d), L.stream_ptr()), 'ymi_mask_loss_f32')
-        return loss, linst, dproto, dcoef
-
-
-class _MaskLossFunction(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, proto, coef, box, gt, gt_idx, img_off, weight, crop, roi_norm, alpha):
-        need_p, need_c = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        loss, _, dproto, dcoef = _launch(proto, coef, box, gt, gt_idx, img_off, weight, crop, roi_norm, alpha, need_p, need_c)
-        ctx.grads = (dproto, dcoef)
-        ctx.dtypes = (proto.dtype, coef.dtype)
-        return loss.reshape(())
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, g):
-        out = tuple(None if d is None else (d * g).to(dt) for d, dt in zip(ctx.grads, ctx.dtypes))
-        return out + (None,) * 8
+        return loss, dproto, dcoef, linst
 
 
 def mask_loss(proto, coef, box, gt, gt_idx, img_off, weight, crop=True, roi_norm=True, alpha=6.125):
     """proto [B,mh,mw,32], coef [N,32], box [N,4] (relative point form), gt [G,mh,mw] 0 / 1, gt_idx [N], img_off [B+1],
     weight [N] -> the 0-dim loss alpha / mh / mw * sum_j weight_j L_j.  A gradient is computed only for the tensor (proto, coef)
     that requires it."""
-    return _MaskLossFunction.apply(proto, coef, box, gt, gt_idx, img_off, weight, crop, roi_norm, alpha)
+    return LC.LossFunction.apply(_launch, 2, proto, coef, box, gt, gt_idx, img_off, weight, crop, roi_norm, alpha)
 
 
 def mask_loss_terms(proto, coef, box, gt, gt_idx, img_off, weight, crop=True, roi_norm=True, alpha=6.125):
     """One launch with every output: (loss [1], loss_inst [N], d_proto [B,mh,mw,32], d_coef [N,32]); no autograd."""
-    return _launch(proto, coef, box, gt, gt_idx, img_off, weight, crop, roi_norm, alpha, True, True, True)
+    loss, dproto, dcoef, linst = _launch(proto, coef, box, gt, gt_idx, img_off, weight, crop, roi_norm, alpha, True, True, True)
+    return loss, linst, dproto, dcoef
 
 
 def check_switches(cfg):
     """NotImplementedError naming the cfg field for every switch outside what the shipped base configs train with."""
-    for field, want in SHIPPED_SWITCHES.items():
-        if bool(getattr(cfg, field)) != want:
-            raise NotImplementedError('yolact_amd lincomb_mask_loss: cfg.%s = %r is not supported (the kernel implements %r, what '
-                                      'yolact_base_config and yolact_plus_base_config train with)' % (field, getattr(cfg, field), want))
+    LC.check_shipped_switches(cfg, SHIPPED_SWITCHES, 'lincomb_mask_loss',
+                              'the kernel implements %r, what yolact_base_config and yolact_plus_base_config train with')
     if act_name(cfg.mask_proto_mask_activation) != 'sigmoid':
         raise NotImplementedError('yolact_amd lincomb_mask_loss: cfg.mask_proto_mask_activation must be the sigmoid')
 
@@ -128,9 +103,7 @@ def gather_instances(pos, idx_t, mask_data, masks, gt_box_t, mask_h, mask_w, mas
     coefs, boxes, gts, gidx, weights, offs, selects = [], [], [], [], [], [0], []
     row0 = 0
     for idx in range(mask_data.size(0)):
-        with torch.no_grad():
-            down = F.interpolate(masks[idx].unsqueeze(0), (mask_h, mask_w), mode='bilinear', align_corners=False).squeeze(0)
-            gts.append(down.gt(0.5).to(torch.uint8))
+        gts.append(LC.downsample_gt(masks[idx], mask_h, mask_w))
         cur_pos = pos[idx]
         pos_idx_t = idx_t[idx, cur_pos]
         pos_gt_box_t = gt_box_t[idx, cur_pos]

@@ -20,10 +20,10 @@ from __future__ import annotations
 import ctypes as C
 
 import torch
-from torch.autograd.function import once_differentiable
 
 from .. import _lib as L
 from ..config import active_cfg
+from . import _loss_common as LC
 
 # cfg field -> the value the kernels implement (every shipped config: data/config.py:443,553,600,620,698-701)
 SHIPPED_SWITCHES = {
@@ -36,10 +36,7 @@ SHIPPED_SWITCHES = {
 
 def check_switches(cfg):
     """NotImplementedError naming the cfg field for every switch outside what the shipped configs train with."""
-    for field, want in SHIPPED_SWITCHES.items():
-        if bool(getattr(cfg, field)) != want:
-            raise NotImplementedError('yolact_amd match_targets / box_loss: cfg.%s = %r is not supported (the kernels implement %r, '
-                                      'what every shipped config trains with)' % (field, getattr(cfg, field), want))
+    LC.check_shipped_switches(cfg, SHIPPED_SWITCHES, 'match_targets / box_loss')
 
 
 def _launch(priors, truth, label, gt_off, crowd, crowd_off, loc_data, pos_thresh, neg_thresh, crowd_thresh, bbox_alpha,
@@ -58,11 +55,8 @@ def _launch(priors, truth, label, gt_off, crowd, crowd_off, loc_data, pos_thresh
     if loc_data is not None and tuple(loc_data.shape) != (B, P, 4):
         raise ValueError('match: loc_data %s is not [%d, %d, 4]' % (tuple(loc_data.shape), B, P))
     with torch.cuda.device(dev), torch.no_grad():
-        f32 = lambda t: t.detach().to(device=dev, dtype=torch.float32).contiguous()
-        priorsd, truthd = f32(priors), f32(truth)
-        labeld = label.detach().to(device=dev, dtype=torch.int32).contiguous()
-        off_h = (C.c_int32 * (B + 1))(*gt_off)
-        off_d = torch.tensor(list(gt_off), dtype=torch.int32).to(dev)
+        priorsd, truthd, labeld = LC.f32(priors, dev), LC.f32(truth, dev), LC.i32(label, dev)
+        off_h, off_d = LC.offsets(gt_off, dev)
         new = lambda dtype, *shape: torch.empty(*shape, dtype=dtype, device=dev)
         out = dict(loc_t=new(torch.float32, B, P, 4), gt_box_t=new(torch.float32, B, P, 4), conf_t=new(torch.int32, B, P),
                    idx_t=new(torch.int32, B, P), pos=new(torch.uint8, B, P), num_pos=new(torch.int32, B))
@@ -70,12 +64,11 @@ def _launch(priors, truth, label, gt_off, crowd, crowd_off, loc_data, pos_thresh
         d.priors, d.truth, d.label, d.gt_off = priorsd.data_ptr(), truthd.data_ptr(), labeld.data_ptr(), off_d.data_ptr()
         d.gt_off_host = C.cast(off_h, C.c_void_p)
         if Gc:
-            crowdd = f32(crowd)
-            coff_h = (C.c_int32 * (B + 1))(*crowd_off)
-            coff_d = torch.tensor(list(crowd_off), dtype=torch.int32).to(dev)
+            crowdd = LC.f32(crowd, dev)
+            coff_h, coff_d = LC.offsets(crowd_off, dev)
             d.crowd, d.crowd_off, d.crowd_off_host = crowdd.data_ptr(), coff_d.data_ptr(), C.cast(coff_h, C.c_void_p)
         if loc_data is not None:
-            locd = f32(loc_data)
+            locd = LC.f32(loc_data, dev)
             out['loss'] = new(torch.float32, 1)
             d.loc_data, d.loss = locd.data_ptr(), out['loss'].data_ptr()
             if want_grad:
@@ -85,11 +78,7 @@ def _launch(priors, truth, label, gt_off, crowd, crowd_off, loc_data, pos_thresh
             setattr(d, name, out[name].data_ptr())
         d.B, d.P, d.G, d.Gc = B, P, G, Gc
         d.pos_thresh, d.neg_thresh, d.crowd_thresh, d.bbox_alpha = pos_thresh, neg_thresh, crowd_thresh, bbox_alpha
-        nbytes = L.lib().ymi_workspace_bytes(L.WS_MATCH, C.byref(d))
-        if nbytes < 0:
-            L.check(int(nbytes), 'ymi_workspace_bytes(YMI_WS_MATCH)')
-        ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
-        d.ws = ws.data_ptr()
+        ws = LC.workspace('MATCH', d, dev)
         L.check(L.lib().ymi_match_f32(C.byref(d), L.stream_ptr()), 'ymi_match_f32')
         return out
 
@@ -133,39 +122,20 @@ def _box_loss_launch(loc_data, loc_t, pos, bbox_alpha, want_grad):
     dev = loc_data.device
     B, P = loc_data.shape[:2]
     with torch.cuda.device(dev), torch.no_grad():
-        f32 = lambda t: t.detach().to(device=dev, dtype=torch.float32).contiguous()
-        locd, loctd = f32(loc_data), f32(loc_t)
-        posd = pos.detach().to(device=dev).ne(0).to(torch.uint8).contiguous()
+        locd, loctd, posd = LC.f32(loc_data, dev), LC.f32(loc_t, dev), LC.mask_u8(pos, dev)
         loss = torch.empty(1, dtype=torch.float32, device=dev)
         dloc = torch.empty(B, P, 4, dtype=torch.float32, device=dev) if want_grad else None
         d = L.MatchDesc()
         d.B, d.P = B, P
-        nbytes = L.lib().ymi_workspace_bytes(L.WS_BOX_LOSS, C.byref(d))
-        if nbytes < 0:
-            L.check(int(nbytes), 'ymi_workspace_bytes(YMI_WS_BOX_LOSS)')
-        ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
+        ws = LC.workspace('BOX_LOSS', d, dev)
         L.check(L.lib().ymi_box_loss_f32(locd.data_ptr(), loctd.data_ptr(), posd.data_ptr(), B, P, float(bbox_alpha),
                                          loss.data_ptr(), None if dloc is None else dloc.data_ptr(), ws.data_ptr(),
                                          L.stream_ptr()), 'ymi_box_loss_f32')
         return loss, dloc
 
 
-class _BoxLossFunction(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, loc_data, loc_t, pos, bbox_alpha):
-        loss, dloc = _box_loss_launch(loc_data, loc_t, pos, bbox_alpha, ctx.needs_input_grad[0])
-        ctx.grad = dloc
-        ctx.dtype = loc_data.dtype
-        return loss.reshape(())
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, g):
-        return (None if ctx.grad is None else (ctx.grad * g).to(ctx.dtype)), None, None, None
-
-
 def box_loss(loc_data, loc_t, pos):
     """loc_data, loc_t [B,P,4], pos [B,P] bool -> {'B': cfg.bbox_alpha * smooth_l1(loc_data[pos], loc_t[pos], sum)}."""
     cfg = active_cfg()
     check_switches(cfg)
-    return {'B': _BoxLossFunction.apply(loc_data, loc_t, pos, float(cfg.bbox_alpha))}
+    return {'B': LC.LossFunction.apply(_box_loss_launch, 1, loc_data, loc_t, pos, float(cfg.bbox_alpha))}

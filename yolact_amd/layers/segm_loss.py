@@ -18,11 +18,10 @@ from __future__ import annotations
 import ctypes as C
 
 import torch
-import torch.nn.functional as F
-from torch.autograd.function import once_differentiable
 
 from .. import _lib as L
 from ..config import active_cfg
+from . import _loss_common as LC
 
 
 def _launch(segm, gt, label, gt_off, alpha, want_grad):
@@ -38,11 +37,8 @@ def _launch(segm, gt, label, gt_off, alpha, want_grad):
     B, K, mh, mw = segm.shape
     G = gt.size(0)
     with torch.cuda.device(dev), torch.no_grad():
-        segmd = segm.detach().to(dtype=torch.float32).contiguous()
-        gtd = gt.detach().to(device=dev).ne(0).to(torch.uint8).contiguous() if gt.dtype != torch.uint8 else gt.detach().contiguous()
-        labeld = label.detach().to(device=dev, dtype=torch.int32).contiguous()
-        off_h = (C.c_int32 * (B + 1))(*gt_off)
-        off_d = torch.tensor(gt_off, dtype=torch.int32).to(dev)
+        segmd, gtd, labeld = LC.f32(segm, dev), LC.mask_u8(gt, dev), LC.i32(label, dev)
+        off_h, off_d = LC.offsets(gt_off, dev)
         loss = torch.empty(1, dtype=torch.float32, device=dev)
         dsegm = torch.empty(B, K, mh, mw, dtype=torch.float32, device=dev) if want_grad else None
         d = L.SegmLossDesc()
@@ -51,32 +47,14 @@ def _launch(segm, gt, label, gt_off, alpha, want_grad):
             d.gt, d.label = gtd.data_ptr(), labeld.data_ptr()
         d.d_segm = None if dsegm is None else dsegm.data_ptr()
         d.B, d.K, d.mh, d.mw, d.G, d.alpha = B, K, mh, mw, G, float(alpha)
-        nbytes = L.lib().ymi_workspace_bytes(L.WS_SEGM_LOSS, C.byref(d))
-        if nbytes < 0:
-            L.check(int(nbytes), 'ymi_workspace_bytes(YMI_WS_SEGM_LOSS)')
-        ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
-        d.ws = ws.data_ptr()
+        ws = LC.workspace('SEGM_LOSS', d, dev)
         L.check(L.lib().ymi_segm_loss_f32(C.byref(d), L.stream_ptr()), 'ymi_segm_loss_f32')
         return loss, dsegm
 
 
-class _SegmLossFunction(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, segm, gt, label, gt_off, alpha):
-        loss, dsegm = _launch(segm, gt, label, gt_off, alpha, ctx.needs_input_grad[0])
-        ctx.grad = dsegm
-        ctx.dtype = segm.dtype
-        return loss.reshape(())
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, g):
-        return (None if ctx.grad is None else (ctx.grad * g).to(ctx.dtype)), None, None, None, None
-
-
 def segm_loss(segm, gt, label, gt_off, alpha=1.0):
     """segm [B,K,mh,mw], gt [G,mh,mw] 0 / 1, label [G], gt_off B + 1 offsets -> alpha / (mh mw) * the summed BCE with logits."""
-    return _SegmLossFunction.apply(segm, gt, label, gt_off, float(alpha))
+    return LC.LossFunction.apply(_launch, 1, segm, gt, label, gt_off, float(alpha))
 
 
 def segm_terms(segm, gt, label, gt_off, alpha=1.0):
@@ -90,8 +68,7 @@ def downsample_targets(mask_t, class_t, mask_h, mask_w, device):
     with torch.no_grad():
         for m, c in zip(mask_t, class_t):
             if m.size(0):
-                down = F.interpolate(m.unsqueeze(0), (mask_h, mask_w), mode='bilinear', align_corners=False).squeeze(0)
-                gts.append(down.gt(0.5).to(torch.uint8))
+                gts.append(LC.downsample_gt(m, mask_h, mask_w))
                 labels.append(c.long())
             off.append(off[-1] + m.size(0))
     gt = torch.cat(gts) if gts else torch.zeros(0, mask_h, mask_w, dtype=torch.uint8, device=device)
