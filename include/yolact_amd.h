@@ -696,6 +696,84 @@ typedef struct ymi_segm_loss_desc {
 } ymi_segm_loss_desc;
 int ymi_segm_loss_f32(const ymi_segm_loss_desc *d, void *stream);
 
+/* -- the mask-IoU term 'I' of YOLACT++ (layers/modules/multibox_loss.py:629-672, 684-694; csrc/maskiou_loss.hip; additive at ABI 9) --
+ * fp32 throughout, no floating-point atomics: the same inputs give the same bits.  No error path launches anything.
+ *
+ * ymi_maskiou_input_f32: the instances as ymi_mask_loss_f32 takes them -> the net's input and its targets, one launch:
+ *     x0[j,r,c] = inside_j(r,c) ? sigmoid(sum_k proto[b,r,c,k] coef[j,k]) : 0      (the crop window of ymi_mask_loss_f32, padding 1)
+ *     iou_t[j]  = inter / ((a1 + a2) - inter):  a1 = window pixels with logit > 0, a2 = set pixels of the whole GT row, inter = both
+ * The reference binarises sigmoid > 0.5 in fp32; logit > 0 is the same decision except for logits in (0, ~6e-8], whose fp32
+ * sigmoid rounds to 0.5.  A union of 0 gives the reference's NaN.
+ * ymi_maskiou_input_bwd_f32: g = inside ? d_x0 p (1 - p) : 0;  d_proto[b,pix,k] = sum_j g coef[j,k] (every element written),
+ *     d_coef[j,k] = sum_pix g proto[b,pix,k]; either may be NULL, not both.  Two launches (one without d_coef).
+ * YMI_ESHAPE: K != 32, mh*mw >= 2^24, N >= 2^24, proto / d_proto / ws not 16-byte aligned, ws_bytes too small; YMI_EARG: B outside
+ * 1..65535, mh / mw / N / G < 1, img_off_host not starting at 0, ending at N or decreasing; YMI_ENULL: a pointer the call reads or
+ * writes is NULL. */
+typedef struct ymi_maskiou_input_desc {
+  const float *proto;           /* [B,mh,mw,K] */
+  const float *coef;            /* [N,K] */
+  const float *box;             /* [N,4] relative point form */
+  const uint8_t *gt;            /* [G,mh,mw] 0 / non-zero (forward only) */
+  const int32_t *gt_idx;        /* [N] row of gt, clamped to 0..G-1 (forward only) */
+  const int32_t *img_off;       /* DEVICE [B+1]: the instances of image b are [img_off[b], img_off[b+1]) */
+  const int32_t *img_off_host;  /* HOST   [B+1]: the same values */
+  float *x0;                    /* [N,mh,mw] (forward) */
+  float *iou_t;                 /* [N] (forward) */
+  const float *d_x0;            /* [N,mh,mw] (backward) */
+  float *d_proto;               /* [B,mh,mw,K] (backward; may be NULL) */
+  float *d_coef;                /* [N,K] (backward; may be NULL) */
+  void *ws;                     /* backward with d_coef: ymi_workspace_bytes(YMI_WS_MASKIOU_INPUT, desc) bytes, 16-byte aligned */
+  int64_t ws_bytes;
+  int32_t B, mh, mw, K, N, G;
+} ymi_maskiou_input_desc;
+int ymi_maskiou_input_f32(const ymi_maskiou_input_desc *d, void *stream);
+int ymi_maskiou_input_bwd_f32(const ymi_maskiou_input_desc *d, void *stream);
+
+/* The backward of y = relu?(conv(x, w) + b) as ymi_conv2d_direct_nhwc_f32 computes it, for any kernel size, stride and padding it
+ * accepts.  With relu = 1, dy is first masked by y > 0 (y = the layer's post-ReLU output).
+ *     dx[n,iy,ix,ci] = sum over the output pixels that read (iy, ix), taps in (ky, kx) order, of sum_co dy w[(ky kw + kx) Cin + ci, co];
+ *                      a pixel no window reaches gets an exact zero.  One launch.
+ *     dw[k,co] = sum_pos im2col(x)[pos,k] dy[pos,co], db[co] = sum_pos dy[pos,co], pos = (n, oy, ox) in order: the positions are cut
+ *                      into chunks whose partial sums go to ws (launch one: the tile of [K + 1, Cout] a block owns and the number
+ *                      of chunks follow the shape) and are added in chunk order (launch two).
+ * dx, or dw and db together, may be NULL.  w and dw are [kh*kw*Cin, ceil4(Cout)], the forward's layout (dw's padding columns are
+ * written as zeros).  YMI_EARG: a size < 1, pad < 0, relu not 0 / 1; YMI_ESHAPE: Ho / Wo not the convolution's, w / y / dy / ws not
+ * 16-byte aligned, ws_bytes too small, more than 65535 tiles of [K + 1, Cout] (tiles of 64 x 64 for wide layers); YMI_ENULL: dy NULL, y NULL with relu, nothing to compute, w NULL with dx, x or ws NULL with dw / db. */
+typedef struct ymi_conv_bwd_desc {
+  const float *x;               /* [B,H,W,Cin] */
+  const float *w;               /* [kh*kw*Cin, ceil4(Cout)], k = (ky*kw + kx)*Cin + ci */
+  const float *y;               /* [B,Ho,Wo,Cout] */
+  const float *dy;              /* [B,Ho,Wo,Cout] */
+  float *dx;                    /* [B,H,W,Cin] */
+  float *dw;                    /* [kh*kw*Cin, ceil4(Cout)] */
+  float *db;                    /* [Cout] */
+  void *ws;                     /* ymi_workspace_bytes(YMI_WS_CONV_BWD, desc) bytes, 16-byte aligned */
+  int64_t ws_bytes;
+  int32_t B, H, W, Cin, Ho, Wo, Cout, kh, kw, stride, pad, relu;
+} ymi_conv_bwd_desc;
+int ymi_conv2d_bwd_nhwc_f32(const ymi_conv_bwd_desc *d, void *stream);
+
+/* The backward of ymi_global_maxpool_nhwc_f32: dy[n,q,c] = d_pool[n,c] at the FIRST q (row-major) where y[n,q,c] is the maximum, 0
+ * elsewhere: the tie rule of torch's CPU max_pool2d. */
+int ymi_global_maxpool_bwd_nhwc_f32(const float *y, const float *d_pool, float *dy, int B, int HW, int C, void *stream);
+
+/* The head of 'I': p_n = pool[n,label[n]], loss = alpha sum_n smooth_l1(p_n - iou_t[n]) (beta 1, summed in ymi's fixed tree),
+ * d_pool[n,c] = c == label[n] ? alpha smooth_l1'(p_n - iou_t[n]) : 0.  Two launches.  YMI_EARG: N / C < 1; YMI_ESHAPE: ws_bytes too
+ * small; YMI_ENULL: pool, iou_t, label, loss or ws NULL. */
+typedef struct ymi_maskiou_head_desc {
+  const float *pool;            /* [N,C] */
+  const float *iou_t;           /* [N] */
+  const int32_t *label;         /* [N], clamped to 0..C-1 */
+  float *loss;                  /* [1] */
+  float *d_pool;                /* [N,C]; may be NULL */
+  void *ws;                     /* ymi_workspace_bytes(YMI_WS_MASKIOU_HEAD, desc) bytes */
+  int64_t ws_bytes;
+  int32_t N, C;
+  float alpha;                  /* cfg.maskiou_alpha */
+  int32_t _pad0;
+} ymi_maskiou_head_desc;
+int ymi_maskiou_head_f32(const ymi_maskiou_head_desc *d, void *stream);
+
 /* -- ResNet stem in one launch (backbone.py:126-133 + the layout change of yolact.py:564) ---------------------------------
  * x [B,3,H,W] NCHW fp32 (the normalised image) -> conv 7x7 / 2 / pad 3 (3 -> 64) + folded BN + ReLU -> max-pool 3x3 / 2 / pad 1
  * -> y [B,Hp,Wp,64] NHWC fp32, Hp = ((H - 1) / 2 + 1 - 1) / 2 + 1.  The 64-channel stem output stays in LDS (csrc/stem.hip).
@@ -805,8 +883,11 @@ enum {
   YMI_WS_CLASS_LOSS = 19,       /* desc: ymi_class_loss_desc, B / P / C read -> ymi_class_loss_desc.ws: per prior the mining key and lse,
                                  * per tile the positives and the loss partial: 4 * (2 B P + 2 B T) bytes, T = ceil(P / R),
                                  * R = min(128, 10752 / (C | 1)) rows per tile, each part padded to 16 */
-  YMI_WS_SEGM_LOSS = 20         /* desc: ymi_segm_loss_desc, B / mh / mw read -> ymi_segm_loss_desc.ws: 4 B ceil(mh*mw / 256) bytes,
+  YMI_WS_SEGM_LOSS = 20,        /* desc: ymi_segm_loss_desc, B / mh / mw read -> ymi_segm_loss_desc.ws: 4 B ceil(mh*mw / 256) bytes,
                                  * padded to 16 */
+  YMI_WS_MASKIOU_INPUT = 21,    /* desc: ymi_maskiou_input_desc, mh / mw / N read -> its ws: ceil(mh*mw / 256) * N * 32 floats */
+  YMI_WS_CONV_BWD = 22,         /* desc: ymi_conv_bwd_desc, the shape read -> its ws: chunks * (kh*kw*Cin + 1) * ceil4(Cout) floats */
+  YMI_WS_MASKIOU_HEAD = 23      /* desc: ymi_maskiou_head_desc, N read -> its ws: N floats, padded to 16 */
 };
 typedef struct { int32_t A, B; int64_t n; } ymi_mask_iou_shape;
 typedef struct { int32_t N, h, w, cap; } ymi_rle_shape;      /* cap <= 0: the safe capacity h*w + 1 */

@@ -147,6 +147,30 @@ class SegmLossDesc(C.Structure):
                 ('B', C.c_int32), ('K', C.c_int32), ('mh', C.c_int32), ('mw', C.c_int32), ('G', C.c_int32), ('alpha', C.c_float)]
 
 
+class MaskIouInputDesc(C.Structure):
+    """include/yolact_amd.h ymi_maskiou_input_desc."""
+    _fields_ = [('proto', C.c_void_p), ('coef', C.c_void_p), ('box', C.c_void_p), ('gt', C.c_void_p), ('gt_idx', C.c_void_p),
+                ('img_off', C.c_void_p), ('img_off_host', C.c_void_p), ('x0', C.c_void_p), ('iou_t', C.c_void_p),
+                ('d_x0', C.c_void_p), ('d_proto', C.c_void_p), ('d_coef', C.c_void_p), ('ws', C.c_void_p), ('ws_bytes', C.c_int64),
+                ('B', C.c_int32), ('mh', C.c_int32), ('mw', C.c_int32), ('K', C.c_int32), ('N', C.c_int32), ('G', C.c_int32)]
+
+
+class ConvBwdDesc(C.Structure):
+    """include/yolact_amd.h ymi_conv_bwd_desc."""
+    _fields_ = [('x', C.c_void_p), ('w', C.c_void_p), ('y', C.c_void_p), ('dy', C.c_void_p), ('dx', C.c_void_p), ('dw', C.c_void_p),
+                ('db', C.c_void_p), ('ws', C.c_void_p), ('ws_bytes', C.c_int64),
+                ('B', C.c_int32), ('H', C.c_int32), ('W', C.c_int32), ('Cin', C.c_int32), ('Ho', C.c_int32), ('Wo', C.c_int32),
+                ('Cout', C.c_int32), ('kh', C.c_int32), ('kw', C.c_int32), ('stride', C.c_int32), ('pad', C.c_int32),
+                ('relu', C.c_int32)]
+
+
+class MaskIouHeadDesc(C.Structure):
+    """include/yolact_amd.h ymi_maskiou_head_desc."""
+    _fields_ = [('pool', C.c_void_p), ('iou_t', C.c_void_p), ('label', C.c_void_p), ('loss', C.c_void_p), ('d_pool', C.c_void_p),
+                ('ws', C.c_void_p), ('ws_bytes', C.c_int64), ('N', C.c_int32), ('C', C.c_int32), ('alpha', C.c_float),
+                ('_pad0', C.c_int32)]
+
+
 class DetectDesc(C.Structure):
     _fields_ = [('conf', C.c_void_p), ('loc', C.c_void_p), ('coef', C.c_void_p), ('priors', C.c_void_p),
                 ('B', C.c_int32), ('P', C.c_int32), ('C', C.c_int32), ('D', C.c_int32),
@@ -237,7 +261,7 @@ class RleShape(C.Structure):
 # ymi_workspace_bytes selectors (include/yolact_amd.h YMI_WS_*)
 (WS_WINO_V, WS_WINO_M, WS_SPLITK, WS_MASK_IOU, WS_JPEG_COEFS, WS_JPEG_PLANES, WS_DETECT_SCORES_T, WS_DETECT_PER_PRIOR,
  WS_DETECT_CAND, WS_DETECT_REC, WS_AMAX_SLOT, WS_RLE_COUNTS, WS_DETECT_GREEDY, WS_JPEG_ENC, WS_JPEG_ENC_OUT,
- WS_MASK_LOSS, WS_MATCH, WS_BOX_LOSS, WS_CLASS_LOSS, WS_SEGM_LOSS) = range(1, 21)
+ WS_MASK_LOSS, WS_MATCH, WS_BOX_LOSS, WS_CLASS_LOSS, WS_SEGM_LOSS, WS_MASKIOU_INPUT, WS_CONV_BWD, WS_MASKIOU_HEAD) = range(1, 24)
 
 EFORMAT, EUNSUPPORTED = -4, -5
 
@@ -273,6 +297,11 @@ SYMBOLS = [
     ('ymi_box_loss_f32', C.c_int, [_P, _P, _P, _I, _I, _F, _P, _P, _P, _P]),
     ('ymi_class_loss_f32', C.c_int, [C.POINTER(ClassLossDesc), _P]),
     ('ymi_segm_loss_f32', C.c_int, [C.POINTER(SegmLossDesc), _P]),
+    ('ymi_maskiou_input_f32', C.c_int, [C.POINTER(MaskIouInputDesc), _P]),
+    ('ymi_maskiou_input_bwd_f32', C.c_int, [C.POINTER(MaskIouInputDesc), _P]),
+    ('ymi_conv2d_bwd_nhwc_f32', C.c_int, [C.POINTER(ConvBwdDesc), _P]),
+    ('ymi_global_maxpool_bwd_nhwc_f32', C.c_int, [_P, _P, _P, _I, _I, _I, _P]),
+    ('ymi_maskiou_head_f32', C.c_int, [C.POINTER(MaskIouHeadDesc), _P]),
     ('ymi_composite_masks_u8', C.c_int, [_P, _P, _P, _I, _I, _I, _F, _P, _P]),
     ('ymi_mask_iou_f32', C.c_int, [_P, _P, _I, _I, C.c_long, _I, _P, _P, _P]),
     ('ymi_jaccard_f32', C.c_int, [_P, _P, _I, _I, _I, _P, _P]),

@@ -76,6 +76,8 @@ _common = Cfg(
     use_objectness_score=False, use_class_existence_loss=False,
     use_semantic_segmentation_loss=True, freeze_bn=False,
     use_maskiou=False, maskiou_net=[], rescore_mask=False, rescore_bbox=False,
+    # the mask-IoU term of the training loss (layers/maskiou_loss.py; data/config.py:642-647)
+    maskiou_alpha=1.0, discard_mask_area=-1, maskious_to_train=-1,
     fpn=_fpn, max_size=550,
     # the mask term of the training loss (layers/mask_loss.py; data/config.py coco_base_config / yolact_base_config)
     mask_alpha=6.125, masks_to_train=100, mask_proto_crop=True, mask_proto_normalize_emulate_roi_pooling=True,
@@ -114,7 +116,7 @@ CONFIGS = {
         backbone=_backbone('ResNet101', 'resnet', _R101, [1, 2, 3],
                            [[int(s[0] / 550 * 700)] for s in _base_scales], True))),
 }
-_plus = dict(use_maskiou=True, rescore_mask=True, rescore_bbox=False,
+_plus = dict(use_maskiou=True, rescore_mask=True, rescore_bbox=False, maskiou_alpha=25, discard_mask_area=5 * 5,      # :787-791
              maskiou_net=[(8, 3, {'stride': 2}), (16, 3, {'stride': 2}), (32, 3, {'stride': 2}),
                           (64, 3, {'stride': 2}), (128, 3, {'stride': 2})])
 CONFIGS['yolact_plus_base_config'] = _common.copy(dict(

@@ -25,11 +25,12 @@ from ... import _lib as L
 from ...config import active_cfg, is_lincomb
 
 
-def check_switches(cfg):
-    """NotImplementedError naming the cfg field for every loss term or switch that does not exist here."""
+def check_switches(cfg, allow_maskiou=False):
+    """NotImplementedError naming the cfg field for every loss term or switch that does not exist here (allow_maskiou: the caller,
+    multibox_loss_plus.MultiBoxLossPlus, computes the term 'I')."""
     def refuse(field, why):
         raise NotImplementedError('yolact_amd MultiBoxLoss: cfg.%s = %r is not supported (%s)' % (field, getattr(cfg, field), why))
-    if cfg.use_maskiou:
+    if cfg.use_maskiou and not allow_maskiou:
         refuse('use_maskiou', "the mask-IoU term 'I' of the YOLACT++ configs is not implemented")
     if cfg.mask_proto_loss is not None:
         refuse('mask_proto_loss', "the prototype term 'P' is not implemented")
@@ -57,6 +58,10 @@ class MultiBoxLoss(nn.Module):
     def forward(self, net, predictions, targets, masks, num_crowds):
         cfg = active_cfg()
         check_switches(cfg)
+        return self._losses(cfg, net, predictions, targets, masks, num_crowds, maskiou=False)
+
+    def _losses(self, cfg, net, predictions, targets, masks, num_crowds, maskiou):
+        """The terms of forward(); maskiou: also 'I' (multibox_loss_plus.MultiBoxLossPlus)."""
         loc_data, conf_data, mask_data = predictions['loc'], predictions['conf'], predictions['mask']
         priors, proto_data = predictions['priors'], predictions['proto']
         for name in ('loc', 'conf', 'mask', 'priors', 'proto'):
@@ -82,10 +87,18 @@ class MultiBoxLoss(nn.Module):
         conf_t, idx_t, pos = m['conf_t'], m['idx_t'], m['pos']
 
         losses = MT.box_loss(loc_data, m['loc_t'], pos)
-        losses.update(ML.lincomb_mask_loss(pos, idx_t, mask_data, proto_data, obj_masks, m['gt_box_t']))
+        maskiou_targets = None
+        if maskiou:
+            from .. import maskiou_loss as MIL
+            ret, maskiou_targets = MIL.lincomb_mask_loss_maskiou(pos, idx_t, mask_data, proto_data, obj_masks, m['gt_box_t'], labels)
+            losses.update(ret)
+        else:
+            losses.update(ML.lincomb_mask_loss(pos, idx_t, mask_data, proto_data, obj_masks, m['gt_box_t']))
         losses['C'] = CL.ohem_conf_loss(conf_data, conf_t, self.negpos_ratio)
         if cfg.use_semantic_segmentation_loss:
             losses['S'] = SL.semantic_segmentation_loss(predictions['segm'], obj_masks, labels)
+        if maskiou_targets is not None:                                      # :186-188
+            losses['I'] = MIL.mask_iou_loss(net, maskiou_targets)
 
         # :196-203
         total_num_pos = m['num_pos'].sum().float()

@@ -4,7 +4,7 @@ These nn.Modules only HOLD parameters under the reference's names so that `Yolac
 the reference checkpoints unchanged (SURVEY §8(a) a18: backbone.conv1/bn1, backbone.layers.{s}.{i}.{conv,bn}{1,2,3}
 [.conv_offset_mask], ...downsample.{0,1}, fpn.{lat,pred,downsample}_layers.{i}, proto_net.{0,2,4,8,10},
 prediction_layers.0.{upfeature.0,bbox_layer,conf_layer,mask_layer}, semantic_seg_conv,
-maskiou_net.maskiou_net.{0,2,..,10}).  They never compute: the arithmetic is done by the HIP engine
+maskiou_net.maskiou_net.{0,2,..,10}).  Apart from DCN and FastMaskIoUNet they never compute: the arithmetic is done by the HIP engine
 (yolact_amd/engine.py), which reads these tensors once, folds BatchNorm and re-lays the filters.
 """
 from __future__ import annotations
@@ -160,9 +160,16 @@ class PredictionModule(_NoCompute):
             self.mask_layer = nn.Conv2d(out_channels, num_priors * mask_dim, **head_layer_params)
 
 
-class FastMaskIoUNet(_NoCompute):
-    """yolact.py:363-369 layout."""
+class FastMaskIoUNet(nn.Module):
+    """yolact.py:363-369 layout.  Like DCN this container computes when called on its own: forward runs the convolutions, the
+    ReLUs and the global max-pool on the HIP kernels from the CURRENT parameter values, once differentiable in x and in every weight
+    and bias (layers/maskiou_loss.py).  Inference (Yolact.maskiou_forward) keeps its own packed filters."""
 
     def __init__(self, maskiou_net_cfg, num_classes):
         super().__init__()
         self.maskiou_net, _ = make_net(1, list(maskiou_net_cfg) + [(num_classes - 1, 1, {})], include_last_relu=True)
+
+    def forward(self, x):
+        """x [N,1,H,W] on the GPU -> [N, num_classes - 1] (yolact.py:371-375)."""
+        from .layers.maskiou_loss import maskiou_net_apply
+        return maskiou_net_apply(self.maskiou_net, x)
