@@ -774,6 +774,41 @@ typedef struct ymi_maskiou_head_desc {
 } ymi_maskiou_head_desc;
 int ymi_maskiou_head_f32(const ymi_maskiou_head_desc *d, void *stream);
 
+/* -- the backward of the train-mode heads and protonet (csrc/conv_train.hip; additive, the ABI number stays) -----------------------
+ * Stride-1 convolutions (3x3 / pad 1, 1x1 / pad 0), ReLU, tanh and the x2 bilinear upsample (yolact.py:133-212, 580-647).  No
+ * floating-point atomics anywhere: the same inputs give the same bits.  The DATA gradient of such a convolution is
+ * ymi_conv2d_nhwc_f32 on g with the filters flipped in both taps and transposed in (Cin, Cout); it has no entry of its own.
+ *
+ * ymi_act_bwd_f32: g[pos,c] = dy[pos,c] * act'(y[pos,c]) for c < C from the layer's OUTPUT y (YMI_ACT_RELU: y > 0 ? 1 : 0,
+ * YMI_ACT_TANH: 1 - y^2, YMI_ACT_NONE: 1, y may be NULL), g[pos,c] = 0 for C <= c < cpad.  ldy / lddy / ldg: the channel strides.
+ * YMI_EARG: another activation, npos / C < 1; YMI_ESHAPE: cpad < C, ldg < cpad, lddy < C, ldy < C; YMI_ENULL: dy, g, or y with an
+ * activation. */
+int ymi_act_bwd_f32(const float *y, const float *dy, float *g, long npos, int C, int cpad, int ldy, int lddy, int ldg, int act,
+                    void *stream);
+
+/* dw[k,co] = sum_pos im2col(x)[pos,k] g[pos,co] (k = (ky*kw + kx)*Cin + ci), db[co] = sum_pos g[pos,co], pos = (n, oy, ox), on the
+ * exact-fp32 matrix instruction with the positions as its k index.  The positions are cut into chunks whose partial sums go to ws
+ * (launch one) and are added in chunk order (launch two).  dw or db may be NULL.  YMI_EARG: a size < 1, a geometry other than
+ * 3x3 / pad 1 and 1x1 / pad 0; YMI_ESHAPE: Cin % 32, ldg < Cout, x or g of 2^29 elements or more (2 GiB, the conv engine's limit), ws not 16-byte aligned, ws_bytes
+ * too small; YMI_ENULL: g or ws NULL, nothing to compute, x NULL with dw.  No error path launches anything. */
+typedef struct ymi_conv_wgrad_desc {
+  const float *x;               /* [B,H,W,Cin] */
+  const float *g;               /* [B,H,W,ldg], channels [0, Cout) are read */
+  float *dw;                    /* [kh*kw*Cin, Cout] */
+  float *db;                    /* [Cout] */
+  void *ws;                     /* ymi_workspace_bytes(YMI_WS_CONV_WGRAD, desc) bytes, 16-byte aligned */
+  int64_t ws_bytes;
+  int32_t B, H, W, Cin, Cout, ldg, kh, kw, pad, _pad0;
+} ymi_conv_wgrad_desc;
+int ymi_conv_wgrad_nhwc_f32(const ymi_conv_wgrad_desc *d, void *stream);
+
+/* The backward of ymi_bilinear_nhwc_f32 (align_corners=False, optional ReLU: dy is masked by y > 0, y = its output) for Ho = 2 Hi,
+ * Wo = 2 Wi, odd sizes included, as a gather: dx[b,iy,ix,c] sums the output pixels that read (iy, ix), rows then columns in order,
+ * with the coordinates of the forward.  YMI_ESHAPE: another ratio, C % 4, a pointer not 16-byte aligned; YMI_EARG: a size < 1, relu
+ * not 0 / 1; YMI_ENULL: dy, dx, or y with relu. */
+int ymi_bilinear_bwd_nhwc_f32(const float *dy, const float *y, float *dx, int B, int Hi, int Wi, int C, int Ho, int Wo, int relu,
+                              void *stream);
+
 /* -- ResNet stem in one launch (backbone.py:126-133 + the layout change of yolact.py:564) ---------------------------------
  * x [B,3,H,W] NCHW fp32 (the normalised image) -> conv 7x7 / 2 / pad 3 (3 -> 64) + folded BN + ReLU -> max-pool 3x3 / 2 / pad 1
  * -> y [B,Hp,Wp,64] NHWC fp32, Hp = ((H - 1) / 2 + 1 - 1) / 2 + 1.  The 64-channel stem output stays in LDS (csrc/stem.hip).
@@ -887,7 +922,9 @@ enum {
                                  * padded to 16 */
   YMI_WS_MASKIOU_INPUT = 21,    /* desc: ymi_maskiou_input_desc, mh / mw / N read -> its ws: ceil(mh*mw / 256) * N * 32 floats */
   YMI_WS_CONV_BWD = 22,         /* desc: ymi_conv_bwd_desc, the shape read -> its ws: chunks * (kh*kw*Cin + 1) * ceil4(Cout) floats */
-  YMI_WS_MASKIOU_HEAD = 23      /* desc: ymi_maskiou_head_desc, N read -> its ws: N floats, padded to 16 */
+  YMI_WS_MASKIOU_HEAD = 23,     /* desc: ymi_maskiou_head_desc, N read -> its ws: N floats, padded to 16 */
+  YMI_WS_CONV_WGRAD = 24        /* desc: ymi_conv_wgrad_desc, the shape read -> its ws: chunks * kh*kw*Cin * Cout floats and chunks *
+                                 * Cout floats, each part padded to 16 */
 };
 typedef struct { int32_t A, B; int64_t n; } ymi_mask_iou_shape;
 typedef struct { int32_t N, h, w, cap; } ymi_rle_shape;      /* cap <= 0: the safe capacity h*w + 1 */

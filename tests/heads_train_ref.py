@@ -1,0 +1,224 @@
+"""The train-mode heads of Yolact (yolact.py:133-212, 579-647) in plain torch, written from the semantics: protonet, the shared
+prediction head over the pyramid levels, semantic_seg_conv.  The oracle of tests/test_heads_train_host.py (pinned there to what the
+reference itself computed: tests/golden/heads_train.npz, tools/make_golden_heads_train.py) and of tests/test_gpu_heads_train.py.
+
+Everything works in the dtype given (fp32 or fp64) on the CPU.  Parameters are a dict under the state-dict names
+(proto_net.N.weight, prediction_layers.0.upfeature.N.weight, prediction_layers.0.{bbox,conf,mask}_layer.weight, semantic_seg_conv.weight
+and the biases).
+"""
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+import helpers
+from packed_fixture import QBITS, ints_of, pack, pack5, planes_of, unpack, unpack5  # noqa: F401
+from helpers import rel_err  # noqa: F401
+
+OUT_NAMES = ('loc', 'conf', 'mask', 'proto', 'segm')
+GOLDEN_PYRAMID, GOLDEN_B, GOLDEN_NF, GOLDEN_CLASSES, GOLDEN_MAX_SIZE = (12, 6, 3, 2, 1), 2, 32, 6, 96
+PARAM_GRID = 2048   # parameters are multiples of 1 / PARAM_GRID (exact in fp16 and fp32), stored as their int16 numerators
+
+
+def golden_cfg_overrides():
+    """The replacements tools/make_golden_heads_train.py makes in yolact_resnet50_config (as (channels, kernel, kwargs) specs)."""
+    nf = GOLDEN_NF
+    return dict(num_features=nf, num_classes=GOLDEN_CLASSES, max_size=GOLDEN_MAX_SIZE,
+                mask_proto_net=[(nf, 3, {'padding': 1})] * 3 + [(None, -2, {}), (nf, 3, {'padding': 1}), (32, 1, {})],
+                extra_head_net=[(nf, 3, {'padding': 1})])
+
+
+def spec_of(cfg):
+    """What the oracle reads of a config (yolact_amd.config.Cfg or the reference's Config)."""
+    from yolact_amd.config import act_name
+    return dict(mask_proto_net=list(cfg.mask_proto_net), extra_head_net=cfg.extra_head_net, head_layer_params=dict(cfg.head_layer_params),
+                num_classes=int(cfg.num_classes), max_size=cfg.max_size, backbone=cfg.backbone, proto_src=cfg.mask_proto_src,
+                coef_act=act_name(cfg.mask_proto_coeff_activation), proto_act=act_name(cfg.mask_proto_prototype_activation),
+                segm=bool(cfg.use_semantic_segmentation_loss))
+
+
+def param_names(spec):
+    """The state-dict names of the head side, in module order."""
+    names = []
+    for i, (ch, k, kw) in enumerate(spec['mask_proto_net']):
+        if ch is not None:
+            names += ['proto_net.%d.weight' % (2 * i), 'proto_net.%d.bias' % (2 * i)]
+    for i, (ch, k, kw) in enumerate(spec['extra_head_net'] or []):
+        names += ['prediction_layers.0.upfeature.%d.weight' % (2 * i), 'prediction_layers.0.upfeature.%d.bias' % (2 * i)]
+    for l in ('bbox', 'conf', 'mask'):
+        names += ['prediction_layers.0.%s_layer.weight' % l, 'prediction_layers.0.%s_layer.bias' % l]
+    if spec['segm']:
+        names += ['semantic_seg_conv.weight', 'semantic_seg_conv.bias']
+    return names
+
+
+def _act(z, name):
+    return z if name == 'none' else {'relu': F.relu, 'tanh': torch.tanh}[name](z)
+
+
+def net_ref(x, layers, params, prefix, last_act, keep=None):
+    """utils/functions.py:163-213 make_net: every layer is followed by a ReLU, the last one by `last_act` ('relu', 'none', ..).
+    keep receives (name, pre-activation, activation) of every convolution that feeds a ReLU (the ReLU behind the interpolation sees a
+    sum of non-negatives and is not recorded)."""
+    for i, (ch, k, kw) in enumerate(layers):
+        act = 'relu' if i + 1 < len(layers) else last_act
+        if ch is None:
+            x = _act(F.interpolate(x, scale_factor=-k, mode='bilinear', align_corners=False), act)
+            continue
+        name = '%s%d' % (prefix, 2 * i)
+        z = F.conv2d(x, params[name + '.weight'], params[name + '.bias'], **kw)
+        x = _act(z, act)
+        if keep is not None and act == 'relu':
+            keep.append((name, z, x))
+    return x
+
+
+def priors_ref(sizes, spec):
+    from yolact_amd.config import make_priors_host
+    bb = spec['backbone']
+    data = []
+    for lvl, (h, w) in enumerate(sizes):
+        data += make_priors_host(h, w, bb.pred_scales[lvl], bb.pred_aspect_ratios[lvl], spec['max_size'], bb)
+    return torch.tensor(data, dtype=torch.float32).view(-1, 4)
+
+
+def heads_ref(outs, params, spec, keep=None, priors=None):
+    """outs: the FPN maps [B,nf,h_i,w_i] (NCHW, any float dtype, leaves or not); params: name -> tensor of the same dtype ->
+    {'loc' [B,P,4], 'conf' [B,P,C], 'mask' [B,P,D], 'priors' [P,4] fp32, 'proto' [B,2h_0,2w_0,D], 'segm' [B,C-1,h_0,w_0]}."""
+    B = outs[0].shape[0]
+    proto = net_ref(outs[spec['proto_src']], spec['mask_proto_net'], params, 'proto_net.', spec['proto_act'], keep)
+    pred = {'loc': [], 'conf': [], 'mask': []}
+    hp = {k: v for k, v in spec['head_layer_params'].items() if k != 'kernel_size'}
+    for x in outs:
+        if spec['extra_head_net'] is not None:
+            x = net_ref(x, spec['extra_head_net'], params, 'prediction_layers.0.upfeature.', 'relu', keep)
+        for name, width, act in (('loc', 4, 'none'), ('conf', spec['num_classes'], 'none'), ('mask', None, spec['coef_act'])):
+            layer = 'prediction_layers.0.%s_layer' % {'loc': 'bbox', 'conf': 'conf', 'mask': 'mask'}[name]
+            z = F.conv2d(x, params[layer + '.weight'], params[layer + '.bias'], **hp)
+            if width is None:
+                width = proto.shape[1]
+            pred[name].append(_act(z.permute(0, 2, 3, 1).contiguous().view(B, -1, width), act))
+    out = {k: torch.cat(v, -2) for k, v in pred.items()}
+    out['priors'] = priors_ref([tuple(o.shape[2:]) for o in outs], spec) if priors is None else priors
+    out['proto'] = proto.permute(0, 2, 3, 1).contiguous()
+    if spec['segm']:
+        out['segm'] = F.conv2d(outs[0], params['semantic_seg_conv.weight'], params['semantic_seg_conv.bias'])
+    return out
+
+
+def run_ref(outs, params, spec, ups, dtype, keep=None):
+    """Forward and the gradients of sum_k <pred_k, ups_k> -> dict(out name -> tensor, 'd_out%d' -> d leaf, 'd_' + name -> d param)."""
+    leaves = [o.detach().to(dtype).requires_grad_(True) for o in outs]
+    names = param_names(spec)
+    P = {n: params[n].detach().to(dtype).requires_grad_(True) for n in names}
+    with helpers.oracle_threads():                       # torch's CPU summation order depends on the thread count
+        pred = heads_ref(leaves, P, spec, keep)
+        total = sum((pred[k] * ups[k].to(dtype)).sum() for k in OUT_NAMES if k in pred)
+        g = torch.autograd.grad(total, leaves + [P[n] for n in names], retain_graph=keep is not None)
+    res = {k: pred[k].detach() for k in OUT_NAMES if k in pred}
+    res['priors'] = pred['priors']
+    res.update({'d_out%d' % i: t for i, t in enumerate(g[:len(leaves)])})
+    res.update({'d_' + n: t for n, t in zip(names, g[len(leaves):])})
+    res['_total'], res['_pred'] = total, pred
+    return res
+
+
+def relu_margins(outs, params, spec, ups):
+    """Per ReLU input (a recorded pre-activation tensor; the shared head's once per level): (name, the smallest |pre-activation|
+    whose activation receives gradient, in fp64; the largest fp32-versus-fp64 deviation of that tensor).  torch's CPU summation
+    order depends on the thread count, so the oracle runs with helpers.ORACLE_THREADS."""
+    res = {}
+    with helpers.oracle_threads():
+        for dtype in (torch.float64, torch.float32):
+            keep = []
+            r = run_ref(outs, params, spec, ups, dtype, keep)
+            ga = torch.autograd.grad(r['_total'], [a for _, _, a in keep], allow_unused=True)
+            res[dtype] = [(n, z.detach(), torch.zeros_like(a) if g is None else g) for (n, z, a), g in zip(keep, ga)]
+    out = []
+    for (n, z64, g), (_, z32, _) in zip(res[torch.float64], res[torch.float32]):
+        hit = g != 0
+        out.append((n, z64[hit].abs().min().item() if hit.any() else float('inf'), (z32.double() - z64).abs().max().item()))
+    return out
+
+
+def tightest(margins):
+    """The (name, margin, deviation) with the smallest margin / deviation."""
+    return min(margins, key=lambda m: m[1] / max(m[2], 1e-300))
+
+
+def param_shapes(spec, nf):
+    """name -> shape of every head-side parameter for nf FPN channels."""
+    bb = spec['backbone']
+    A = sum(len(a) * len(bb.pred_scales[0]) for a in bb.pred_aspect_ratios[0])
+    shapes, cin = {}, nf
+    for i, (ch, k, kw) in enumerate(spec['mask_proto_net']):
+        if ch is not None:
+            shapes['proto_net.%d.weight' % (2 * i)], shapes['proto_net.%d.bias' % (2 * i)] = (ch, cin, k, k), (ch,)
+            cin = ch
+    mask_dim, cin = cin, nf
+    for i, (ch, k, kw) in enumerate(spec['extra_head_net'] or []):
+        n = 'prediction_layers.0.upfeature.%d' % (2 * i)
+        shapes[n + '.weight'], shapes[n + '.bias'] = (ch, cin, k, k), (ch,)
+        cin = ch
+    k = spec['head_layer_params']['kernel_size']
+    for l, width in (('bbox', 4), ('conf', spec['num_classes']), ('mask', mask_dim)):
+        n = 'prediction_layers.0.%s_layer' % l
+        shapes[n + '.weight'], shapes[n + '.bias'] = (A * width, cin, k, k), (A * width,)
+    if spec['segm']:
+        shapes['semantic_seg_conv.weight'], shapes['semantic_seg_conv.bias'] = (spec['num_classes'] - 1, nf, 1, 1), (spec['num_classes'] - 1,)
+    return {n: shapes[n] for n in param_names(spec)}
+
+
+def grid(t, step):
+    """t rounded to multiples of 1 / step: exact in fp16 for |t| < 2048 / step."""
+    q = torch.round(t * step) / step
+    assert torch.equal(q.half().float(), q)
+    return q
+
+
+def random_case(seed, spec, nf, sizes, B):
+    """(outs, params, ups) on fp16-exact grids: maps ~ N(0, 1) in 1/256, weights ~ N(0, 2 / fan_in) in 1/2048 (the output layers,
+    which no ReLU follows, at half that deviation: trained heads are small there), biases in 1/2048, upstream gradients in
+    {-1, -1/2, 0, 1/2, 1}."""
+    g = torch.Generator().manual_seed(seed)
+    outs = [grid(torch.randn(B, nf, h, w, generator=g).clamp(-4, 4), 256) for h, w in sizes]
+    params = {}
+    for n, shp in param_shapes(spec, nf).items():
+        if n.endswith('weight'):
+            std = (2.0 / (shp[1] * shp[2] * shp[3])) ** 0.5 * (0.5 if ('_layer' in n or n.startswith('semantic')) else 1.0)
+            params[n] = grid((torch.randn(*shp, generator=g) * std).clamp(-0.9, 0.9), PARAM_GRID)
+        else:
+            params[n] = grid((torch.randn(*shp, generator=g) * 0.1).clamp(-0.9, 0.9), PARAM_GRID)
+    with torch.no_grad():
+        pred = heads_ref(outs, params, spec)
+    ups = {k: torch.randint(-2, 3, tuple(pred[k].shape), generator=g).float() / 2 for k in OUT_NAMES if k in pred}
+    return outs, params, ups
+
+
+def assert_margins(margins, factor=16):
+    """Every ReLU input keeps `factor` times its own fp32 deviation as margin; also takes one bare (margin, deviation) pair."""
+    if margins and not isinstance(margins[0], tuple):
+        margins = [('',) + tuple(margins)]
+    for name, lo, dev in margins:
+        assert lo >= factor * dev, (name, lo, dev)
+
+
+# ---- the stored reference results ---------------------------------------------------------------------------------------------------
+def load_golden():
+    """tests/golden/heads_train.npz -> (meta, outs [5 fp32 NCHW], params {name: fp32}, ups {name: fp32}, want {name: fp64})."""
+    meta, z = helpers.load_golden('heads_train')
+    outs = [torch.from_numpy(z['out%d' % i].astype(np.float32)) for i in range(len(meta['pyramid']))]
+    params = {n: torch.from_numpy((ints_of(z['p_' + n]).astype(np.float32) / PARAM_GRID).reshape(meta['param_shapes'][n])) for n in meta['params']}
+    ups = {k: unpack5(z['up_' + k], meta['shapes'][k]) for k in OUT_NAMES}
+    want = {k: unpack(z['q_' + k], meta['steps'][k], meta['shapes'][k]) for k in meta['steps']}
+    want['priors'] = torch.from_numpy(z['priors'])
+    return meta, outs, params, ups, want
+
+
+def golden_spec():
+    """The golden config as the oracle reads it, from yolact_amd's own config table."""
+    import yolact_amd
+    cfg = yolact_amd.CONFIGS['yolact_resnet50_config'].copy()
+    o = golden_cfg_overrides()
+    cfg.fpn = cfg.fpn.copy({'num_features': o.pop('num_features')})
+    cfg.update(o)
+    return spec_of(cfg), cfg

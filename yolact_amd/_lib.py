@@ -171,6 +171,14 @@ class MaskIouHeadDesc(C.Structure):
                 ('_pad0', C.c_int32)]
 
 
+class ConvWgradDesc(C.Structure):
+    """include/yolact_amd.h ymi_conv_wgrad_desc."""
+    _fields_ = [('x', C.c_void_p), ('g', C.c_void_p), ('dw', C.c_void_p), ('db', C.c_void_p), ('ws', C.c_void_p),
+                ('ws_bytes', C.c_int64),
+                ('B', C.c_int32), ('H', C.c_int32), ('W', C.c_int32), ('Cin', C.c_int32), ('Cout', C.c_int32), ('ldg', C.c_int32),
+                ('kh', C.c_int32), ('kw', C.c_int32), ('pad', C.c_int32), ('_pad0', C.c_int32)]
+
+
 class DetectDesc(C.Structure):
     _fields_ = [('conf', C.c_void_p), ('loc', C.c_void_p), ('coef', C.c_void_p), ('priors', C.c_void_p),
                 ('B', C.c_int32), ('P', C.c_int32), ('C', C.c_int32), ('D', C.c_int32),
@@ -261,7 +269,8 @@ class RleShape(C.Structure):
 # ymi_workspace_bytes selectors (include/yolact_amd.h YMI_WS_*)
 (WS_WINO_V, WS_WINO_M, WS_SPLITK, WS_MASK_IOU, WS_JPEG_COEFS, WS_JPEG_PLANES, WS_DETECT_SCORES_T, WS_DETECT_PER_PRIOR,
  WS_DETECT_CAND, WS_DETECT_REC, WS_AMAX_SLOT, WS_RLE_COUNTS, WS_DETECT_GREEDY, WS_JPEG_ENC, WS_JPEG_ENC_OUT,
- WS_MASK_LOSS, WS_MATCH, WS_BOX_LOSS, WS_CLASS_LOSS, WS_SEGM_LOSS, WS_MASKIOU_INPUT, WS_CONV_BWD, WS_MASKIOU_HEAD) = range(1, 24)
+ WS_MASK_LOSS, WS_MATCH, WS_BOX_LOSS, WS_CLASS_LOSS, WS_SEGM_LOSS, WS_MASKIOU_INPUT, WS_CONV_BWD, WS_MASKIOU_HEAD,
+ WS_CONV_WGRAD) = range(1, 25)
 
 EFORMAT, EUNSUPPORTED = -4, -5
 
@@ -302,6 +311,9 @@ SYMBOLS = [
     ('ymi_conv2d_bwd_nhwc_f32', C.c_int, [C.POINTER(ConvBwdDesc), _P]),
     ('ymi_global_maxpool_bwd_nhwc_f32', C.c_int, [_P, _P, _P, _I, _I, _I, _P]),
     ('ymi_maskiou_head_f32', C.c_int, [C.POINTER(MaskIouHeadDesc), _P]),
+    ('ymi_act_bwd_f32', C.c_int, [_P, _P, _P, C.c_long] + [_I] * 6 + [_P]),
+    ('ymi_conv_wgrad_nhwc_f32', C.c_int, [C.POINTER(ConvWgradDesc), _P]),
+    ('ymi_bilinear_bwd_nhwc_f32', C.c_int, [_P, _P, _P] + [_I] * 7 + [_P]),
     ('ymi_composite_masks_u8', C.c_int, [_P, _P, _P, _I, _I, _I, _F, _P, _P]),
     ('ymi_mask_iou_f32', C.c_int, [_P, _P, _I, _I, C.c_long, _I, _P, _P, _P]),
     ('ymi_jaccard_f32', C.c_int, [_P, _P, _I, _I, _I, _P, _P]),

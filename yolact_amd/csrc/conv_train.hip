@@ -1,0 +1,325 @@
+// The backward of the train-mode heads and protonet (yolact.py:133-212, 580-647; utils/functions.py:163-213): stride-1 convolutions
+// (3x3 / pad 1, 1x1 / pad 0), ReLU, tanh and the x2 bilinear upsample, NHWC fp32, without floating-point atomics (the same inputs
+// give the same bits).  The data gradient of a convolution is a convolution again and runs on ymi_conv2d_nhwc_f32; what is new here:
+//
+//   ymi_act_bwd_f32             g[pos,c] = dy[pos,c] * act'(y[pos,c]) from the layer's OUTPUT y (ReLU: y > 0, tanh: 1 - y^2), written
+//                               with the channel stride the consumers want; the padding channels get exact zeros.
+//   ymi_conv_wgrad_nhwc_f32     dw[k,co] = sum_pos im2col(x)[pos,k] g[pos,co], db[co] = sum_pos g[pos,co] on the exact-fp32 matrix
+//                               instruction (v_mfma_f32_32x32x2_f32: fp32 in, fp32 accumulate).  The POSITIONS are the instruction's k
+//                               index, so both operands are read in their natural NHWC layout: lane = channel, the two halves of a
+//                               wave = two consecutive positions.  A block owns one (tap, 32 input channels), a chunk of positions and
+//                               NT * 128 output channels (each wave NT column tiles of 32); the tap only shifts the address of x, a
+//                               shifted pixel outside the image contributes 0.  Every instruction needs one 4-byte load per lane
+//                               and operand, so the loads of 32 positions are issued as a group, one group ahead of the MFMAs that use
+//                               them (two waves per SIMD for NT <= 2, one for NT = 4: 198 / 250 / 357 registers, no spills).  db
+//                               falls out of the g fragments of the blocks of (tap 0, chunk 0 of the channels).  The chunk partial
+//                               sums go to the workspace, a second launch adds them in chunk order.
+//   ymi_bilinear_bwd_nhwc_f32   the backward of ymi_bilinear_nhwc_f32 for Ho = 2 Hi, Wo = 2 Wi as a gather: an input pixel (iy, ix)
+//                               walks the output rows 2 iy - 2 .. 2 iy + 2 and columns 2 ix - 2 .. 2 ix + 2 in order, asks
+//                               upsample_math.h which of them read it and with what weight, and sums.
+#include "loss_common.h"
+#include "upsample_math.h"
+#include "../../include/yolact_amd.h"
+
+namespace {
+
+// ---- activation backward ------------------------------------------------------------------------------------------------------------
+struct AbParams {
+  const float *y, *dy;
+  float *g;
+  long total;
+  int C, cpad, ldy, lddy, ldg, act;
+};
+
+// thread = (position, channel of [0, cpad))
+__global__ __launch_bounds__(256) void act_bwd_k(const AbParams p) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= p.total) return;
+  const long pos = i / p.cpad;
+  const int c = (int)(i - pos * p.cpad);
+  float v = 0.f;
+  if (c < p.C) {
+    v = p.dy[(size_t)pos * p.lddy + c];
+    if (p.act == YMI_ACT_RELU) {
+      v = p.y[(size_t)pos * p.ldy + c] > 0.f ? v : 0.f;
+    } else if (p.act == YMI_ACT_TANH) {
+      const float yv = p.y[(size_t)pos * p.ldy + c];
+      v = v * (1.f - yv * yv);
+    }
+  }
+  p.g[(size_t)pos * p.ldg + c] = v;
+}
+
+// ---- weight gradient ----------------------------------------------------------------------------------------------------------------
+struct WgParams {
+  const float *x, *g;
+  float *dw, *db, *ws_w, *ws_b;
+  int H, W, Cin, Cout, ldg, kw, pad, ncc, K, nchunks, want_w, want_b;
+  long P, per;
+};
+
+// row of a 32 x 32 accumulator held in register r by this lane (column = lane & 31)
+__device__ __forceinline__ int acc_row(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
+
+// NT: 32-column output-channel tiles per wave (a block covers NT * 128 output channels, gridDim.z such groups)
+template <int NT> __global__ __launch_bounds__(256, NT == 4 ? 1 : 2) void wgrad_k(const WgParams p) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int ln = lane & 31, kk = lane >> 5;
+  const int tap = (int)blockIdx.x / p.ncc, c0 = ((int)blockIdx.x % p.ncc) * 32;
+  const int ky = tap / p.kw, kx = tap - ky * p.kw;
+  const int sy = ky - p.pad, sx = kx - p.pad;          // the tap's shift of the input pixel
+  const int ob = blockIdx.z * (NT * 128);
+  const long pos0 = (long)blockIdx.y * p.per;
+  const long pos1 = pos0 + p.per < p.P ? pos0 + p.per : p.P;
+  const bool do_w = p.want_w != 0;
+  const bool do_bias = p.want_b != 0 && blockIdx.x == 0;
+
+  // the wave's column tiles that hold a real output channel are a prefix of its NT tiles
+  int nact = 0;
+#pragma unroll
+  for (int j = 0; j < NT; ++j) nact += (ob + (wave + 4 * j) * 32 < p.Cout) ? 1 : 0;
+  if (nact == 0) return;                               // (no barrier below)
+
+  f32x16 acc[NT];
+  float bs[NT];
+  unsigned gc[NT];                                     // byte offset in g of this lane's channel of tile j (channel 0 where the tile has none)
+  bool col[NT];
+#pragma unroll
+  for (int j = 0; j < NT; ++j) {
+    bs[j] = 0.f;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
+    const int o = ob + (wave + 4 * j) * 32 + ln;
+    col[j] = o < p.Cout;
+    gc[j] = 4u * (unsigned)(col[j] ? o : 0);
+  }
+
+  // this lane's positions: pos0 + kk, + 2, + 4, ..; their pixel coordinates are carried along
+  long pos = pos0 + kk;
+  int ox = (int)(pos % p.W), oy = (int)((pos / p.W) % p.H);
+  // byte offsets fit 32 bits (validate_wgrad): a uniform base plus one register per load
+  const int xlane = 4 * (c0 + ln), shift = 4 * ((sy * p.W + sx) * p.Cin);
+  const char *xb = reinterpret_cast<const char *>(p.x), *gb = reinterpret_cast<const char *>(p.g);
+  const unsigned xstep = 4u * (unsigned)p.Cin, gstep = 4u * (unsigned)p.ldg;
+
+  // One group = 32 positions = 16 instructions.  All loads of a group are issued before its first MFMA, and the next group's are
+  // issued before this group's MFMAs, so that the memory latency hides under the matrix pipe.  The loads are unconditional: a
+  // position past the chunk or a shifted pixel outside the image reads element 0 instead and is zeroed by its mask bit afterwards.
+  struct Grp { float a[16]; float b[NT][16]; unsigned am, lm; };
+  auto issue = [&](Grp &G) {
+    G.am = 0u; G.lm = 0u;
+#pragma unroll
+    for (int s = 0; s < 16; ++s) {
+      const bool live = pos < pos1;
+      const bool inside = live && (unsigned)(oy + sy) < (unsigned)p.H && (unsigned)(ox + sx) < (unsigned)p.W;
+      G.lm |= (live ? 1u : 0u) << s;
+      G.am |= (inside ? 1u : 0u) << s;
+      const unsigned xo = (inside ? (unsigned)((int)((unsigned)pos * xstep) + shift) : 0u) + (unsigned)xlane;
+      G.a[s] = do_w ? *reinterpret_cast<const float *>(xb + xo) : 0.f;
+      const unsigned gi = live ? (unsigned)pos * gstep : 0u;
+#pragma unroll
+      for (int j = 0; j < NT; ++j) G.b[j][s] = j < nact ? *reinterpret_cast<const float *>(gb + (gi + gc[j])) : 0.f;
+      pos += 2; ox += 2;
+      if (ox >= p.W) { ox -= p.W; ++oy; }               // twice: W may be 1
+      if (ox >= p.W) { ox -= p.W; ++oy; }
+      if (oy >= p.H) oy -= p.H;
+      if (oy >= p.H) oy -= p.H;
+    }
+  };
+  auto consume = [&](const Grp &G) {
+#pragma unroll
+    for (int s = 0; s < 16; ++s) {
+      const float a = (G.am >> s & 1u) ? G.a[s] : 0.f;
+#pragma unroll
+      for (int j = 0; j < NT; ++j) {
+        if (j < nact) {
+          const float b = ((G.lm >> s & 1u) && col[j]) ? G.b[j][s] : 0.f;
+          bs[j] += b;
+          if (do_w) acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc[j], 0, 0, 0);
+        }
+      }
+    }
+  };
+  Grp G0, G1;
+  issue(G0);
+  for (long m0 = pos0; m0 < pos1; m0 += 64) {
+    issue(G1);                                         // (past the chunk: every mask bit is 0)
+    consume(G0);
+    issue(G0);
+    consume(G1);
+  }
+
+  if (do_w) {
+    float *dst = p.ws_w + (size_t)blockIdx.y * p.K * p.Cout + ((size_t)tap * p.Cin + c0) * p.Cout;
+#pragma unroll
+    for (int j = 0; j < NT; ++j) {
+      const int o = ob + (wave + 4 * j) * 32 + ln;
+      if (j < nact && o < p.Cout) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) dst[(size_t)acc_row(r, kk) * p.Cout + o] = acc[j][r];
+      }
+    }
+  }
+  if (do_bias) {
+#pragma unroll
+    for (int j = 0; j < NT; ++j) {
+      const float v = bs[j] + __shfl_xor(bs[j], 32);   // even positions + odd positions
+      const int o = ob + (wave + 4 * j) * 32 + ln;
+      if (j < nact && kk == 0 && o < p.Cout) p.ws_b[(size_t)blockIdx.y * p.Cout + o] = v;
+    }
+  }
+#endif
+}
+
+// thread = one element of dw [K, Cout], then of db [Cout]: the chunk partials in chunk order
+__global__ __launch_bounds__(256) void wgrad_sum_k(const WgParams p) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x, nw = (long)p.K * p.Cout;
+  if (i < nw) {
+    if (!p.want_w) return;
+    float s = 0.f;
+    for (int c = 0; c < p.nchunks; ++c) s += p.ws_w[(size_t)c * nw + i];
+    p.dw[i] = s;
+  } else if (i < nw + p.Cout) {
+    if (!p.want_b) return;
+    const int o = (int)(i - nw);
+    float s = 0.f;
+    for (int c = 0; c < p.nchunks; ++c) s += p.ws_b[(size_t)c * p.Cout + o];
+    p.db[o] = s;
+  }
+}
+
+int validate_wgrad(const ymi_conv_wgrad_desc *d) {
+  if (!d) return YMI_ENULL;
+  if (d->B < 1 || d->H < 1 || d->W < 1 || d->Cin < 1 || d->Cout < 1) return YMI_EARG;
+  if (!((d->kh == 3 && d->kw == 3 && d->pad == 1) || (d->kh == 1 && d->kw == 1 && d->pad == 0))) return YMI_EARG;
+  if (d->Cin % 32 != 0 || d->ldg < d->Cout) return YMI_ESHAPE;
+  const long P = (long)d->B * d->H * d->W;
+  if (P * d->Cin >= (1L << 29) || P * d->ldg >= (1L << 29) || (long)d->kh * d->kw * d->Cin * d->Cout >= (1L << 31)) return YMI_ESHAPE;
+  return YMI_OK;
+}
+
+struct WgPlan { int nt, gx, gz, nchunks; long per; };
+
+// the decomposition for a validated shape: about 1024 blocks, chunks of a multiple of 32 positions
+WgPlan wgrad_plan(const ymi_conv_wgrad_desc *d) {
+  WgPlan w;
+  const long P = (long)d->B * d->H * d->W;
+  const int tiles = (d->Cout + 31) / 32;
+  w.nt = tiles <= 4 ? 1 : (tiles <= 8 ? 2 : 4);
+  w.gz = (d->Cout + w.nt * 128 - 1) / (w.nt * 128);
+  w.gx = d->kh * d->kw * (d->Cin / 32);
+  const long mb = (P + 31) / 32;
+  long sp = (1024 + (long)w.gx * w.gz - 1) / ((long)w.gx * w.gz);
+  sp = sp < 1 ? 1 : (sp > mb ? mb : sp);
+  w.per = (mb + sp - 1) / sp * 32;
+  w.nchunks = (int)((P + w.per - 1) / w.per);
+  return w;
+}
+
+// ---- x2 bilinear upsample backward ----------------------------------------------------------------------------------------------------
+struct UbParams {
+  const float *dy, *y;
+  float *dx;
+  int Hi, Wi, C4, Ho, Wo, relu;
+  long total;
+};
+
+// the weight with which output index o reads input index i along one axis (0 when it does not)
+__device__ __forceinline__ float up_weight(int o, int i, int in_size) {
+  int i0, i1; float l1;
+  up_coord(o, 0.5f, in_size, i0, i1, l1);
+  return (i0 == i ? 1.f - l1 : 0.f) + (i1 == i ? l1 : 0.f);
+}
+
+// thread = (input pixel, 4 channels)
+__global__ __launch_bounds__(256) void bilinear_bwd_k(const UbParams p) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= p.total) return;
+  const int c4 = (int)(i % p.C4);
+  long r = i / p.C4;
+  const int ix = (int)(r % p.Wi); r /= p.Wi;
+  const int iy = (int)(r % p.Hi);
+  const long b = r / p.Hi;
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+  for (int oy = 2 * iy - 2; oy <= 2 * iy + 2; ++oy) {
+    if (oy < 0 || oy >= p.Ho) continue;
+    const float wy = up_weight(oy, iy, p.Hi);
+    if (wy == 0.f) continue;
+    for (int ox = 2 * ix - 2; ox <= 2 * ix + 2; ++ox) {
+      if (ox < 0 || ox >= p.Wo) continue;
+      const float wx = up_weight(ox, ix, p.Wi);
+      if (wx == 0.f) continue;
+      const size_t o = (((size_t)b * p.Ho + oy) * p.Wo + ox) * p.C4 * 4 + (size_t)c4 * 4;
+      f32x4 d = *reinterpret_cast<const f32x4 *>(p.dy + o);
+      if (p.relu) {
+        const f32x4 yv = *reinterpret_cast<const f32x4 *>(p.y + o);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) d[e] = yv[e] > 0.f ? d[e] : 0.f;
+      }
+      const float w = wy * wx;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) acc[e] += w * d[e];
+    }
+  }
+  *reinterpret_cast<f32x4 *>(p.dx + (size_t)i * 4) = acc;
+}
+
+}  // namespace
+
+extern "C" int ymi_act_bwd_f32(const float *y, const float *dy, float *g, long npos, int C, int cpad, int ldy, int lddy, int ldg, int act,
+                               void *stream) {
+  if (!dy || !g) return YMI_ENULL;
+  if (act != YMI_ACT_NONE && act != YMI_ACT_RELU && act != YMI_ACT_TANH) return YMI_EARG;
+  if (act != YMI_ACT_NONE && !y) return YMI_ENULL;
+  if (npos < 1 || C < 1) return YMI_EARG;
+  if (cpad < C || ldg < cpad || lddy < C || (act != YMI_ACT_NONE && ldy < C)) return YMI_ESHAPE;
+  if (npos * (long)ldg >= (1L << 40) || npos * (long)cpad >= (1L << 39)) return YMI_ESHAPE;
+  AbParams p;
+  p.y = y; p.dy = dy; p.g = g; p.total = npos * cpad; p.C = C; p.cpad = cpad; p.ldy = ldy; p.lddy = lddy; p.ldg = ldg; p.act = act;
+  return ymi_launch(act_bwd_k, dim3((unsigned)((p.total + 255) / 256)), dim3(256), 0, stream, p);
+}
+
+// Workspace of ymi_conv_wgrad_nhwc_f32: [nchunks][kh*kw*Cin][Cout] floats, then [nchunks][Cout] floats
+extern "C" int64_t ymi_conv_wgrad_ws_bytes(const ymi_conv_wgrad_desc *d) {
+  const int rc = validate_wgrad(d);
+  if (rc) return rc;
+  const WgPlan w = wgrad_plan(d);
+  if (w.gz > 65535) return YMI_ESHAPE;
+  const int64_t K = (int64_t)d->kh * d->kw * d->Cin;
+  return ymi_ws_part((int64_t)w.nchunks * K * d->Cout) + ymi_ws_part((int64_t)w.nchunks * d->Cout);
+}
+
+extern "C" int ymi_conv_wgrad_nhwc_f32(const ymi_conv_wgrad_desc *d, void *stream) {
+  const int rc = validate_wgrad(d);
+  if (rc) return rc;
+  if (!d->g || (!d->dw && !d->db) || (d->dw && !d->x) || !d->ws) return YMI_ENULL;
+  if ((uintptr_t)d->ws & 15) return YMI_ESHAPE;
+  const WgPlan w = wgrad_plan(d);
+  if (w.gz > 65535 || d->ws_bytes < ymi_conv_wgrad_ws_bytes(d)) return YMI_ESHAPE;
+  WgParams p;
+  p.x = d->x; p.g = d->g; p.dw = d->dw; p.db = d->db;
+  p.H = d->H; p.W = d->W; p.Cin = d->Cin; p.Cout = d->Cout; p.ldg = d->ldg; p.kw = d->kw; p.pad = d->pad;
+  p.ncc = d->Cin / 32; p.K = d->kh * d->kw * d->Cin; p.nchunks = w.nchunks; p.want_w = d->dw != nullptr; p.want_b = d->db != nullptr;
+  p.P = (long)d->B * d->H * d->W; p.per = w.per;
+  p.ws_w = static_cast<float *>(d->ws);
+  p.ws_b = reinterpret_cast<float *>(static_cast<char *>(d->ws) + ymi_ws_part((int64_t)w.nchunks * p.K * d->Cout));
+  const dim3 grid(d->dw ? w.gx : 1, w.nchunks, w.gz);     // bias alone: the blocks of tap 0, channels 0 .. 31
+  int rl = w.nt == 1 ? ymi_launch(wgrad_k<1>, grid, dim3(256), 0, stream, p)
+                     : (w.nt == 2 ? ymi_launch(wgrad_k<2>, grid, dim3(256), 0, stream, p) : ymi_launch(wgrad_k<4>, grid, dim3(256), 0, stream, p));
+  if (!rl) rl = ymi_launch(wgrad_sum_k, dim3((unsigned)(((long)p.K * d->Cout + d->Cout + 255) / 256)), dim3(256), 0, stream, p);
+  return rl;
+}
+
+extern "C" int ymi_bilinear_bwd_nhwc_f32(const float *dy, const float *y, float *dx, int B, int Hi, int Wi, int C, int Ho, int Wo, int relu,
+                                         void *stream) {
+  if (!dy || !dx || (relu && !y)) return YMI_ENULL;
+  if (B < 1 || Hi < 1 || Wi < 1 || C < 1 || (relu != 0 && relu != 1)) return YMI_EARG;
+  if (Ho != 2 * Hi || Wo != 2 * Wi || C % 4 != 0) return YMI_ESHAPE;
+  if ((long)B * Ho * Wo * C >= (1L << 40)) return YMI_ESHAPE;
+  if (((uintptr_t)dy | (uintptr_t)y | (uintptr_t)dx) & 15) return YMI_ESHAPE;
+  UbParams p;
+  p.dy = dy; p.y = y; p.dx = dx; p.Hi = Hi; p.Wi = Wi; p.C4 = C / 4; p.Ho = Ho; p.Wo = Wo; p.relu = relu;
+  p.total = (long)B * Hi * Wi * (C / 4);
+  return ymi_launch(bilinear_bwd_k, dim3((unsigned)((p.total + 255) / 256)), dim3(256), 0, stream, p);
+}

@@ -1,0 +1,271 @@
+"""Differentiable building blocks of the train-mode heads and protonet on the HIP kernels (csrc/conv_train.hip and the conv engine).
+
+    conv2d_act(x, weight, bias, padding, act)            -> y [B,H,W,Cout]: act(conv(x, weight) + bias), act in {None, 'relu', 'tanh'}
+    conv2d_multi(x, [(weight, bias, act), ..], padding)  -> one y per entry: up to three convolutions of the SAME input as one launch
+                                                            (the head's bbox / conf / mask layers, yolact.py:169-173)
+    upsample2x(x, relu)                                  -> [B,2H,2W,C]: F.interpolate(scale_factor=2, bilinear, align_corners=False)
+
+x and the results are NHWC fp32 GPU tensors; weight and bias are nn.Conv2d parameters in torch layout.  Everything is once
+differentiable in x, every weight and every bias.  Each call packs its filters from the CURRENT parameter values (a permute; no
+cache), launches only what needs_input_grad asks for, and saves its inputs, so autograd's version check refuses a backward after an
+in-place edit.  Geometry: 3x3 / stride 1 / pad 1 and 1x1 / pad 0, Cin % 32 == 0, any Cout; anything else raises NotImplementedError
+naming it.  CPU tensors raise: there is no CPU path.
+
+Launches of one convolution's backward: ymi_act_bwd_f32 per output (g = dy * act'(y), side by side in one buffer whose channel stride
+is padded to a multiple of 32, padding zeroed), ymi_conv_wgrad_nhwc_f32 once over all outputs (dw, db), ymi_conv2d_nhwc_f32 once on g
+with the filters flipped in both taps and transposed in (Cin, Cout) (dx).
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import torch
+import torch.nn.functional as F
+from torch.autograd.function import once_differentiable
+
+from .. import _lib as L
+from . import _loss_common as LC
+
+ACTS = {None: L.ACT_NONE, 'none': L.ACT_NONE, 'relu': L.ACT_RELU, 'tanh': L.ACT_TANH}
+
+
+def _ceil(a, b):
+    return (a + b - 1) // b * b
+
+
+def check_conv(weight, padding, stride=1, dilation=1, groups=1, who='conv2d_act'):
+    """NotImplementedError naming what of a convolution's geometry the kernels do not take -> (kh, pad)."""
+    pair = lambda v: (int(v), int(v)) if isinstance(v, int) else tuple(int(e) for e in v)
+    if isinstance(padding, str):
+        raise NotImplementedError('yolact_amd %s: padding = %r is not supported (an integer padding is)' % (who, padding))
+    stride, dilation, padding = pair(stride), pair(dilation), pair(padding)
+    Cout, Cin, kh, kw = weight.shape
+    if stride != (1, 1):
+        raise NotImplementedError('yolact_amd %s: stride = %r is not supported (stride 1 is)' % (who, stride))
+    if dilation != (1, 1):
+        raise NotImplementedError('yolact_amd %s: dilation = %r is not supported (dilation 1 is)' % (who, dilation))
+    if groups != 1:
+        raise NotImplementedError('yolact_amd %s: groups = %r is not supported (groups 1 is)' % (who, groups))
+    if (kh, kw, padding) not in (((3, 3, (1, 1))), (1, 1, (0, 0))):
+        raise NotImplementedError('yolact_amd %s: a %d x %d kernel with padding = %r is not supported (3 x 3 / padding 1 and '
+                                  '1 x 1 / padding 0 are)' % (who, kh, kw, padding))
+    if Cin % 32 != 0:
+        raise NotImplementedError('yolact_amd %s: Cin = %d is not supported (a multiple of 32 input channels is)' % (who, Cin))
+    return kh, padding[0]
+
+
+def _engine_conv(x, ldx, wpk, bias, Cin, Cout, k, pad, segs):
+    """One ymi_conv2d_nhwc_f32 launch on the exact-fp32 tiles: x [B,H,W,ldx], wpk [CoutPad][k*k*Cin], segs = (n0, n1, act, tensor)."""
+    B, H, W = x.shape[:3]
+    d = L.ConvDesc()
+    d.x, d.w, d.bias = x.data_ptr(), wpk.data_ptr(), (None if bias is None else bias.data_ptr())
+    d.B, d.H, d.W, d.Cin, d.ldx, d.Ho, d.Wo, d.Cout = B, H, W, Cin, ldx, H, W, Cout
+    d.kh, d.kw, d.stride, d.pad, d.Kpad, d.tile = k, k, 1, pad, k * k * Cin, L.TILE_AUTO
+    d.nseg = len(segs)
+    for i, (n0, n1, act, y) in enumerate(segs):
+        d.seg[i] = L.ConvSeg(n0, n1, act, n1 - n0, H * W * (n1 - n0), y.data_ptr())
+    L.check(L.lib().ymi_conv2d_nhwc_f32(C.byref(d), L.stream_ptr()), 'ymi_conv2d_nhwc_f32')
+
+
+def _pack_forward(wcat):
+    """[Cout,Cin,kh,kw] -> [ceil128(Cout)][kh*kw*Cin], k = (ky*kw + kx)*Cin + c (a permute of the CURRENT values)."""
+    Cout, Cin, kh, kw = wcat.shape
+    out = torch.zeros(_ceil(Cout, 128), kh * kw * Cin, dtype=torch.float32, device=wcat.device)
+    out[:Cout] = wcat.permute(0, 2, 3, 1).reshape(Cout, kh * kw * Cin)
+    return out
+
+
+def _pack_dgrad(wcat, ldg):
+    """The filters of the data gradient: flipped in both taps, transposed in (Cin, Cout), Cout padded to ldg with zeros ->
+    [ceil128(Cin)][kh*kw*ldg]."""
+    Cout, Cin, kh, kw = wcat.shape
+    t = F.pad(wcat.flip(2, 3).permute(1, 2, 3, 0), (0, ldg - Cout))          # [Cin,kh,kw,ldg]
+    out = torch.zeros(_ceil(Cin, 128), kh * kw * ldg, dtype=torch.float32, device=wcat.device)
+    out[:Cin] = t.reshape(Cin, kh * kw * ldg)
+    return out
+
+
+class ConvMulti(torch.autograd.Function):
+    """apply(k, pad, acts, x, w1, b1, .., wn, bn) -> (y1, .., yn)."""
+
+    @staticmethod
+    def forward(ctx, k, pad, acts, x, *params):
+        dev = x.device
+        ws, bs = params[0::2], params[1::2]
+        couts = [int(w.shape[0]) for w in ws]
+        Cin = int(ws[0].shape[1])
+        with torch.cuda.device(dev), torch.no_grad():
+            xd = LC.f32(x, dev)
+            B, H, W, _ = xd.shape
+            wcat = torch.cat([w.detach().float() for w in ws], 0) if len(ws) > 1 else ws[0].detach().float()
+            bcat = torch.cat([b.detach().float() for b in bs], 0).contiguous()
+            ys, segs, n0 = [], [], 0
+            for co, a in zip(couts, acts):
+                y = torch.empty(B, H, W, co, dtype=torch.float32, device=dev)
+                ys.append(y)
+                segs.append((n0, n0 + co, a, y))
+                n0 += co
+            _engine_conv(xd, Cin, _pack_forward(wcat), bcat, Cin, n0, k, pad, segs)
+        # the outputs are this call's own tensors; the inputs are saved too, so that autograd's version check refuses a backward
+        # after x or a parameter was edited in place
+        ctx.save_for_backward(x, *params, *ys)
+        ctx.k, ctx.pad, ctx.acts, ctx.couts = k, pad, acts, couts
+        ctx.dtypes = [x.dtype] + [p.dtype for p in params]
+        return tuple(ys)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *dys):
+        need = ctx.needs_input_grad[3:]
+        saved = ctx.saved_tensors                         # (the version check)
+        n = len(ctx.couts)
+        x, params, ys = saved[0], saved[1:1 + 2 * n], saved[1 + 2 * n:]
+        want_x, want_p = need[0], need[1:]
+        if not any(need):
+            return (None,) * (3 + len(need))
+        dev = x.device
+        lib, s = L.lib(), L.stream_ptr()
+        k, pad, couts = ctx.k, ctx.pad, ctx.couts
+        with torch.cuda.device(dev), torch.no_grad():
+            xd = LC.f32(x, dev)
+            B, H, W, Cin = xd.shape
+            npos, ctot = B * H * W, sum(couts)
+            ldg = _ceil(ctot, 32)
+            g = torch.empty(B, H, W, ldg, dtype=torch.float32, device=dev)
+            n0, keep = 0, []
+            for i, (co, a, y, dy) in enumerate(zip(couts, ctx.acts, ys, dys)):
+                dyd = torch.zeros_like(y) if dy is None else LC.f32(dy, dev)
+                keep.append(dyd)
+                cpad = co + (ldg - ctot if i == len(couts) - 1 else 0)
+                L.check(lib.ymi_act_bwd_f32(y.data_ptr(), dyd.data_ptr(), g.data_ptr() + 4 * n0, npos, co, cpad, co, co, ldg, a, s),
+                        'ymi_act_bwd_f32')
+                n0 += co
+            grads = [None] * len(params)
+            want_w, want_b = any(want_p[0::2]), any(want_p[1::2])
+            if want_w or want_b:
+                d = L.ConvWgradDesc()
+                dw = torch.empty(k * k * Cin, ctot, dtype=torch.float32, device=dev) if want_w else None
+                db = torch.empty(ctot, dtype=torch.float32, device=dev) if want_b else None
+                d.x, d.g = xd.data_ptr(), g.data_ptr()
+                d.dw, d.db = (None if t is None else t.data_ptr() for t in (dw, db))
+                d.B, d.H, d.W, d.Cin, d.Cout, d.ldg, d.kh, d.kw, d.pad = B, H, W, Cin, ctot, ldg, k, k, pad
+                ws = LC.workspace('CONV_WGRAD', d, dev)
+                d.ws_bytes = ws.numel()
+                L.check(lib.ymi_conv_wgrad_nhwc_f32(C.byref(d), s), 'ymi_conv_wgrad_nhwc_f32')
+                n0 = 0
+                for i, co in enumerate(couts):
+                    if want_p[2 * i]:
+                        grads[2 * i] = dw[:, n0:n0 + co].reshape(k, k, Cin, co).permute(3, 2, 0, 1).contiguous()
+                    if want_p[2 * i + 1]:
+                        grads[2 * i + 1] = db[n0:n0 + co].clone()
+                    n0 += co
+            dx = None
+            if want_x:
+                wcat = torch.cat([w.detach().float() for w in params[0::2]], 0)
+                dx = torch.empty(B, H, W, Cin, dtype=torch.float32, device=dev)
+                _engine_conv(g, ldg, _pack_dgrad(wcat, ldg), None, ldg, Cin, k, k - 1 - pad, [(0, Cin, L.ACT_NONE, dx)])
+        out = [dx] + grads
+        return (None, None, None) + tuple(None if t is None else t.to(dt) for t, dt in zip(out, ctx.dtypes))
+
+
+def conv2d_multi(x, layers, padding, stride=1, dilation=1, groups=1):
+    """layers = [(weight, bias, act), ..] (one to three convolutions of equal geometry on the same x) -> tuple of NHWC outputs."""
+    L.require_cuda(x, 'conv2d_act x')
+    if not 1 <= len(layers) <= 3:
+        raise ValueError('conv2d_multi: one to three convolutions share a launch, got %d' % len(layers))
+    if x.dim() != 4:
+        raise ValueError('conv2d_act: x must be [B,H,W,Cin], got %s' % (tuple(x.shape),))
+    params, acts, geo = [], [], None
+    for w, b, act in layers:
+        L.require_cuda(w, 'conv2d_act weight')
+        if act not in ACTS:
+            raise NotImplementedError('yolact_amd conv2d_act: act = %r is not supported (None, \'relu\' and \'tanh\' are)' % (act,))
+        if b is None:
+            raise NotImplementedError('yolact_amd conv2d_act: bias = None is not supported (a biased convolution is)')
+        g = check_conv(w, padding, stride, dilation, groups) + (int(w.shape[1]),)
+        if geo is not None and g != geo:
+            raise ValueError('conv2d_multi: the convolutions differ in geometry: %r and %r' % (geo, g))
+        geo = g
+        if b.numel() != w.shape[0]:
+            raise ValueError('conv2d_act: weight %s / bias %s' % (tuple(w.shape), tuple(b.shape)))
+        params += [w, b]
+        acts.append(ACTS[act])
+    if x.shape[3] != geo[2]:
+        raise ValueError('conv2d_act: x %s has %d channels, the weight takes %d' % (tuple(x.shape), x.shape[3], geo[2]))
+    return ConvMulti.apply(geo[0], geo[1], tuple(acts), x, *params)
+
+
+def conv2d_act(x, weight, bias, padding, act=None, stride=1, dilation=1, groups=1):
+    """act(conv2d(x, weight, bias, padding)) on NHWC x -> NHWC."""
+    return conv2d_multi(x, [(weight, bias, act)], padding, stride, dilation, groups)[0]
+
+
+class Upsample2x(torch.autograd.Function):
+    """apply(x [B,H,W,C], relu) -> [B,2H,2W,C]."""
+
+    @staticmethod
+    def forward(ctx, x, relu):
+        dev = x.device
+        with torch.cuda.device(dev), torch.no_grad():
+            xd = LC.f32(x, dev)
+            B, H, W, Cc = xd.shape
+            y = torch.empty(B, 2 * H, 2 * W, Cc, dtype=torch.float32, device=dev)
+            L.check(L.lib().ymi_bilinear_nhwc_f32(xd.data_ptr(), y.data_ptr(), B, H, W, Cc, 2 * H, 2 * W, 0.5, 0.5, int(relu),
+                                                  L.stream_ptr()), 'ymi_bilinear_nhwc_f32')
+        ctx.save_for_backward(*((x, y) if relu else (x,)))
+        ctx.relu, ctx.dtype = int(relu), x.dtype
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        x, y = (tuple(ctx.saved_tensors) + (None,))[:2]   # (the version check)
+        if not ctx.needs_input_grad[0]:
+            return None, None
+        dev = x.device
+        with torch.cuda.device(dev), torch.no_grad():
+            B, H, W, Cc = x.shape
+            dyd = LC.f32(dy, dev)
+            dx = torch.empty(B, H, W, Cc, dtype=torch.float32, device=dev)
+            L.check(L.lib().ymi_bilinear_bwd_nhwc_f32(dyd.data_ptr(), None if y is None else y.data_ptr(), dx.data_ptr(),
+                                                      B, H, W, Cc, 2 * H, 2 * W, ctx.relu, L.stream_ptr()),
+                    'ymi_bilinear_bwd_nhwc_f32')
+        return dx.to(ctx.dtype), None
+
+
+def upsample2x(x, relu=False):
+    """F.interpolate(x, scale_factor=2, mode='bilinear', align_corners=False) (+ ReLU) on NHWC x."""
+    L.require_cuda(x, 'upsample2x x')
+    if x.dim() != 4 or x.shape[3] % 4 != 0:
+        raise NotImplementedError('yolact_amd upsample2x: x %s is not supported ([B,H,W,C] with C %% 4 == 0 is)' % (tuple(x.shape),))
+    return Upsample2x.apply(x, bool(relu))
+
+
+class SharedParams(torch.autograd.Function):
+    """apply(n, *params) -> n aliases of every parameter, use-major (use 0's parameters, use 1's, ..).  The backward adds a
+    parameter's n gradients in use order: g0 + g1 + .. + g(n-1), whatever order autograd ran the uses in."""
+
+    @staticmethod
+    def forward(ctx, n, *params):
+        ctx.n, ctx.k = n, len(params)
+        return tuple(p.view_as(p) for _ in range(n) for p in params)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *gs):
+        out = []
+        for j in range(ctx.k):
+            tot = None
+            for u in range(ctx.n):
+                g = gs[u * ctx.k + j]
+                if g is not None:
+                    tot = g if tot is None else tot + g
+            out.append(tot)
+        return (None,) + tuple(out)
+
+
+def share_params(n, params):
+    """[params of use 0, params of use 1, ..]: n lists of aliases whose gradients are summed in use order."""
+    params = list(params)
+    flat = SharedParams.apply(n, *params)
+    return [list(flat[u * len(params):(u + 1) * len(params)]) for u in range(n)]

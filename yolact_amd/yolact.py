@@ -411,6 +411,107 @@ class Yolact(nn.Module):
         return parallel.assemble_sharded(rec, mine, lo, hi, self.mask_dim, self, bits=bits,
                                          mask_size=(hh, ww) if masks == 'bits' else None)
 
+    # ---- train-mode heads -------------------------------------------------------------------------------
+    @staticmethod
+    def _apply_net(seq, x, last_act=None, params=None):
+        """A make_net Sequential (utils/functions.py:163-213) on NHWC x through layers/train_ops: Conv2d (+ the ReLU behind it),
+        InterpolateModule (+ the ReLU behind it).  last_act: the activation applied after a final layer that has no ReLU of its own.
+        params: [w, b, w, b, ..] to use in place of the convolutions' own parameters (aliases of a shared head)."""
+        from .layers import train_ops as TO
+        mods = list(seq)
+        params = None if params is None else list(params)
+        for i, m in enumerate(mods):
+            if isinstance(m, nn.ReLU):
+                continue
+            relu = i + 1 < len(mods) and isinstance(mods[i + 1], nn.ReLU)
+            act = 'relu' if relu else (last_act if i == len(mods) - 1 else None)
+            if isinstance(m, nn.Conv2d):
+                w, b = (m.weight, m.bias) if params is None else (params.pop(0), params.pop(0))
+                x = TO.conv2d_act(x, w, b, m.padding, act, stride=m.stride, dilation=m.dilation, groups=m.groups)
+            elif isinstance(m, M.InterpolateModule):
+                if m.scale_factor != 2 or act not in (None, 'relu'):
+                    raise NotImplementedError('yolact_amd forward_heads: an interpolation by %r followed by %r is not supported '
+                                              '(x2 bilinear with or without ReLU is)' % (m.scale_factor, act))
+                x = TO.upsample2x(x, relu=act == 'relu')
+            else:
+                raise NotImplementedError('yolact_amd forward_heads: layer %r is not implemented' % (m,))
+        return x
+
+    def _train_priors(self, sizes, cfg, device):
+        """The priors of forward_heads: built on the host once per (level sizes, every cfg value they are made from, device) and
+        kept on the device, as the reference keeps them per map size (yolact.py:214-263); cfg is still read at every call."""
+        from .config import make_priors_host
+        bbc = cfg.backbone
+        nlev = len(sizes)
+        freeze = lambda v: tuple(freeze(e) for e in v) if isinstance(v, (list, tuple)) else v
+        key = (tuple(sizes), freeze(list(bbc.pred_scales[:nlev])), freeze(list(bbc.pred_aspect_ratios[:nlev])), cfg.max_size,
+               bool(bbc.use_pixel_scales), bool(bbc.preapply_sqrt), bool(bbc.use_square_anchors), str(device))
+        cache = self.__dict__.setdefault('_train_prior_cache', {})
+        pri = cache.get(key)
+        if pri is None:
+            data = []
+            for lvl, (h, w) in enumerate(sizes):
+                data += make_priors_host(h, w, bbc.pred_scales[lvl], bbc.pred_aspect_ratios[lvl], cfg.max_size, bbc)
+            if len(cache) >= 8:
+                cache.clear()
+            pri = cache[key] = torch.tensor(data, dtype=torch.float32).view(-1, 4).to(device)
+        return pri
+
+    def forward_heads(self, outs):
+        """The reference's TRAIN-mode pred_outs (yolact.py:579-647) from the FPN maps `outs` ([B,nf,h_i,w_i] NCHW fp32 on the GPU,
+        one per prediction level, as yolact.py:577 yields them): {'loc' [B,P,4], 'conf' [B,P,C] raw logits, 'mask' [B,P,mask_dim]
+        after the coefficient activation, 'priors' [P,4], 'proto' [B,2h_0,2w_0,mask_dim] after the prototype activation, and
+        'segm' [B,C-1,h_0,w_0] under cfg.use_semantic_segmentation_loss}: what MultiBoxLoss takes.  Once differentiable in `outs`
+        and in the parameters of proto_net, prediction_layers[0] and semantic_seg_conv (layers/train_ops.py on the HIP kernels;
+        the shared head's gradients are summed over the levels in level order).  Needs no plan and reads cfg at call time; the
+        model stays in eval mode (train() raises) and forward() is untouched."""
+        from .layers import train_ops as TO
+        from .config import act_name
+        cfg = self.cfg
+        outs = list(outs)
+        if len(outs) != len(self.selected_layers):
+            raise ValueError('forward_heads: %d FPN maps for %d prediction levels' % (len(outs), len(self.selected_layers)))
+        if not bool(getattr(cfg, 'eval_mask_branch', True)):
+            raise NotImplementedError('yolact_amd forward_heads: cfg.eval_mask_branch = False is not supported')
+        for o in outs:
+            L.require_cuda(o, 'forward_heads FPN map')
+            if o.dim() != 4 or o.shape[0] != outs[0].shape[0]:
+                raise ValueError('forward_heads: expected [B,C,h,w] maps of one batch, got %s' % (tuple(o.shape),))
+        feats = [o.to(torch.float32).permute(0, 2, 3, 1).contiguous() for o in outs]
+        B = feats[0].shape[0]
+        pm = self.prediction_layers[0]
+        coef_act = act_name(cfg.mask_proto_coeff_activation)
+        proto_act = act_name(cfg.mask_proto_prototype_activation)
+        for what, a in (('mask_proto_coeff_activation', coef_act), ('mask_proto_prototype_activation', proto_act)):
+            if a not in TO.ACTS:
+                raise NotImplementedError('yolact_amd forward_heads: cfg.%s = %s is not supported (none, relu and tanh are)' % (what, a))
+        with torch.cuda.device(feats[0].device):
+            proto = self._apply_net(self.proto_net, feats[self.proto_src], last_act=None if proto_act == 'none' else proto_act)
+            loc, conf, mask = [], [], []
+            up = [m for m in pm.upfeature if isinstance(m, nn.Conv2d)] if hasattr(pm, 'upfeature') else []
+            hl = pm.bbox_layer
+            # one set of weights on every level: each level works on aliases whose gradients are added in level order
+            shared = TO.share_params(len(feats), [t for m in up + [pm.bbox_layer, pm.conf_layer, pm.mask_layer]
+                                                  for t in (m.weight, m.bias)])
+            for lvl, x in enumerate(feats):
+                hp = shared[lvl]
+                if up:
+                    x = self._apply_net(pm.upfeature, x, params=hp[:2 * len(up)])
+                wb, bb_, wc, bc, wm, bm = hp[2 * len(up):]
+                b, c, m = TO.conv2d_multi(x, [(wb, bb_, None), (wc, bc, None), (wm, bm, coef_act)],
+                                          hl.padding, stride=hl.stride, dilation=hl.dilation, groups=hl.groups)
+                loc.append(b.reshape(B, -1, 4))
+                conf.append(c.reshape(B, -1, cfg.num_classes))
+                mask.append(m.reshape(B, -1, self.mask_dim))
+            pred = {'loc': torch.cat(loc, 1), 'conf': torch.cat(conf, 1), 'mask': torch.cat(mask, 1),
+                    'priors': self._train_priors([tuple(f.shape[1:3]) for f in feats], cfg, feats[0].device), 'proto': proto}
+            if cfg.use_semantic_segmentation_loss:
+                sc = self.semantic_seg_conv
+                segm = TO.conv2d_act(feats[0], sc.weight, sc.bias, sc.padding, None, stride=sc.stride, dilation=sc.dilation,
+                                     groups=sc.groups)
+                pred['segm'] = segm.permute(0, 3, 1, 2)
+        return pred
+
     def forward_raw(self, x):
         """Head outputs before Detect (for parity tests): loc, conf (logits), mask, priors, proto — clones."""
         L.require_cuda(x, 'input batch')
