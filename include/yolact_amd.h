@@ -347,6 +347,14 @@ int ymi_lincomb_crop_batch_f32(const float *proto, const float *coef, const floa
                                float *masks_lo, int B, int cap, int ph, int pw, int D, int crop, void *stream);
 int ymi_mask_upsample_batch_f32(const float *masks_lo, const int32_t *count, float *out, int B, int cap, int ph, int pw,
                                 int h, int w, float thresh, void *stream);
+/* Which kernel the two upsample calls above run for these arguments (host only: no launch, no device access): one of YMI_UP_*, or
+ * the YMI_E* code the call itself returns (YMI_ENULL out_addr 0, YMI_EARG a size <= 0 or nmask > 65535 with a count, YMI_ESHAPE a
+ * count with a width only the flat kernel takes).  nmask = N, or B * cap; out_addr = the `out` pointer (its alignment takes part);
+ * has_count != 0: ymi_mask_upsample_batch_f32 with a count, 0: without one, and ymi_mask_upsample_f32.  The launcher calls the
+ * same function, and it respects the A/B switches YOLACT_AMD_UPSAMPLE / YOLACT_AMD_UPSAMPLE_FLAT (the latter: calls without a
+ * count).  All four kernels write the same bits.  Additive to ABI 9. */
+enum { YMI_UP_FLAT = 1, YMI_UP_BAND = 2, YMI_UP_ROWS16 = 3, YMI_UP_ROWS32 = 4 };
+int ymi_mask_upsample_kernel(int nmask, int ph, int pw, int h, int w, uintptr_t out_addr, int has_count);
 /* boxes [N,4] relative -> int64 absolute pixels via sanitize_coordinates(cast=False) then truncation */
 int ymi_boxes_to_pixels(const float *box, int64_t *out, int N, int w, int h, void *stream);
 

@@ -273,6 +273,8 @@ class RleShape(C.Structure):
  WS_CONV_WGRAD) = range(1, 25)
 
 EFORMAT, EUNSUPPORTED = -4, -5
+UP_FLAT, UP_BAND, UP_ROWS16, UP_ROWS32 = 1, 2, 3, 4       # ymi_mask_upsample_kernel (include/yolact_amd.h YMI_UP_*)
+UP_NAMES = {1: 'flat', 2: 'band', 3: 'rows16', 4: 'rows32'}
 
 # every symbol include/yolact_amd.h declares: (name, restype, argtypes)
 _P, _I, _F = C.c_void_p, C.c_int, C.c_float
@@ -298,6 +300,7 @@ SYMBOLS = [
     ('ymi_mask_upsample_f32', C.c_int, [_P, _P, _I, _I, _I, _I, _I, _F, _P]),
     ('ymi_lincomb_crop_batch_f32', C.c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     ('ymi_mask_upsample_batch_f32', C.c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P]),
+    ('ymi_mask_upsample_kernel', C.c_int, [_I, _I, _I, _I, _I, C.c_size_t, _I]),
     ('ymi_boxes_to_pixels', C.c_int, [_P, _P, _I, _I, _I, _P]),
     ('ymi_dcn_v2_forward_f32', C.c_int, [C.POINTER(DcnDesc), _P]),
     ('ymi_dcn_v2_backward_f32', C.c_int, [C.POINTER(DcnBwdDesc), _P]),

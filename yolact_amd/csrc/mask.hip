@@ -387,47 +387,65 @@ int upsample_variant() {
   }();
   return v;
 }
+// Which kernel an upsample call runs: YMI_UP_* (include/yolact_amd.h), or the YMI_E* code the call returns instead of launching.
+// The one place that decides: launch_upsample switches on it and ymi_mask_upsample_kernel exports it.
 // rows kernel when its source rows fit the LDS budget, banded kernel when a band does, flat kernel otherwise
-int launch_upsample(const float *masks_lo, float *out, const int32_t *count, int nmask, int cap, int ph, int pw, int h, int w,
-                    float thresh, hipStream_t s) {
+struct UpChoice { int kernel, R; size_t lds; };
+UpChoice choose_upsample(int nmask, int ph, int pw, int h, int w, uintptr_t out_addr, bool has_count) {
+  static const bool flat = getenv("YOLACT_AMD_UPSAMPLE_FLAT") != nullptr;   // A/B switch for the measurement log (calls without a count)
+  if (flat && !has_count) return {YMI_UP_FLAT, 0, 0};
   {
     const float sh = (float)ph / (float)h;
-    const int variant = upsample_variant();
-    int abl = 0;
-#ifdef YMI_DIAGNOSTICS
-    { const char *e = getenv("YMI_UP_ABLATE"); abl = e ? atoi(e) : 0; }
-#endif
     // bands of 32 output rows when that still gives every CU several blocks, else 16; tiny launches (< ~2 blocks per CU even so)
     // stay on the band kernel, whose 8-row blocks spread better (100 masks of 550 x 550: 0.033 vs 0.037 ms)
     const long bands32 = (long)((h + 31) / 32) * nmask, bands16 = (long)((h + 15) / 16) * nmask;
     const int R = bands32 >= 5120 ? 32 : 16;
     const long ns_max = (long)((float)R * sh) + 3;               // source rows a band of R output rows can touch
     const size_t lds = (size_t)ns_max * (w + pw) * sizeof(float);
-    if (variant != 2 && w >= 64 && lds <= 48 * 1024 && nmask <= 65535 && ((uintptr_t)out & 15) == 0 && (R == 32 || bands16 >= 4096)) {
+    if (upsample_variant() != 2 && w >= 64 && lds <= 48 * 1024 && nmask <= 65535 && (out_addr & 15) == 0 && (R == 32 || bands16 >= 4096))
+      return {R == 32 ? YMI_UP_ROWS32 : YMI_UP_ROWS16, R, lds};
+  }
+  const size_t band_lds = ((size_t)UP_ROWS * w + 4) * sizeof(float);
+  if (band_lds <= 64 * 1024 && nmask <= 65535 && (out_addr & 15) == 0) return {YMI_UP_BAND, UP_ROWS, band_lds};
+  if (has_count) return {YMI_ESHAPE, 0, 0};
+  return {YMI_UP_FLAT, 0, 0};
+}
+
+int launch_upsample(const float *masks_lo, float *out, const int32_t *count, int nmask, int cap, int ph, int pw, int h, int w,
+                    float thresh, hipStream_t s) {
+  const UpChoice c = choose_upsample(nmask, ph, pw, h, w, (uintptr_t)out, count != nullptr);
+  const float sh = (float)ph / (float)h, sw = (float)pw / (float)w;
+  switch (c.kernel) {
+    case YMI_UP_ROWS16:
+    case YMI_UP_ROWS32: {
+      const int variant = upsample_variant();
+      int abl = 0;
+#ifdef YMI_DIAGNOSTICS
+      { const char *e = getenv("YMI_UP_ABLATE"); abl = e ? atoi(e) : 0; }
+#endif
       // (one block per band: persistent blocks looping over bands measured SLOWER, 0.295 vs 0.272 ms — profiles/r04_upsample_ablation.txt)
-      const dim3 grid((h + R - 1) / R, nmask);
-      const float sw = (float)pw / (float)w;
-#define YMI_UP_LAUNCH(RR, NTV) hipLaunchKernelGGL((mask_upsample_rows_k<RR, NTV>), grid, dim3(256), lds, s, masks_lo, out, ph, pw, h, w, \
+      const dim3 grid((h + c.R - 1) / c.R, nmask);
+#define YMI_UP_LAUNCH(RR, NTV) hipLaunchKernelGGL((mask_upsample_rows_k<RR, NTV>), grid, dim3(256), c.lds, s, masks_lo, out, ph, pw, h, w, \
                                                   sh, sw, thresh, (const int *)count, cap, abl, nmask)
-      if (R == 32) { if (variant == 1) YMI_UP_LAUNCH(32, true); else YMI_UP_LAUNCH(32, false); }
+      if (c.R == 32) { if (variant == 1) YMI_UP_LAUNCH(32, true); else YMI_UP_LAUNCH(32, false); }
       else { if (variant == 1) YMI_UP_LAUNCH(16, true); else YMI_UP_LAUNCH(16, false); }
 #undef YMI_UP_LAUNCH
       return ymi_launch_status();
     }
+    case YMI_UP_BAND:
+      hipLaunchKernelGGL(mask_upsample_band_k<UP_ROWS>, dim3((h + UP_ROWS - 1) / UP_ROWS, nmask), dim3(256), c.lds, s, masks_lo, out,
+                         ph, pw, h, w, sh, sw, thresh, (const int *)count, cap);
+      return ymi_launch_status();
+    case YMI_UP_FLAT: {
+      const long total = (long)nmask * h * w, total4 = (total + 3) / 4;
+      const long g = (total4 + 255) / 256, capg = 256L * 16;
+      hipLaunchKernelGGL(mask_upsample_k, dim3((int)(g > capg ? capg : g)), dim3(256), 0, s, masks_lo, out, ph, pw, h, w, sh, sw,
+                         thresh, total4, total);
+      return ymi_launch_status();
+    }
+    default:
+      return c.kernel;
   }
-  if (((size_t)UP_ROWS * w + 4) * sizeof(float) <= 64 * 1024 && nmask <= 65535 && ((uintptr_t)out & 15) == 0) {
-    hipLaunchKernelGGL(mask_upsample_band_k<UP_ROWS>, dim3((h + UP_ROWS - 1) / UP_ROWS, nmask), dim3(256),
-                       ((size_t)UP_ROWS * w + 4) * sizeof(float), s, masks_lo, out, ph, pw, h, w, (float)ph / (float)h,
-                       (float)pw / (float)w, thresh, (const int *)count, cap);
-    return ymi_launch_status();
-  }
-  if (count) return YMI_ESHAPE;
-  const long total = (long)nmask * h * w, total4 = (total + 3) / 4;
-  long g = (total4 + 255) / 256;
-  const long capg = 256L * 16;
-  hipLaunchKernelGGL(mask_upsample_k, dim3((int)(g > capg ? capg : g)), dim3(256), 0, s, masks_lo, out, ph, pw, h, w,
-                     (float)ph / (float)h, (float)pw / (float)w, thresh, total4, total);
-  return ymi_launch_status();
 }
 }  // namespace
 
@@ -442,16 +460,13 @@ int ymi_mask_upsample_f32(const float *masks_lo, float *out, int N, int ph, int 
                           void *stream) {
   if (!masks_lo || !out) return YMI_ENULL;
   if (N <= 0 || ph <= 0 || pw <= 0 || h <= 0 || w <= 0) return YMI_EARG;
-  static const bool flat = getenv("YOLACT_AMD_UPSAMPLE_FLAT") != nullptr;   // A/B switch for the measurement log
-  if (!flat)
-    return launch_upsample(masks_lo, out, nullptr, N, N, ph, pw, h, w, thresh, (hipStream_t)stream);
-  const long total = (long)N * h * w, total4 = (total + 3) / 4;
-  long g = (total4 + 255) / 256;
-  const long cap = 256L * 16;
-  const int grid = (int)(g > cap ? cap : g);
-  hipLaunchKernelGGL(mask_upsample_k, dim3(grid), dim3(256), 0, (hipStream_t)stream, masks_lo, out, ph, pw, h, w,
-                     (float)ph / (float)h, (float)pw / (float)w, thresh, total4, total);
-  return ymi_launch_status();
+  return launch_upsample(masks_lo, out, nullptr, N, N, ph, pw, h, w, thresh, (hipStream_t)stream);
+}
+
+int ymi_mask_upsample_kernel(int nmask, int ph, int pw, int h, int w, uintptr_t out_addr, int has_count) {
+  if (!out_addr) return YMI_ENULL;
+  if (nmask <= 0 || ph <= 0 || pw <= 0 || h <= 0 || w <= 0 || (has_count && nmask > 65535)) return YMI_EARG;
+  return choose_upsample(nmask, ph, pw, h, w, out_addr, has_count != 0).kernel;
 }
 
 int ymi_boxes_to_pixels(const float *box, int64_t *out, int N, int w, int h, void *stream) {
