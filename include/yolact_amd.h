@@ -783,6 +783,7 @@ typedef struct ymi_maskiou_head_desc {
 int ymi_maskiou_head_f32(const ymi_maskiou_head_desc *d, void *stream);
 
 /* -- the backward of the train-mode heads and protonet (csrc/conv_train.hip; additive, the ABI number stays) -----------------------
+ * and of the train-mode FPN (yolact.py:311-360: ymi_conv_wgrad_desc.stride, ymi_bilinear_size_bwd_nhwc_f32).
  * Stride-1 convolutions (3x3 / pad 1, 1x1 / pad 0), ReLU, tanh and the x2 bilinear upsample (yolact.py:133-212, 580-647).  No
  * floating-point atomics anywhere: the same inputs give the same bits.  The DATA gradient of such a convolution is
  * ymi_conv2d_nhwc_f32 on g with the filters flipped in both taps and transposed in (Cin, Cout); it has no entry of its own.
@@ -798,15 +799,21 @@ int ymi_act_bwd_f32(const float *y, const float *dy, float *g, long npos, int C,
  * exact-fp32 matrix instruction with the positions as its k index.  The positions are cut into chunks whose partial sums go to ws
  * (launch one) and are added in chunk order (launch two).  dw or db may be NULL.  YMI_EARG: a size < 1, a geometry other than
  * 3x3 / pad 1 and 1x1 / pad 0; YMI_ESHAPE: Cin % 32, ldg < Cout, x or g of 2^29 elements or more (2 GiB, the conv engine's limit), ws not 16-byte aligned, ws_bytes
- * too small; YMI_ENULL: g or ws NULL, nothing to compute, x NULL with dw.  No error path launches anything. */
+ * too small; YMI_ENULL: g or ws NULL, nothing to compute, x NULL with dw.  No error path launches anything.
+ * stride = 2 (the FPN's downsample layers, the backbone's stage entries): g is [B,Ho,Wo,ldg] with Ho = (H + 2 pad - kh) / 2 + 1, the
+ * positions (n, oy, ox) are those of g, and tap (ky, kx) reads x at (2 oy + ky - pad, 2 ox + kx - pad), 0 outside the map (on an odd H
+ * the bottom row of taps of the last output row falls outside).  The chunks, hence the workspace, follow the positions of g; the
+ * chunk-ordered second pass, the db rule and the 2^29 limits (x, and g over its own positions) are those of stride 1.  YMI_EARG: a
+ * stride other than 0, 1, 2. */
 typedef struct ymi_conv_wgrad_desc {
   const float *x;               /* [B,H,W,Cin] */
-  const float *g;               /* [B,H,W,ldg], channels [0, Cout) are read */
+  const float *g;               /* [B,Ho,Wo,ldg] (Ho = H, Wo = W at stride 1), channels [0, Cout) are read */
   float *dw;                    /* [kh*kw*Cin, Cout] */
   float *db;                    /* [Cout] */
   void *ws;                     /* ymi_workspace_bytes(YMI_WS_CONV_WGRAD, desc) bytes, 16-byte aligned */
   int64_t ws_bytes;
-  int32_t B, H, W, Cin, Cout, ldg, kh, kw, pad, _pad0;
+  int32_t B, H, W, Cin, Cout, ldg, kh, kw, pad;
+  int32_t stride;               /* 0 or 1: stride 1 (callers from before the field had a name leave it 0); 2: stride 2 */
 } ymi_conv_wgrad_desc;
 int ymi_conv_wgrad_nhwc_f32(const ymi_conv_wgrad_desc *d, void *stream);
 
@@ -816,6 +823,16 @@ int ymi_conv_wgrad_nhwc_f32(const ymi_conv_wgrad_desc *d, void *stream);
  * not 0 / 1; YMI_ENULL: dy, dx, or y with relu. */
 int ymi_bilinear_bwd_nhwc_f32(const float *dy, const float *y, float *dx, int B, int Hi, int Wi, int C, int Ho, int Wo, int relu,
                               void *stream);
+
+/* The backward of y = F.interpolate(x, size=(Ho, Wo), mode='bilinear', align_corners=False) (ymi_bilinear_nhwc_f32 with scale 0, the
+ * FPN's top-down step, yolact.py:332) for ANY Ho >= Hi and Wo >= Wi, Ho = Hi (the identity: dx = dy bit for bit) and Hi = 1 included;
+ * the scale is (float)Hi / (float)Ho.  A gather: one thread per (input pixel, 4 channels) inverts the coordinate map into a
+ * conservative range of candidate output rows and columns, asks the forward's own fp32 coordinates (upsample_math.h up_coord) which
+ * of them read its pixel, and adds (1 - l1) dy where i0 is its index and l1 dy where i1 is (both at the clamped last row).
+ * SUMMATION ORDER (part of the contract): output rows ascending, within a row output columns ascending, each term (wy * wx) * dy.
+ * Every element of dx is written; no atomics.  YMI_ENULL: dy or dx NULL; YMI_EARG: a size < 1; YMI_ESHAPE: Ho < Hi, Wo < Wi, C % 4,
+ * a pointer not 16-byte aligned, 2^40 elements of dy or more.  No error path launches anything. */
+int ymi_bilinear_size_bwd_nhwc_f32(const float *dy, float *dx, int B, int Hi, int Wi, int C, int Ho, int Wo, void *stream);
 
 /* -- ResNet stem in one launch (backbone.py:126-133 + the layout change of yolact.py:564) ---------------------------------
  * x [B,3,H,W] NCHW fp32 (the normalised image) -> conv 7x7 / 2 / pad 3 (3 -> 64) + folded BN + ReLU -> max-pool 3x3 / 2 / pad 1

@@ -176,7 +176,7 @@ class ConvWgradDesc(C.Structure):
     _fields_ = [('x', C.c_void_p), ('g', C.c_void_p), ('dw', C.c_void_p), ('db', C.c_void_p), ('ws', C.c_void_p),
                 ('ws_bytes', C.c_int64),
                 ('B', C.c_int32), ('H', C.c_int32), ('W', C.c_int32), ('Cin', C.c_int32), ('Cout', C.c_int32), ('ldg', C.c_int32),
-                ('kh', C.c_int32), ('kw', C.c_int32), ('pad', C.c_int32), ('_pad0', C.c_int32)]
+                ('kh', C.c_int32), ('kw', C.c_int32), ('pad', C.c_int32), ('stride', C.c_int32)]
 
 
 class DetectDesc(C.Structure):
@@ -317,6 +317,7 @@ SYMBOLS = [
     ('ymi_act_bwd_f32', C.c_int, [_P, _P, _P, C.c_long] + [_I] * 6 + [_P]),
     ('ymi_conv_wgrad_nhwc_f32', C.c_int, [C.POINTER(ConvWgradDesc), _P]),
     ('ymi_bilinear_bwd_nhwc_f32', C.c_int, [_P, _P, _P] + [_I] * 7 + [_P]),
+    ('ymi_bilinear_size_bwd_nhwc_f32', C.c_int, [_P, _P] + [_I] * 6 + [_P]),
     ('ymi_composite_masks_u8', C.c_int, [_P, _P, _P, _I, _I, _I, _F, _P, _P]),
     ('ymi_mask_iou_f32', C.c_int, [_P, _P, _I, _I, C.c_long, _I, _P, _P, _P]),
     ('ymi_jaccard_f32', C.c_int, [_P, _P, _I, _I, _I, _P, _P]),

@@ -17,6 +17,12 @@
 //   ymi_bilinear_bwd_nhwc_f32   the backward of ymi_bilinear_nhwc_f32 for Ho = 2 Hi, Wo = 2 Wi as a gather: an input pixel (iy, ix)
 //                               walks the output rows 2 iy - 2 .. 2 iy + 2 and columns 2 ix - 2 .. 2 ix + 2 in order, asks
 //                               upsample_math.h which of them read it and with what weight, and sums.
+//
+// The backward of the train-mode FPN (yolact.py:311-360) adds two things: a stride (1 or 2) in the weight gradient, as a template
+// parameter of wgrad_k (the positions stay those of g, the stride only changes which pixel of x a tap reads), and
+//   ymi_bilinear_size_bwd_nhwc_f32   the backward of the size-form interpolation for any Ho >= Hi, Wo >= Wi (the pyramid of a 550 x 550
+//                               image is 69 -> 35 -> 18: neither step is x2), the same gather with the candidate outputs found by
+//                               inverting the coordinate map.
 #include "loss_common.h"
 #include "upsample_math.h"
 #include "../../include/yolact_amd.h"
@@ -56,13 +62,16 @@ struct WgParams {
   float *dw, *db, *ws_w, *ws_b;
   int H, W, Cin, Cout, ldg, kw, pad, ncc, K, nchunks, want_w, want_b;
   long P, per;
+  int Ho, Wo;                                          // the map of g (stride 2; H, W at stride 1)
 };
 
 // row of a 32 x 32 accumulator held in register r by this lane (column = lane & 31)
 __device__ __forceinline__ int acc_row(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
 
 // NT: 32-column output-channel tiles per wave (a block covers NT * 128 output channels, gridDim.z such groups)
-template <int NT> __global__ __launch_bounds__(256, NT == 4 ? 1 : 2) void wgrad_k(const WgParams p) {
+// S: the convolution's stride, 1 or 2.  A template parameter, so that the stride-1 instantiation carries nothing of stride 2: the
+// positions are those of g, [B, Ho, Wo]; at stride 2 tap (ky, kx) of position (n, oy, ox) reads x at (2 oy + ky - pad, 2 ox + kx - pad).
+template <int NT, int S> __global__ __launch_bounds__(256, NT == 4 ? 1 : 2) void wgrad_k(const WgParams p) {
 #if defined(__HIP_DEVICE_COMPILE__)
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int ln = lane & 31, kk = lane >> 5;
@@ -97,7 +106,9 @@ template <int NT> __global__ __launch_bounds__(256, NT == 4 ? 1 : 2) void wgrad_
 
   // this lane's positions: pos0 + kk, + 2, + 4, ..; their pixel coordinates are carried along
   long pos = pos0 + kk;
-  int ox = (int)(pos % p.W), oy = (int)((pos / p.W) % p.H);
+  const int PW = S == 1 ? p.W : p.Wo, PH = S == 1 ? p.H : p.Ho;   // the map the positions run over
+  int ox = (int)(pos % PW), oy = (int)((pos / PW) % PH);
+  int n = S == 1 ? 0 : (int)(pos / ((long)PW * PH));   // stride 2 only: the image, for the address of x
   // byte offsets fit 32 bits (validate_wgrad): a uniform base plus one register per load
   const int xlane = 4 * (c0 + ln), shift = 4 * ((sy * p.W + sx) * p.Cin);
   const char *xb = reinterpret_cast<const char *>(p.x), *gb = reinterpret_cast<const char *>(p.g);
@@ -112,19 +123,29 @@ template <int NT> __global__ __launch_bounds__(256, NT == 4 ? 1 : 2) void wgrad_
 #pragma unroll
     for (int s = 0; s < 16; ++s) {
       const bool live = pos < pos1;
-      const bool inside = live && (unsigned)(oy + sy) < (unsigned)p.H && (unsigned)(ox + sx) < (unsigned)p.W;
+      const bool inside = live && (unsigned)(S * oy + sy) < (unsigned)p.H && (unsigned)(S * ox + sx) < (unsigned)p.W;
       G.lm |= (live ? 1u : 0u) << s;
       G.am |= (inside ? 1u : 0u) << s;
-      const unsigned xo = (inside ? (unsigned)((int)((unsigned)pos * xstep) + shift) : 0u) + (unsigned)xlane;
+      unsigned xo;
+      if constexpr (S == 1) {
+        xo = (inside ? (unsigned)((int)((unsigned)pos * xstep) + shift) : 0u) + (unsigned)xlane;
+      } else {
+        xo = (inside ? (unsigned)((n * p.H + S * oy + sy) * p.W + S * ox + sx) * xstep : 0u) + (unsigned)xlane;
+      }
       G.a[s] = do_w ? *reinterpret_cast<const float *>(xb + xo) : 0.f;
       const unsigned gi = live ? (unsigned)pos * gstep : 0u;
 #pragma unroll
       for (int j = 0; j < NT; ++j) G.b[j][s] = j < nact ? *reinterpret_cast<const float *>(gb + (gi + gc[j])) : 0.f;
       pos += 2; ox += 2;
-      if (ox >= p.W) { ox -= p.W; ++oy; }               // twice: W may be 1
-      if (ox >= p.W) { ox -= p.W; ++oy; }
-      if (oy >= p.H) oy -= p.H;
-      if (oy >= p.H) oy -= p.H;
+      if (ox >= PW) { ox -= PW; ++oy; }                 // twice: W may be 1
+      if (ox >= PW) { ox -= PW; ++oy; }
+      if constexpr (S == 1) {
+        if (oy >= PH) oy -= PH;
+        if (oy >= PH) oy -= PH;
+      } else {
+        if (oy >= PH) { oy -= PH; ++n; }
+        if (oy >= PH) { oy -= PH; ++n; }
+      }
     }
   };
   auto consume = [&](const Grp &G) {
@@ -189,22 +210,27 @@ __global__ __launch_bounds__(256) void wgrad_sum_k(const WgParams p) {
   }
 }
 
+// the map of g: H x W at stride 1 (the field is 0 or 1), (H + 2 pad - kh) / 2 + 1 at stride 2
+inline int wgrad_out(const ymi_conv_wgrad_desc *d, int size, int k) { return d->stride == 2 ? (size + 2 * d->pad - k) / 2 + 1 : size; }
+inline long wgrad_positions(const ymi_conv_wgrad_desc *d) { return (long)d->B * wgrad_out(d, d->H, d->kh) * wgrad_out(d, d->W, d->kw); }
+
 int validate_wgrad(const ymi_conv_wgrad_desc *d) {
   if (!d) return YMI_ENULL;
   if (d->B < 1 || d->H < 1 || d->W < 1 || d->Cin < 1 || d->Cout < 1) return YMI_EARG;
   if (!((d->kh == 3 && d->kw == 3 && d->pad == 1) || (d->kh == 1 && d->kw == 1 && d->pad == 0))) return YMI_EARG;
+  if (d->stride < 0 || d->stride > 2) return YMI_EARG;
   if (d->Cin % 32 != 0 || d->ldg < d->Cout) return YMI_ESHAPE;
   const long P = (long)d->B * d->H * d->W;
-  if (P * d->Cin >= (1L << 29) || P * d->ldg >= (1L << 29) || (long)d->kh * d->kw * d->Cin * d->Cout >= (1L << 31)) return YMI_ESHAPE;
+  if (P * d->Cin >= (1L << 29) || wgrad_positions(d) * d->ldg >= (1L << 29) || (long)d->kh * d->kw * d->Cin * d->Cout >= (1L << 31)) return YMI_ESHAPE;
   return YMI_OK;
 }
 
 struct WgPlan { int nt, gx, gz, nchunks; long per; };
 
-// the decomposition for a validated shape: about 1024 blocks, chunks of a multiple of 32 positions
+// the decomposition for a validated shape: about 1024 blocks, chunks of a multiple of 32 positions (of g)
 WgPlan wgrad_plan(const ymi_conv_wgrad_desc *d) {
   WgPlan w;
-  const long P = (long)d->B * d->H * d->W;
+  const long P = wgrad_positions(d);
   const int tiles = (d->Cout + 31) / 32;
   w.nt = tiles <= 4 ? 1 : (tiles <= 8 ? 2 : 4);
   w.gz = (d->Cout + w.nt * 128 - 1) / (w.nt * 128);
@@ -265,6 +291,61 @@ __global__ __launch_bounds__(256) void bilinear_bwd_k(const UbParams p) {
   *reinterpret_cast<f32x4 *>(p.dx + (size_t)i * 4) = acc;
 }
 
+// ---- size-form bilinear backward (any Ho >= Hi, Wo >= Wi) ------------------------------------------------------------------------------
+struct UsParams {
+  const float *dy;
+  float *dx;
+  int Hi, Wi, C4, Ho, Wo;
+  float sh, sw;
+  long total;
+};
+
+__device__ __forceinline__ float up_weight_s(int o, float scale, int i, int in_size) {
+  int i0, i1; float l1;
+  up_coord(o, scale, in_size, i0, i1, l1);
+  return (i0 == i ? 1.f - l1 : 0.f) + (i1 == i ? l1 : 0.f);   // the clamped last row: i1 == i0, both terms count
+}
+
+// The output indices that can read input index i: i0 == i or i1 == i needs the source coordinate (o + 1/2) in / out - 1/2 inside
+// (i - 1, i + 1), that is o inside ((2 i - 1) out / (2 in) - 1/2, (2 i + 3) out / (2 in) - 1/2).  Integer bounds around that, one more
+// index each side for the fp32 rounding of the forward's coordinate, clipped; up_coord decides within.
+__device__ __forceinline__ void up_candidates(int i, int in_size, int out_size, int &lo, int &hi) {
+  const long a = (2L * i - 1) * out_size, b = (2L * i + 3) * out_size, d2 = 2L * in_size;
+  long l = (a > 0 ? a / d2 : 0) - 2, h = (b + d2 - 1) / d2 + 1;
+  lo = (int)(l < 0 ? 0 : l);
+  hi = (int)(h > out_size - 1 ? out_size - 1 : h);
+}
+
+// thread = (input pixel, 4 channels); output rows ascending, within a row columns ascending
+__global__ __launch_bounds__(256) void bilinear_size_bwd_k(const UsParams p) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= p.total) return;
+  const int c4 = (int)(i % p.C4);
+  long r = i / p.C4;
+  const int ix = (int)(r % p.Wi); r /= p.Wi;
+  const int iy = (int)(r % p.Hi);
+  const long b = r / p.Hi;
+  int oy0, oy1, ox0, ox1;
+  up_candidates(iy, p.Hi, p.Ho, oy0, oy1);
+  up_candidates(ix, p.Wi, p.Wo, ox0, ox1);
+  // -0.0 is the identity of the addition (+0.0 would turn a lone -0.0 into +0.0); for Ho >= Hi, Wo >= Wi every input pixel is read
+  // with a non-zero weight by some output pixel, so the start value never reaches dx
+  f32x4 acc = {-0.f, -0.f, -0.f, -0.f};
+  for (int oy = oy0; oy <= oy1; ++oy) {
+    const float wy = up_weight_s(oy, p.sh, iy, p.Hi);
+    if (wy == 0.f) continue;
+    for (int ox = ox0; ox <= ox1; ++ox) {
+      const float wx = up_weight_s(ox, p.sw, ix, p.Wi);
+      if (wx == 0.f) continue;
+      const f32x4 d = *reinterpret_cast<const f32x4 *>(p.dy + ((((size_t)b * p.Ho + oy) * p.Wo + ox) * p.C4 + c4) * 4);
+      const float w = wy * wx;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) acc[e] += w * d[e];
+    }
+  }
+  *reinterpret_cast<f32x4 *>(p.dx + (size_t)i * 4) = acc;
+}
+
 }  // namespace
 
 extern "C" int ymi_act_bwd_f32(const float *y, const float *dy, float *g, long npos, int C, int cpad, int ldy, int lddy, int ldg, int act,
@@ -301,12 +382,18 @@ extern "C" int ymi_conv_wgrad_nhwc_f32(const ymi_conv_wgrad_desc *d, void *strea
   p.x = d->x; p.g = d->g; p.dw = d->dw; p.db = d->db;
   p.H = d->H; p.W = d->W; p.Cin = d->Cin; p.Cout = d->Cout; p.ldg = d->ldg; p.kw = d->kw; p.pad = d->pad;
   p.ncc = d->Cin / 32; p.K = d->kh * d->kw * d->Cin; p.nchunks = w.nchunks; p.want_w = d->dw != nullptr; p.want_b = d->db != nullptr;
-  p.P = (long)d->B * d->H * d->W; p.per = w.per;
+  p.P = wgrad_positions(d); p.per = w.per; p.Ho = wgrad_out(d, d->H, d->kh); p.Wo = wgrad_out(d, d->W, d->kw);
   p.ws_w = static_cast<float *>(d->ws);
   p.ws_b = reinterpret_cast<float *>(static_cast<char *>(d->ws) + ymi_ws_part((int64_t)w.nchunks * p.K * d->Cout));
   const dim3 grid(d->dw ? w.gx : 1, w.nchunks, w.gz);     // bias alone: the blocks of tap 0, channels 0 .. 31
-  int rl = w.nt == 1 ? ymi_launch(wgrad_k<1>, grid, dim3(256), 0, stream, p)
-                     : (w.nt == 2 ? ymi_launch(wgrad_k<2>, grid, dim3(256), 0, stream, p) : ymi_launch(wgrad_k<4>, grid, dim3(256), 0, stream, p));
+  int rl;
+  if (d->stride == 2) {
+    rl = w.nt == 1 ? ymi_launch(wgrad_k<1, 2>, grid, dim3(256), 0, stream, p)
+                   : (w.nt == 2 ? ymi_launch(wgrad_k<2, 2>, grid, dim3(256), 0, stream, p) : ymi_launch(wgrad_k<4, 2>, grid, dim3(256), 0, stream, p));
+  } else {
+    rl = w.nt == 1 ? ymi_launch(wgrad_k<1, 1>, grid, dim3(256), 0, stream, p)
+                   : (w.nt == 2 ? ymi_launch(wgrad_k<2, 1>, grid, dim3(256), 0, stream, p) : ymi_launch(wgrad_k<4, 1>, grid, dim3(256), 0, stream, p));
+  }
   if (!rl) rl = ymi_launch(wgrad_sum_k, dim3((unsigned)(((long)p.K * d->Cout + d->Cout + 255) / 256)), dim3(256), 0, stream, p);
   return rl;
 }
@@ -322,4 +409,17 @@ extern "C" int ymi_bilinear_bwd_nhwc_f32(const float *dy, const float *y, float 
   p.dy = dy; p.y = y; p.dx = dx; p.Hi = Hi; p.Wi = Wi; p.C4 = C / 4; p.Ho = Ho; p.Wo = Wo; p.relu = relu;
   p.total = (long)B * Hi * Wi * (C / 4);
   return ymi_launch(bilinear_bwd_k, dim3((unsigned)((p.total + 255) / 256)), dim3(256), 0, stream, p);
+}
+
+extern "C" int ymi_bilinear_size_bwd_nhwc_f32(const float *dy, float *dx, int B, int Hi, int Wi, int C, int Ho, int Wo, void *stream) {
+  if (!dy || !dx) return YMI_ENULL;
+  if (B < 1 || Hi < 1 || Wi < 1 || C < 1 || Ho < 1 || Wo < 1) return YMI_EARG;
+  if (Ho < Hi || Wo < Wi || C % 4 != 0) return YMI_ESHAPE;
+  if ((double)B * Ho * Wo * C >= 0x1p40) return YMI_ESHAPE;
+  if (((uintptr_t)dy | (uintptr_t)dx) & 15) return YMI_ESHAPE;
+  UsParams p;
+  p.dy = dy; p.dx = dx; p.Hi = Hi; p.Wi = Wi; p.C4 = C / 4; p.Ho = Ho; p.Wo = Wo;
+  p.sh = (float)Hi / (float)Ho; p.sw = (float)Wi / (float)Wo;       // as ymi_bilinear_nhwc_f32 derives them from the sizes
+  p.total = (long)B * Hi * Wi * (C / 4);
+  return ymi_launch(bilinear_size_bwd_k, dim3((unsigned)((p.total + 255) / 256)), dim3(256), 0, stream, p);
 }

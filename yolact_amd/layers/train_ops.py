@@ -1,9 +1,15 @@
-"""Differentiable building blocks of the train-mode heads and protonet on the HIP kernels (csrc/conv_train.hip and the conv engine).
+"""Differentiable building blocks of the train-mode heads, protonet and FPN on the HIP kernels (csrc/conv_train.hip and the conv
+engine).
 
     conv2d_act(x, weight, bias, padding, act)            -> y [B,H,W,Cout]: act(conv(x, weight) + bias), act in {None, 'relu', 'tanh'}
     conv2d_multi(x, [(weight, bias, act), ..], padding)  -> one y per entry: up to three convolutions of the SAME input as one launch
                                                             (the head's bbox / conf / mask layers, yolact.py:169-173)
     upsample2x(x, relu)                                  -> [B,2H,2W,C]: F.interpolate(scale_factor=2, bilinear, align_corners=False)
+
+    conv2d_down(x, weight, bias, act)                    -> [B,Ho,Wo,Cout]: the same at stride 2 with padding k // 2 (the FPN's
+                                                            downsample layers, yolact.py:349-351); 3x3 and 1x1, Cin % 32 == 0
+    upsample_add(top, lat)                               -> F.interpolate(top, size of lat, bilinear, align_corners=False) + lat (the
+                                                            FPN's top-down sum, yolact.py:332-334), any size of lat >= that of top
 
 x and the results are NHWC fp32 GPU tensors; weight and bias are nn.Conv2d parameters in torch layout.  Everything is once
 differentiable in x, every weight and every bias.  Each call packs its filters from the CURRENT parameter values (a permute; no
@@ -13,7 +19,10 @@ naming it.  CPU tensors raise: there is no CPU path.
 
 Launches of one convolution's backward: ymi_act_bwd_f32 per output (g = dy * act'(y), side by side in one buffer whose channel stride
 is padded to a multiple of 32, padding zeroed), ymi_conv_wgrad_nhwc_f32 once over all outputs (dw, db), ymi_conv2d_nhwc_f32 once on g
-with the filters flipped in both taps and transposed in (Cin, Cout) (dx).
+with the filters flipped in both taps and transposed in (Cin, Cout) (dx).  conv2d_down: the same with ymi_conv_wgrad_desc.stride = 2;
+its dx first spreads g over a zeroed [B,H,W,ldg] buffer (gz[:, ::2, ::2] = g) and then runs the stride-1 data gradient on it, which
+spends four times the useful FLOPs (fine for the FPN's 18 x 18 and 9 x 9 maps, not for a backbone).  upsample_add: d_lat = dy,
+d_top = ymi_bilinear_size_bwd_nhwc_f32 (a gather in a fixed order).
 """
 from __future__ import annotations
 
@@ -54,16 +63,17 @@ def check_conv(weight, padding, stride=1, dilation=1, groups=1, who='conv2d_act'
     return kh, padding[0]
 
 
-def _engine_conv(x, ldx, wpk, bias, Cin, Cout, k, pad, segs):
+def _engine_conv(x, ldx, wpk, bias, Cin, Cout, k, pad, segs, stride=1):
     """One ymi_conv2d_nhwc_f32 launch on the exact-fp32 tiles: x [B,H,W,ldx], wpk [CoutPad][k*k*Cin], segs = (n0, n1, act, tensor)."""
     B, H, W = x.shape[:3]
+    Ho, Wo = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
     d = L.ConvDesc()
     d.x, d.w, d.bias = x.data_ptr(), wpk.data_ptr(), (None if bias is None else bias.data_ptr())
-    d.B, d.H, d.W, d.Cin, d.ldx, d.Ho, d.Wo, d.Cout = B, H, W, Cin, ldx, H, W, Cout
-    d.kh, d.kw, d.stride, d.pad, d.Kpad, d.tile = k, k, 1, pad, k * k * Cin, L.TILE_AUTO
+    d.B, d.H, d.W, d.Cin, d.ldx, d.Ho, d.Wo, d.Cout = B, H, W, Cin, ldx, Ho, Wo, Cout
+    d.kh, d.kw, d.stride, d.pad, d.Kpad, d.tile = k, k, stride, pad, k * k * Cin, L.TILE_AUTO
     d.nseg = len(segs)
     for i, (n0, n1, act, y) in enumerate(segs):
-        d.seg[i] = L.ConvSeg(n0, n1, act, n1 - n0, H * W * (n1 - n0), y.data_ptr())
+        d.seg[i] = L.ConvSeg(n0, n1, act, n1 - n0, Ho * Wo * (n1 - n0), y.data_ptr())
     L.check(L.lib().ymi_conv2d_nhwc_f32(C.byref(d), L.stream_ptr()), 'ymi_conv2d_nhwc_f32')
 
 
@@ -239,6 +249,144 @@ def upsample2x(x, relu=False):
     if x.dim() != 4 or x.shape[3] % 4 != 0:
         raise NotImplementedError('yolact_amd upsample2x: x %s is not supported ([B,H,W,C] with C %% 4 == 0 is)' % (tuple(x.shape),))
     return Upsample2x.apply(x, bool(relu))
+
+
+def check_down(weight, who='conv2d_down'):
+    """NotImplementedError naming what of a stride-2 convolution's geometry the kernels do not take -> (k, pad = k // 2)."""
+    if weight.dim() != 4:
+        raise NotImplementedError('yolact_amd %s: a weight of shape %s is not supported ([Cout,Cin,k,k] is)' % (who, tuple(weight.shape)))
+    Cout, Cin, kh, kw = weight.shape
+    if (kh, kw) not in ((3, 3), (1, 1)):
+        raise NotImplementedError('yolact_amd %s: a %d x %d kernel at stride 2 is not supported (3 x 3 / padding 1 and 1 x 1 / '
+                                  'padding 0 are)' % (who, kh, kw))
+    if Cin % 32 != 0:
+        raise NotImplementedError('yolact_amd %s: Cin = %d is not supported (a multiple of 32 input channels is)' % (who, Cin))
+    return kh, kh // 2
+
+
+class ConvDown(torch.autograd.Function):
+    """apply(k, act, x [B,H,W,Cin], weight, bias) -> y [B,Ho,Wo,Cout], Ho = (H + 2 (k // 2) - k) // 2 + 1: a stride-2 convolution."""
+
+    @staticmethod
+    def forward(ctx, k, act, x, weight, bias):
+        dev = x.device
+        Cout, Cin = int(weight.shape[0]), int(weight.shape[1])
+        pad = k // 2
+        with torch.cuda.device(dev), torch.no_grad():
+            xd = LC.f32(x, dev)
+            B, H, W, _ = xd.shape
+            y = torch.empty(B, (H + 2 * pad - k) // 2 + 1, (W + 2 * pad - k) // 2 + 1, Cout, dtype=torch.float32, device=dev)
+            _engine_conv(xd, Cin, _pack_forward(weight.detach().float()), LC.f32(bias, dev), Cin, Cout, k, pad, [(0, Cout, act, y)],
+                         stride=2)
+        ctx.save_for_backward(x, weight, bias, y)          # (the inputs: autograd's version check)
+        ctx.k, ctx.act = k, act
+        ctx.dtypes = [x.dtype, weight.dtype, bias.dtype]
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        want_x, want_w, want_b = ctx.needs_input_grad[2:]
+        x, weight, bias, y = ctx.saved_tensors
+        if not (want_x or want_w or want_b):
+            return (None,) * 5
+        dev = x.device
+        lib, s = L.lib(), L.stream_ptr()
+        k, pad = ctx.k, ctx.k // 2
+        with torch.cuda.device(dev), torch.no_grad():
+            xd = LC.f32(x, dev)
+            B, H, W, Cin = xd.shape
+            _, Ho, Wo, Cout = y.shape
+            ldg = _ceil(Cout, 32)
+            dyd = LC.f32(dy, dev)
+            g = torch.empty(B, Ho, Wo, ldg, dtype=torch.float32, device=dev)
+            L.check(lib.ymi_act_bwd_f32(y.data_ptr(), dyd.data_ptr(), g.data_ptr(), B * Ho * Wo, Cout, ldg, Cout, Cout, ldg, ctx.act, s),
+                    'ymi_act_bwd_f32')
+            dw = db = dx = None
+            if want_w or want_b:
+                d = L.ConvWgradDesc()
+                dwf = torch.empty(k * k * Cin, Cout, dtype=torch.float32, device=dev) if want_w else None
+                db = torch.empty(Cout, dtype=torch.float32, device=dev) if want_b else None
+                d.x, d.g = xd.data_ptr(), g.data_ptr()
+                d.dw, d.db = (None if t is None else t.data_ptr() for t in (dwf, db))
+                d.B, d.H, d.W, d.Cin, d.Cout, d.ldg, d.kh, d.kw, d.pad, d.stride = B, H, W, Cin, Cout, ldg, k, k, pad, 2
+                ws = LC.workspace('CONV_WGRAD', d, dev)
+                d.ws_bytes = ws.numel()
+                L.check(lib.ymi_conv_wgrad_nhwc_f32(C.byref(d), s), 'ymi_conv_wgrad_nhwc_f32')
+                if want_w:
+                    dw = dwf.reshape(k, k, Cin, Cout).permute(3, 2, 0, 1).contiguous()
+            if want_x:
+                # g with zeros between its pixels, exactly H x W (even and odd sizes), then the stride-1 data gradient: the added
+                # zeros change no bit of a sum, and a pixel no window reads (1x1) gets an exact +0.0.  Four times the useful FLOPs.
+                gz = torch.zeros(B, H, W, ldg, dtype=torch.float32, device=dev)
+                gz[:, ::2, ::2] = g
+                dx = torch.empty(B, H, W, Cin, dtype=torch.float32, device=dev)
+                _engine_conv(gz, ldg, _pack_dgrad(weight.detach().float(), ldg), None, ldg, Cin, k, k - 1 - pad, [(0, Cin, L.ACT_NONE, dx)])
+        out = [dx, dw, db]
+        return (None, None) + tuple(None if t is None else t.to(dt) for t, dt in zip(out, ctx.dtypes))
+
+
+def conv2d_down(x, weight, bias, act=None):
+    """act(conv2d(x, weight, bias, stride=2, padding=k // 2)) on NHWC x -> NHWC: 3 x 3 / pad 1 and 1 x 1 / pad 0, Cin % 32 == 0."""
+    L.require_cuda(x, 'conv2d_down x')
+    L.require_cuda(weight, 'conv2d_down weight')
+    if act not in ACTS:
+        raise NotImplementedError('yolact_amd conv2d_down: act = %r is not supported (None, \'relu\' and \'tanh\' are)' % (act,))
+    if bias is None:
+        raise NotImplementedError('yolact_amd conv2d_down: bias = None is not supported (a biased convolution is)')
+    k, _ = check_down(weight)
+    if x.dim() != 4 or x.shape[3] != weight.shape[1]:
+        raise ValueError('conv2d_down: x %s for a weight %s ([B,H,W,Cin] is expected)' % (tuple(x.shape), tuple(weight.shape)))
+    if bias.numel() != weight.shape[0]:
+        raise ValueError('conv2d_down: weight %s / bias %s' % (tuple(weight.shape), tuple(bias.shape)))
+    return ConvDown.apply(k, ACTS[act], x, weight, bias)
+
+
+class UpsampleAdd(torch.autograd.Function):
+    """apply(top [B,h,w,C], lat [B,H,W,C]) -> bilinear(top -> H x W) + lat."""
+
+    @staticmethod
+    def forward(ctx, top, lat):
+        dev = lat.device
+        with torch.cuda.device(dev), torch.no_grad():
+            td = LC.f32(top, dev)
+            y = lat.detach().to(torch.float32).clone(memory_format=torch.contiguous_format)     # never write into an autograd input
+            B, H, W, Cc = y.shape
+            L.check(L.lib().ymi_bilinear_add_nhwc_f32(td.data_ptr(), y.data_ptr(), B, td.shape[1], td.shape[2], Cc, H, W, None,
+                                                      L.stream_ptr()), 'ymi_bilinear_add_nhwc_f32')
+        ctx.save_for_backward(top, lat)                     # (the version check)
+        ctx.dtypes = (top.dtype, lat.dtype)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        top, lat = ctx.saved_tensors
+        want_top, want_lat = ctx.needs_input_grad
+        d_top = None
+        if want_top:
+            dev = top.device
+            with torch.cuda.device(dev), torch.no_grad():
+                dyd = LC.f32(dy, dev)
+                B, h, w, Cc = top.shape
+                d_top = torch.empty(B, h, w, Cc, dtype=torch.float32, device=dev)
+                L.check(L.lib().ymi_bilinear_size_bwd_nhwc_f32(dyd.data_ptr(), d_top.data_ptr(), B, h, w, Cc, dyd.shape[1], dyd.shape[2],
+                                                               L.stream_ptr()), 'ymi_bilinear_size_bwd_nhwc_f32')
+            d_top = d_top.to(ctx.dtypes[0])
+        return d_top, (dy.to(ctx.dtypes[1]) if want_lat else None)
+
+
+def upsample_add(top, lat):
+    """F.interpolate(top, size=lat.shape[1:3], mode='bilinear', align_corners=False) + lat on NHWC tensors (the FPN's top-down sum)."""
+    L.require_cuda(top, 'upsample_add top')
+    L.require_cuda(lat, 'upsample_add lat')
+    if top.dim() != 4 or lat.dim() != 4 or top.shape[0] != lat.shape[0] or top.shape[3] != lat.shape[3] or top.shape[3] % 4 != 0:
+        raise NotImplementedError('yolact_amd upsample_add: top %s / lat %s is not supported ([B,h,w,C] and [B,H,W,C] with '
+                                  'C %% 4 == 0 are)' % (tuple(top.shape), tuple(lat.shape)))
+    if top.shape[1] > lat.shape[1] or top.shape[2] > lat.shape[2]:
+        raise NotImplementedError('yolact_amd upsample_add: a top map %s larger than the lateral %s is not supported (the backward '
+                                  'handles Ho >= Hi, Wo >= Wi)' % (tuple(top.shape[1:3]), tuple(lat.shape[1:3])))
+    return UpsampleAdd.apply(top, lat)
 
 
 class SharedParams(torch.autograd.Function):

@@ -512,6 +512,51 @@ class Yolact(nn.Module):
                 pred['segm'] = segm.permute(0, 3, 1, 2)
         return pred
 
+    def forward_fpn(self, convouts):
+        """The reference's FPN.forward (yolact.py:311-360) on the backbone's selected maps `convouts` ([B,C_j,h_j,w_j] NCHW fp32 on the
+        GPU, finest first, one per entry of fpn.lat_layers) -> the len(selected_layers) maps [B,nf,h,w] that forward_heads takes, for
+        the variant __init__ insists on (conv downsample, relu_pred_layers, no relu_downsample_layers, bilinear).  Once differentiable
+        in every convout and in every parameter of self.fpn (layers/train_ops.py on the HIP kernels).  Each result is a permuted view
+        of NHWC storage, so forward_heads' .permute(0, 2, 3, 1).contiguous() copies nothing.  Needs no plan and reads cfg at call
+        time; the model stays in eval mode and forward() is untouched."""
+        from .layers import train_ops as TO
+        cfg = self.cfg
+        fpn = self.fpn
+        convouts = list(convouts)
+        if not cfg.fpn.pad:
+            raise NotImplementedError('yolact_amd forward_fpn: cfg.fpn.pad = False is not supported (padded pred layers are)')
+        if len(convouts) != len(fpn.lat_layers):
+            raise ValueError('forward_fpn: %d backbone maps for %d lateral layers' % (len(convouts), len(fpn.lat_layers)))
+        for j, c in enumerate(convouts):
+            if c.dim() != 4 or c.shape[0] != convouts[0].shape[0]:
+                raise ValueError('forward_fpn: expected [B,C,h,w] maps of one batch, got %s' % (tuple(c.shape),))
+            if j > 0 and (c.shape[2] > convouts[j - 1].shape[2] or c.shape[3] > convouts[j - 1].shape[3]):
+                raise ValueError('forward_fpn: level %d (%d x %d) is larger than the level below it (%d x %d); the maps come finest '
+                                 'first' % (j, c.shape[2], c.shape[3], convouts[j - 1].shape[2], convouts[j - 1].shape[3]))
+        for c in convouts:
+            L.require_cuda(c, 'forward_fpn backbone map')
+        feats = [c.to(torch.float32).permute(0, 2, 3, 1).contiguous() for c in convouts]
+        n = len(feats)
+        conv = lambda x, m, act: TO.conv2d_act(x, m.weight, m.bias, m.padding, act, stride=m.stride, dilation=m.dilation, groups=m.groups)
+        with torch.cuda.device(feats[0].device):
+            # lat_layers and pred_layers are stored deepest level first (yolact.py:286-296, 324-341)
+            out, x = [None] * n, None
+            for i, lat in enumerate(fpn.lat_layers):
+                j = n - 1 - i
+                lateral = conv(feats[j], lat, None)
+                x = lateral if x is None else TO.upsample_add(x, lateral)
+                out[j] = x
+            for i, pred in enumerate(fpn.pred_layers):
+                j = n - 1 - i
+                out[j] = conv(out[j], pred, 'relu')
+            for down in fpn.downsample_layers:
+                if tuple(down.stride) != (2, 2) or tuple(down.padding) != (down.kernel_size[0] // 2,) * 2 or \
+                        tuple(down.dilation) != (1, 1) or down.groups != 1:
+                    raise NotImplementedError('yolact_amd forward_fpn: downsample layer %r is not supported (stride 2, padding k // 2 is)'
+                                              % (down,))
+                out.append(TO.conv2d_down(out[-1], down.weight, down.bias))
+        return [o.permute(0, 3, 1, 2) for o in out]
+
     def forward_raw(self, x):
         """Head outputs before Detect (for parity tests): loc, conf (logits), mask, priors, proto — clones."""
         L.require_cuda(x, 'input batch')
