@@ -834,6 +834,66 @@ int ymi_bilinear_bwd_nhwc_f32(const float *dy, const float *y, float *dx, int B,
  * a pointer not 16-byte aligned, 2^40 elements of dy or more.  No error path launches anything. */
 int ymi_bilinear_size_bwd_nhwc_f32(const float *dy, float *dx, int B, int Hi, int Wi, int C, int Ho, int Wo, void *stream);
 
+/* -- the backward of the train-mode backbone (csrc/conv_dgrad.hip, csrc/bn_train.hip; additive, the ABI number stays) -------------------
+ * ymi_conv_dgrad_s2_nhwc_f32: the data gradient of a STRIDE-2 convolution, 3x3 / pad 1 or 1x1 / pad 0 (each ResNet stage's first conv2
+ * and the projection shortcuts): dx[n,y,x,ci] = sum over the taps (ky, kx) that exist for the pixel of sum_co g[n,oy,ox,co] w[co,ci,ky,kx],
+ * oy = (y + pad - ky) / 2 where exact and inside [0, Ho), Ho = (H + 2 pad - kh) / 2 + 1 (odd and even H, W).  Only existing taps are
+ * computed: the four parity phases (y & 1, x & 1) of a 3x3 have 1, 2, 2 and 4 taps, 9 tap-products per 2 x 2 pixels (the zero-insert
+ * route over ymi_conv2d_nhwc_f32 spends 36); a tap whose oy or ox lies outside g (the last odd row / column of an even extent) is
+ * masked.  At 1x1 the even / even pixels get one product and every other pixel an exact +0.0.  On v_mfma_f32_32x32x2_f32 (fp32 in,
+ * fp32 accumulate) with Cout as its k index.  w is PACKED by the caller from the current values: [kh][kw][Cout / 4][Cin][4] with
+ * element (ky, kx, co / 4, ci, co % 4) = weight[co, ci, ky, kx].  g's channels [0, Cout) are read; [Cout, ldg) may hold anything.
+ * SUMMATION ORDER (part of the contract, a function of the shape only): an element starts from +0.0 and adds its taps with ky
+ * ascending, within ky kx ascending; within a tap q = 0 .. Cout / 8 - 1 ascending, within q e = 0 .. 3, and step (q, e) adds the two
+ * products of co = 8 q + e and co = 8 q + 4 + e in one instruction.  Every element of dx is written, once; no atomics; the same inputs
+ * give the same bits.  YMI_EARG: a size < 1, another geometry, stride != 2; YMI_ESHAPE: Cin % 32, Cout % 32, ldg < Cout, ldg % 4, 2^29
+ * elements or more in g, dx or w, a pointer not 16-byte aligned; YMI_ENULL: a NULL pointer.  No error path launches anything. */
+typedef struct ymi_conv_dgrad_desc {
+  const float *g;               /* [B,Ho,Wo,ldg] */
+  const float *w;               /* [kh][kw][Cout/4][Cin][4] */
+  float *dx;                    /* [B,H,W,Cin] */
+  int32_t B, H, W, Cin, Cout, ldg, kh, kw, pad;
+  int32_t stride;               /* 2 */
+} ymi_conv_dgrad_desc;
+int ymi_conv_dgrad_s2_nhwc_f32(const ymi_conv_dgrad_desc *d, void *stream);
+
+/* BatchNorm2d on its own, NHWC fp32 viewed as [npos, C], C % 4 == 0; one descriptor for both directions.
+ * ymi_bn_fwd_nhwc_f32, training = 1: mean_c and the biased var_c over npos, invstd = 1 / sqrt(var + eps),
+ * y = gamma (x - mean) invstd + beta (+ res) (then ReLU when relu = 1); mean and invstd are written for the backward; running_mean /
+ * running_var (may be NULL) become (1 - momentum) r + momentum stat, with the unbiased variance var npos / (npos - 1).  The variance is
+ * the mean of squared deviations about the mean (two passes over x; never E[x^2] - E[x]^2), and the sums run over x - x[0, c].
+ * training = 0 (frozen): mean = running_mean, invstd = 1 / sqrt(running_var + eps), the same map; mean / invstd are written, nothing
+ * is updated.
+ * ymi_bn_bwd_nhwc_f32: gh = dy [y > 0] with relu (y = the forward's output), else dy; d_res = gh; dbeta = sum gh; dgamma = sum gh xh,
+ * xh = (x - mean) invstd; dx = gamma invstd (gh - dbeta / npos - xh dgamma / npos) (training: the sums are always formed) or
+ * gamma invstd gh (frozen).  dx, d_res, dgamma, dbeta may each be NULL.
+ * COLUMN SUMS (part of the contract): chunks of per = max(32, ceil(npos / 1024)) positions; a chunk's positions are added in ascending
+ * order from +0.0; of the chunk partials (in ws) of a channel, lane l of one wave adds the chunks l, l + 64, .. in ascending order from
+ * +0.0 and the 64 lane sums are added by a butterfly over the lane distances 32, 16, 8, 4, 2, 1.  No atomics; the same inputs give the same bits.
+ * YMI_EARG: npos / C < 1, training or relu not 0 / 1, eps < 0, training = 1 with npos < 2 (PyTorch refuses it too); YMI_ESHAPE: C % 4,
+ * 2^40 elements or more, a pointer not 16-byte aligned, ws_bytes too small; YMI_ENULL: a pointer the call needs (forward: x, gamma,
+ * beta, y, mean, invstd, ws, and the running statistics when frozen; backward: dy, ws, y with relu, x / mean / invstd for the sums or
+ * dx, gamma for dx, at least one result).  No error path launches anything. */
+typedef struct ymi_bn_desc {
+  const float *x;               /* [npos,C] */
+  const float *res;             /* [npos,C] or NULL (forward) */
+  const float *gamma, *beta;    /* [C] */
+  float *running_mean, *running_var;   /* [C]; updated in place when training */
+  float *y;                     /* [npos,C]: the forward's result; read by the backward when relu */
+  float *mean, *invstd;         /* [C]: written by the forward, read by the backward */
+  const float *dy;              /* [npos,C] (backward) */
+  float *dx, *d_res;            /* [npos,C] or NULL */
+  float *dgamma, *dbeta;        /* [C] or NULL */
+  void *ws;                     /* ymi_workspace_bytes(YMI_WS_BN, desc) bytes, 16-byte aligned */
+  int64_t ws_bytes;
+  int64_t npos;
+  int32_t C, training, relu;
+  float eps, momentum;
+  int32_t _pad0;
+} ymi_bn_desc;
+int ymi_bn_fwd_nhwc_f32(const ymi_bn_desc *d, void *stream);
+int ymi_bn_bwd_nhwc_f32(const ymi_bn_desc *d, void *stream);
+
 /* -- ResNet stem in one launch (backbone.py:126-133 + the layout change of yolact.py:564) ---------------------------------
  * x [B,3,H,W] NCHW fp32 (the normalised image) -> conv 7x7 / 2 / pad 3 (3 -> 64) + folded BN + ReLU -> max-pool 3x3 / 2 / pad 1
  * -> y [B,Hp,Wp,64] NHWC fp32, Hp = ((H - 1) / 2 + 1 - 1) / 2 + 1.  The 64-channel stem output stays in LDS (csrc/stem.hip).
@@ -948,8 +1008,10 @@ enum {
   YMI_WS_MASKIOU_INPUT = 21,    /* desc: ymi_maskiou_input_desc, mh / mw / N read -> its ws: ceil(mh*mw / 256) * N * 32 floats */
   YMI_WS_CONV_BWD = 22,         /* desc: ymi_conv_bwd_desc, the shape read -> its ws: chunks * (kh*kw*Cin + 1) * ceil4(Cout) floats */
   YMI_WS_MASKIOU_HEAD = 23,     /* desc: ymi_maskiou_head_desc, N read -> its ws: N floats, padded to 16 */
-  YMI_WS_CONV_WGRAD = 24        /* desc: ymi_conv_wgrad_desc, the shape read -> its ws: chunks * kh*kw*Cin * Cout floats and chunks *
+  YMI_WS_CONV_WGRAD = 24,       /* desc: ymi_conv_wgrad_desc, the shape read -> its ws: chunks * kh*kw*Cin * Cout floats and chunks *
                                  * Cout floats, each part padded to 16 */
+  YMI_WS_BN = 25                /* desc: ymi_bn_desc, npos / C read -> its ws: 2 * chunks * C + 2 * C floats, chunks = ceil(npos / max(32,
+                                 * ceil(npos / 1024))), each part padded to 16 */
 };
 typedef struct { int32_t A, B; int64_t n; } ymi_mask_iou_shape;
 typedef struct { int32_t N, h, w, cap; } ymi_rle_shape;      /* cap <= 0: the safe capacity h*w + 1 */

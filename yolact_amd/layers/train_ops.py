@@ -11,6 +11,11 @@ engine).
     upsample_add(top, lat)                               -> F.interpolate(top, size of lat, bilinear, align_corners=False) + lat (the
                                                             FPN's top-down sum, yolact.py:332-334), any size of lat >= that of top
 
+    conv2d_plain(x, weight, stride)                      -> [B,Ho,Wo,Cout]: a bias-free convolution, 3x3 / pad 1 or 1x1 / pad 0 at stride 1 or 2
+                                                            (the backbone's convolutions, backbone.py:19-31); Cin % 32 == 0
+    batch_norm_act(x, bn, batch_stats, residual, relu)   -> relu(bn(x) + residual) for an nn.BatchNorm2d, batch statistics or frozen
+    bottleneck(x, block, batch_stats)                    -> a modules.Bottleneck (backbone.py:37-57); bn3 + shortcut + ReLU are one launch
+
 x and the results are NHWC fp32 GPU tensors; weight and bias are nn.Conv2d parameters in torch layout.  Everything is once
 differentiable in x, every weight and every bias.  Each call packs its filters from the CURRENT parameter values (a permute; no
 cache), launches only what needs_input_grad asks for, and saves its inputs, so autograd's version check refuses a backward after an
@@ -22,7 +27,9 @@ is padded to a multiple of 32, padding zeroed), ymi_conv_wgrad_nhwc_f32 once ove
 with the filters flipped in both taps and transposed in (Cin, Cout) (dx).  conv2d_down: the same with ymi_conv_wgrad_desc.stride = 2;
 its dx first spreads g over a zeroed [B,H,W,ldg] buffer (gz[:, ::2, ::2] = g) and then runs the stride-1 data gradient on it, which
 spends four times the useful FLOPs (fine for the FPN's 18 x 18 and 9 x 9 maps, not for a backbone).  upsample_add: d_lat = dy,
-d_top = ymi_bilinear_size_bwd_nhwc_f32 (a gather in a fixed order).
+d_top = ymi_bilinear_size_bwd_nhwc_f32 (a gather in a fixed order).  conv2d_plain: dw from ymi_conv_wgrad_nhwc_f32 with db = NULL; dx at
+stride 1 from the flipped-filter engine launch, at stride 2 from ymi_conv_dgrad_s2_nhwc_f32 (csrc/conv_dgrad.hip: only the taps that
+exist, no zero-filled buffer).  batch_norm_act: ymi_bn_fwd_nhwc_f32 / ymi_bn_bwd_nhwc_f32 (csrc/bn_train.hip).
 """
 from __future__ import annotations
 
@@ -417,3 +424,228 @@ def share_params(n, params):
     params = list(params)
     flat = SharedParams.apply(n, *params)
     return [list(flat[u * len(params):(u + 1) * len(params)]) for u in range(n)]
+
+
+# ---- the backbone: bias-free convolutions, BatchNorm, the bottleneck ----------------------------------------------------------------------
+def check_plain(weight, stride, who='conv2d_plain'):
+    """NotImplementedError naming what of a bias-free convolution's geometry the kernels do not take -> (k, pad = k // 2, stride)."""
+    stride = (int(stride),) * 2 if isinstance(stride, int) else tuple(int(e) for e in stride)
+    if stride not in ((1, 1), (2, 2)):
+        raise NotImplementedError('yolact_amd %s: stride = %r is not supported (stride 1 and stride 2 are)' % (who, stride))
+    if stride == (2, 2):
+        return check_down(weight, who) + (2,)
+    if weight.dim() != 4:
+        raise NotImplementedError('yolact_amd %s: a weight of shape %s is not supported ([Cout,Cin,k,k] is)' % (who, tuple(weight.shape)))
+    k = int(weight.shape[2])
+    return check_conv(weight, k // 2, who=who) + (1,)
+
+
+def _pack_dgrad_s2(w, cpad):
+    """The filters of ymi_conv_dgrad_s2_nhwc_f32: [Cout,Cin,k,k] -> [k][k][cpad/4][Cin][4], Cout padded to cpad with zeros."""
+    Cout, Cin, k, _ = w.shape
+    t = F.pad(w.permute(2, 3, 0, 1), (0, 0, 0, cpad - Cout))                    # [k,k,cpad,Cin]
+    return t.reshape(k, k, cpad // 4, 4, Cin).permute(0, 1, 2, 4, 3).contiguous()
+
+
+class ConvPlain(torch.autograd.Function):
+    """apply(k, stride, x [B,H,W,Cin], weight) -> y [B,Ho,Wo,Cout], padding k // 2, no bias."""
+
+    @staticmethod
+    def forward(ctx, k, stride, x, weight):
+        dev = x.device
+        Cout, Cin = int(weight.shape[0]), int(weight.shape[1])
+        pad = k // 2
+        with torch.cuda.device(dev), torch.no_grad():
+            xd = LC.f32(x, dev)
+            B, H, W, _ = xd.shape
+            y = torch.empty(B, (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1, Cout, dtype=torch.float32, device=dev)
+            _engine_conv(xd, Cin, _pack_forward(weight.detach().float()), None, Cin, Cout, k, pad, [(0, Cout, L.ACT_NONE, y)],
+                         stride=stride)
+        ctx.save_for_backward(x, weight)                   # (the inputs: autograd's version check)
+        ctx.k, ctx.stride, ctx.oshape = k, stride, tuple(y.shape)
+        ctx.dtypes = [x.dtype, weight.dtype]
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        want_x, want_w = ctx.needs_input_grad[2:]
+        x, weight = ctx.saved_tensors
+        if not (want_x or want_w):
+            return (None,) * 4
+        dev = x.device
+        lib, s = L.lib(), L.stream_ptr()
+        k, pad, stride = ctx.k, ctx.k // 2, ctx.stride
+        with torch.cuda.device(dev), torch.no_grad():
+            xd = LC.f32(x, dev)
+            B, H, W, Cin = xd.shape
+            _, Ho, Wo, Cout = ctx.oshape
+            ldg = _ceil(Cout, 32)
+            g = LC.f32(dy, dev)
+            if ldg != Cout:                                # (no backbone layer: their widths are multiples of 32)
+                g = F.pad(g, (0, ldg - Cout))
+            dw = dx = None
+            if want_w:
+                d = L.ConvWgradDesc()
+                dwf = torch.empty(k * k * Cin, Cout, dtype=torch.float32, device=dev)
+                d.x, d.g, d.dw, d.db = xd.data_ptr(), g.data_ptr(), dwf.data_ptr(), None
+                d.B, d.H, d.W, d.Cin, d.Cout, d.ldg, d.kh, d.kw, d.pad, d.stride = B, H, W, Cin, Cout, ldg, k, k, pad, stride
+                ws = LC.workspace('CONV_WGRAD', d, dev)
+                d.ws_bytes = ws.numel()
+                L.check(lib.ymi_conv_wgrad_nhwc_f32(C.byref(d), s), 'ymi_conv_wgrad_nhwc_f32')
+                dw = dwf.reshape(k, k, Cin, Cout).permute(3, 2, 0, 1).contiguous()
+            if want_x:
+                dx = torch.empty(B, H, W, Cin, dtype=torch.float32, device=dev)
+                wf = weight.detach().float()
+                if stride == 1:
+                    _engine_conv(g, ldg, _pack_dgrad(wf, ldg), None, ldg, Cin, k, k - 1 - pad, [(0, Cin, L.ACT_NONE, dx)])
+                else:
+                    wpk = _pack_dgrad_s2(wf, ldg)
+                    d = L.ConvDgradDesc()
+                    d.g, d.w, d.dx = g.data_ptr(), wpk.data_ptr(), dx.data_ptr()
+                    d.B, d.H, d.W, d.Cin, d.Cout, d.ldg, d.kh, d.kw, d.pad, d.stride = B, H, W, Cin, ldg, ldg, k, k, pad, 2
+                    L.check(lib.ymi_conv_dgrad_s2_nhwc_f32(C.byref(d), s), 'ymi_conv_dgrad_s2_nhwc_f32')
+        out = [dx, dw]
+        return (None, None) + tuple(None if t is None else t.to(dt) for t, dt in zip(out, ctx.dtypes))
+
+
+def conv2d_plain(x, weight, stride=1):
+    """conv2d(x, weight, None, stride, padding=k // 2) on NHWC x -> NHWC: 3 x 3 / pad 1 and 1 x 1 / pad 0, stride 1 or 2, Cin % 32 == 0."""
+    L.require_cuda(x, 'conv2d_plain x')
+    L.require_cuda(weight, 'conv2d_plain weight')
+    k, _, st = check_plain(weight, stride)
+    if x.dim() != 4 or x.shape[3] != weight.shape[1]:
+        raise ValueError('conv2d_plain: x %s for a weight %s ([B,H,W,Cin] is expected)' % (tuple(x.shape), tuple(weight.shape)))
+    return ConvPlain.apply(k, st, x, weight)
+
+
+class BnAct(torch.autograd.Function):
+    """apply(stats, relu, eps, momentum, running_mean, running_var, x [..,C], residual or None, gamma, beta) -> y.  stats: batch
+    statistics (the running ones are updated in place) or the running ones as they are."""
+
+    @staticmethod
+    def forward(ctx, stats, relu, eps, momentum, rmean, rvar, x, residual, gamma, beta):
+        dev = x.device
+        with torch.cuda.device(dev), torch.no_grad():
+            xd = LC.f32(x, dev)
+            Cc = xd.shape[-1]
+            npos = xd.numel() // Cc
+            y = torch.empty_like(xd)
+            mean = torch.empty(Cc, dtype=torch.float32, device=dev)
+            invstd = torch.empty(Cc, dtype=torch.float32, device=dev)
+            rd = None if residual is None else LC.f32(residual, dev)
+            gd, bd = LC.f32(gamma, dev), LC.f32(beta, dev)
+            d = L.BnDesc()
+            d.x, d.res, d.gamma, d.beta = xd.data_ptr(), (None if rd is None else rd.data_ptr()), gd.data_ptr(), bd.data_ptr()
+            d.running_mean, d.running_var = rmean.data_ptr(), rvar.data_ptr()
+            d.y, d.mean, d.invstd = y.data_ptr(), mean.data_ptr(), invstd.data_ptr()
+            d.npos, d.C, d.training, d.relu, d.eps, d.momentum = npos, Cc, int(stats), int(relu), eps, momentum
+            ws = LC.workspace('BN', d, dev)
+            d.ws_bytes = ws.numel()
+            L.check(L.lib().ymi_bn_fwd_nhwc_f32(C.byref(d), L.stream_ptr()), 'ymi_bn_fwd_nhwc_f32')
+        # the inputs are saved too: autograd's version check refuses a backward after x or a parameter was edited in place
+        ctx.save_for_backward(x, gamma, beta, y, mean, invstd, *(() if residual is None else (residual,)))
+        ctx.stats, ctx.relu, ctx.eps = int(stats), int(relu), eps
+        ctx.dtypes = [x.dtype, None if residual is None else residual.dtype, gamma.dtype, beta.dtype]
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        want_x, want_r, want_g, want_b = ctx.needs_input_grad[6:]
+        x, gamma, beta, y, mean, invstd = ctx.saved_tensors[:6]      # (the version check)
+        if not (want_x or want_r or want_g or want_b):
+            return (None,) * 10
+        dev = x.device
+        with torch.cuda.device(dev), torch.no_grad():
+            xd, dyd, gd = LC.f32(x, dev), LC.f32(dy, dev), LC.f32(gamma, dev)
+            Cc = xd.shape[-1]
+            new = lambda like: torch.empty_like(like)
+            dx = new(xd) if want_x else None
+            # without a ReLU d_res is dy itself
+            dres = new(xd) if (want_r and ctx.relu) else None
+            dg = torch.empty(Cc, dtype=torch.float32, device=dev) if want_g else None
+            db = torch.empty(Cc, dtype=torch.float32, device=dev) if want_b else None
+            if dx is not None or dres is not None or dg is not None or db is not None:
+                d = L.BnDesc()
+                d.x, d.gamma, d.y, d.mean, d.invstd, d.dy = (xd.data_ptr(), gd.data_ptr(), y.data_ptr(), mean.data_ptr(),
+                                                             invstd.data_ptr(), dyd.data_ptr())
+                d.dx, d.d_res, d.dgamma, d.dbeta = (None if t is None else t.data_ptr() for t in (dx, dres, dg, db))
+                d.npos, d.C, d.training, d.relu, d.eps = xd.numel() // Cc, Cc, ctx.stats, ctx.relu, ctx.eps
+                ws = LC.workspace('BN', d, dev)
+                d.ws_bytes = ws.numel()
+                L.check(L.lib().ymi_bn_bwd_nhwc_f32(C.byref(d), L.stream_ptr()), 'ymi_bn_bwd_nhwc_f32')
+            if want_r and not ctx.relu:
+                dres = dyd
+        out = [dx, dres, dg, db]
+        return (None,) * 6 + tuple(None if (t is None or dt is None) else t.to(dt) for t, dt in zip(out, ctx.dtypes))
+
+
+def batch_norm_act(x, bn, batch_stats=None, residual=None, relu=False):
+    """relu(bn(x) + residual) on NHWC x for an nn.BatchNorm2d `bn`.  batch_stats None follows bn.training; True: the batch statistics
+    (running_mean / running_var updated in place, num_batches_tracked incremented); False: the running statistics (frozen)."""
+    L.require_cuda(x, 'batch_norm_act x')
+    if not isinstance(bn, torch.nn.BatchNorm2d):
+        raise NotImplementedError('yolact_amd batch_norm_act: a %s is not supported (an nn.BatchNorm2d is)' % type(bn).__name__)
+    if not bn.affine:
+        raise NotImplementedError('yolact_amd batch_norm_act: affine = False is not supported')
+    if not bn.track_running_stats:
+        raise NotImplementedError('yolact_amd batch_norm_act: track_running_stats = False is not supported')
+    if bn.momentum is None:
+        raise NotImplementedError('yolact_amd batch_norm_act: momentum = None (a cumulative average) is not supported')
+    stats = bool(bn.training if batch_stats is None else batch_stats)
+    Cc = int(bn.num_features)
+    if x.dim() < 2 or x.shape[-1] != Cc or Cc % 4 != 0:
+        raise NotImplementedError('yolact_amd batch_norm_act: x %s for %d features is not supported ([..,C] with C %% 4 == 0 is)'
+                                  % (tuple(x.shape), Cc))
+    if residual is not None:
+        L.require_cuda(residual, 'batch_norm_act residual')
+        if residual.shape != x.shape:
+            raise ValueError('batch_norm_act: residual %s for x %s' % (tuple(residual.shape), tuple(x.shape)))
+    if stats and x.numel() // Cc < 2:
+        raise NotImplementedError('yolact_amd batch_norm_act: batch statistics over npos = %d values per channel are not supported '
+                                  '(more than one is; PyTorch refuses it too)' % (x.numel() // Cc))
+    L.require_cuda(bn.weight, 'batch_norm_act bn.weight')
+    for t in (bn.running_mean, bn.running_var):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.device != x.device:
+            raise NotImplementedError('yolact_amd batch_norm_act: running statistics that are not contiguous fp32 on the device of x '
+                                      'are not supported')
+    y = BnAct.apply(stats, bool(relu), float(bn.eps), float(bn.momentum), bn.running_mean, bn.running_var, x, residual, bn.weight,
+                    bn.bias)
+    if stats:
+        with torch.no_grad():
+            bn.num_batches_tracked += 1
+        for t in (bn.running_mean, bn.running_var):        # written by the kernel: tell autograd's version check, as an in-place op does
+            torch.autograd.graph.increment_version(t)
+    return y
+
+
+def check_bottleneck(block, name='block'):
+    """NotImplementedError naming what of a backbone block the kernels do not take."""
+    from .. import modules as M
+    if not isinstance(block, M.Bottleneck):
+        raise NotImplementedError('yolact_amd bottleneck: %s is a %s, which is not supported (a Bottleneck is)' % (name, type(block).__name__))
+    if block.use_dcn or not isinstance(block.conv2, torch.nn.Conv2d):
+        raise NotImplementedError('yolact_amd bottleneck: %s is a DCN block (use_dcn = True), which is not supported yet' % name)
+    convs = [('conv1', block.conv1, 1, 1), ('conv2', block.conv2, 3, block.stride), ('conv3', block.conv3, 1, 1)]
+    if block.downsample is not None:
+        convs.append(('downsample.0', block.downsample[0], 1, block.stride))
+    for n, m, k, st in convs:
+        if (tuple(m.kernel_size), tuple(m.stride), tuple(m.padding), tuple(m.dilation), m.groups, m.bias is None) != \
+                ((k, k), (st, st), (k // 2, k // 2), (1, 1), 1, True):
+            raise NotImplementedError('yolact_amd bottleneck: %s.%s = %r is not supported (a bias-free %d x %d / stride %d / padding %d '
+                                      'is)' % (name, n, m, k, k, st, k // 2))
+        check_plain(m.weight, st, 'bottleneck %s.%s' % (name, n))
+
+
+def bottleneck(x, block, batch_stats=None):
+    """backbone.py:37-57 on NHWC x: relu(bn1(conv1 x)), relu(bn2(conv2 .)), relu(bn3(conv3 .) + (downsample(x) or x))."""
+    L.require_cuda(x, 'bottleneck x')
+    check_bottleneck(block)
+    out = batch_norm_act(conv2d_plain(x, block.conv1.weight), block.bn1, batch_stats, relu=True)
+    out = batch_norm_act(conv2d_plain(out, block.conv2.weight, block.stride), block.bn2, batch_stats, relu=True)
+    out = conv2d_plain(out, block.conv3.weight)
+    res = x
+    if block.downsample is not None:
+        res = batch_norm_act(conv2d_plain(x, block.downsample[0].weight, block.stride), block.downsample[1], batch_stats)
+    return batch_norm_act(out, block.bn3, batch_stats, residual=res, relu=True)

@@ -557,6 +557,35 @@ class Yolact(nn.Module):
                 out.append(TO.conv2d_down(out[-1], down.weight, down.bias))
         return [o.permute(0, 3, 1, 2) for o in out]
 
+    def forward_backbone(self, x, batch_stats=None):
+        """The reference's ResNetBackbone.forward behind the stem (backbone.py:135-142): x [B,64,h,w] NCHW fp32 on the GPU, the
+        max-pool's output -> the four stage outputs [B,256 .. 2048,h_i,w_i].  Each result is a permuted view of NHWC storage, so
+        forward_fpn([outs[i] for i in cfg.backbone.selected_layers]) copies nothing.  Once differentiable in x, in every convolution of
+        backbone.layers and in the BatchNorm affine parameters that require grad (layers/train_ops.py on the HIP kernels).
+        batch_stats None follows each BatchNorm's own .training (False while the model is in eval mode: the reference's freeze_bn());
+        True normalises with the batch statistics and updates the running ones.  Needs no plan; the model stays in eval mode and
+        forward() is untouched.  A DarkNet backbone or a DCN block raises NotImplementedError naming it."""
+        from .layers import train_ops as TO
+        from .modules import ResNetBackbone
+        if not isinstance(self.backbone, ResNetBackbone):
+            raise NotImplementedError('yolact_amd forward_backbone: a %s is not supported (a ResNetBackbone is)'
+                                      % type(self.backbone).__name__)
+        for si, layer in enumerate(self.backbone.layers):
+            for bi, block in enumerate(layer):
+                TO.check_bottleneck(block, 'backbone.layers.%d.%d' % (si, bi))
+        L.require_cuda(x, 'forward_backbone stem map')
+        cin = self.backbone.layers[0][0].conv1.in_channels
+        if x.dim() != 4 or x.shape[1] != cin:
+            raise ValueError('forward_backbone: expected the stem\'s output [B,%d,h,w], got %s' % (cin, tuple(x.shape)))
+        x = x.to(torch.float32).permute(0, 2, 3, 1).contiguous()
+        outs = []
+        with torch.cuda.device(x.device):
+            for layer in self.backbone.layers:
+                for block in layer:
+                    x = TO.bottleneck(x, block, batch_stats)
+                outs.append(x.permute(0, 3, 1, 2))
+        return outs
+
     def forward_raw(self, x):
         """Head outputs before Detect (for parity tests): loc, conf (logits), mask, priors, proto — clones."""
         L.require_cuda(x, 'input batch')
