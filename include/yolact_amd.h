@@ -943,6 +943,24 @@ typedef struct ymi_chain_desc {
 } ymi_chain_desc;
 int ymi_pointwise_chain_f32(const ymi_chain_desc *d, void *stream);
 
+/* -- the EXIT of the first ResNet stage in one launch (csrc/chain.hip, chain_h2_k<128>; additive within ABI 9) ---------------------
+ *     y = act_a(scale_a * (W_a x) + bias_a + res)      conv3 + bn3 + shortcut + ReLU of the stage's last Bottleneck (64 -> 256)
+ *     z = act_b(scale_b * (W_b y) + bias_b)            conv1 + bn1 + ReLU of the next stage's first Bottleneck    (256 -> 128)
+ * `chain` is read as in ymi_pointwise_chain_f32 with (k_a, n_a, n_b) = (64, 256, 128) and z REQUIRED (gain_a / bias_max_a /
+ * res_amax are ignored).  chain.M == B * H * W.  y_stride = 1: y is stored for every pixel; y_stride = 2: a row of y is stored
+ * only where h % 2 == 0 && w % 2 == 0 — what a 1x1 stride-2 reader (the next stage's projection shortcut) touches — and the other
+ * rows of y are NOT WRITTEN AT ALL.  Either way y_amax bounds y over EVERY pixel and z (with z_amax) is written for every pixel.
+ * ALIASING: z must not overlap x, res or y; there is no in-place form (z is wider than x).  y must not overlap x or res.
+ * Codes: NULL descriptor / pointer -> YMI_ENULL; (k_a, n_a, n_b) != (64, 256, 128), y_stride not 1 or 2, M != B*H*W, an unknown
+ * activation -> YMI_EARG; row pitches / 16-byte alignment / 32-bit offsets / filter-plane rows -> YMI_ESHAPE.
+ * LIMIT: M * max(H, W) < 2^32, otherwise YMI_ESHAPE (the kernel finds a row's (h, w) by a 32-bit reciprocal multiplication that is
+ * exact only below that; 16 x 138 x 138 x 138 = 4.2e7). */
+typedef struct ymi_stage_exit_desc {
+  ymi_chain_desc chain;
+  int32_t B, H, W, y_stride;
+} ymi_stage_exit_desc;
+int ymi_stage_exit_chain_f32(const ymi_stage_exit_desc *d, void *stream);
+
 /* -- native plan executor (ABI 7; csrc/plan_exec.cpp) ----------------------------------------------------------------------------
  * The engine's execution plan is a flat list of the calls above on two HIP streams (A = the caller's stream, B = a side stream
  * for the small P4..P7 / Detect / projection-shortcut launches) with record / wait markers between them.  ymi_plan_run walks ops
@@ -953,14 +971,15 @@ int ymi_pointwise_chain_f32(const ymi_chain_desc *d, void *stream);
  * per-kernel timing needs).  skip_sections: bit k set = ops whose `section` is k are skipped (bit YMI_SEC_PROTO: the protonet, when
  * cfg.eval_mask_branch is False).  On failure returns the failing call's code and, through failed_op, its index. */
 enum { YMI_OP_NOP = 0, YMI_OP_CONV = 1, YMI_OP_WINO = 2, YMI_OP_DCN = 3, YMI_OP_CHAIN = 4, YMI_OP_STEM = 5, YMI_OP_INPUT = 6,
-       YMI_OP_BILINEAR = 7, YMI_OP_MAXPOOL = 8, YMI_OP_BILINEAR_ADD = 9, YMI_OP_RECORD = 10, YMI_OP_WAIT = 11, YMI_OP_MEMSET = 12 };
+       YMI_OP_BILINEAR = 7, YMI_OP_MAXPOOL = 8, YMI_OP_BILINEAR_ADD = 9, YMI_OP_RECORD = 10, YMI_OP_WAIT = 11, YMI_OP_MEMSET = 12,
+       YMI_OP_STAGE_EXIT = 13 };
 enum { YMI_SEC_NONE = 0, YMI_SEC_BACKBONE = 1, YMI_SEC_FPN = 2, YMI_SEC_PROTO = 3, YMI_SEC_HEADS = 4 };
 typedef struct ymi_plan_op {
   int32_t kind;        /* YMI_OP_* */
   int32_t stream;      /* 0 = A, 1 = B */
   int32_t section;     /* YMI_SEC_* (the reference's timer sections, yolact.py:570-607) */
   int32_t _pad;
-  const void *desc;    /* CONV / WINO / DCN / CHAIN / STEM: the call's descriptor */
+  const void *desc;    /* CONV / WINO / DCN / CHAIN / STEM / STAGE_EXIT: the call's descriptor */
   void *p[3];          /* pointer arguments of the descriptor-less calls (see csrc/plan_exec.cpp) */
   int64_t i[8];        /* their integer arguments; RECORD / WAIT: i[0] = event index; MEMSET: i[0] = bytes */
   double f[2];         /* BILINEAR: scale_h, scale_w */

@@ -8,6 +8,10 @@ rotating buffer sets (3 x 390 MB: nothing survives in the 256 MB memory-side cac
 the operands were written by the previous layer and everything else has passed through since), and prints the bytes per second of
 the launch's algorithmic traffic.  The two launches of the plan it replaces: layer0.N.conv3 0.083 + layer0.(N+1).conv1 0.055 ms
 in the step (profiles/r04_layers.txt), 0.0745 + 0.035 ms alone on resident buffers (profiles/r04_ws_probe.txt).
+
+Then the stage EXIT (ymi_stage_exit_chain_f32: layer0.2.conv3 + residual -> layer1.0.conv1, 256 -> 128, y stored at even rows and
+columns only) next to the two launches it replaces: the chain kernel without its second layer ('chain1') and the plan's 1x1
+256 -> 128 convolution on the tile the shipped table gives that shape; same rotating buffer sets.
 """
 import argparse
 import ctypes as C
@@ -70,6 +74,59 @@ def main():
             e1.synchronize()
             best = min(best, e0.elapsed_time(e1) / args.reps)
         nbytes = 4.0 * M * (64 + 256 + (256 if with_res else 0) + (64 if two else 0))
+        print('%-30s M=%d  %.4f ms  %6.1f MB  %.2f TB/s' % (name, M, best, nbytes / 1e6, nbytes / best / 1e9))
+
+    # ---- the stage exit against the two launches it replaces
+    from yolact_amd.engine import load_tune_table
+    B, H, W = args.batch, 138, 138
+    wx = torch.randn(128, 256, 1, 1, generator=g) / 16
+    px = Packed(wx, torch.randn(128, generator=g), None, 1, 0, None, dev)
+    plx, scx, winvx = px.h2()
+    zs = [torch.empty(M, 128, device=dev) for _ in range(args.sets)]
+
+    def conv1_desc(k):
+        d = L.ConvDesc()
+        d.x, d.w, d.bias = sets[k][2].data_ptr(), px.w.data_ptr(), px.bias.data_ptr()
+        d.scale = px.scale.data_ptr() if px.scale is not None else None
+        d.B, d.H, d.W, d.Cin, d.ldx, d.Ho, d.Wo, d.Cout = B, H, W, 256, 256, H, W, 128
+        d.kh, d.kw, d.stride, d.pad, d.Kpad, d.cin_alg, d.cout_alg = 1, 1, 1, 0, px.Kpad, px.cin_alg, px.cout_alg
+        d.nseg = 1
+        d.seg[0] = L.ConvSeg(0, 128, L.ACT_RELU, 128, H * W * 128, zs[k].data_ptr())
+        d.x_amax, d.y_amax = amax.data_ptr() + 4096, amax.data_ptr() + 8192
+        d.w_h2, d.scale_h2, d.winv_h2 = plx.data_ptr(), scx.data_ptr(), winvx.data_ptr()
+        val = load_tune_table(dev).get(str((B, H, W, 256, 128, 1, 1, 1, 0, 0, 1, 256)) + '|h2')
+        d.tile = (int(val) & 255) if val is not None else L.TILE_AUTO
+        return d
+
+    def exit_desc(k, y_stride):
+        e = L.StageExitDesc()
+        e.chain = desc(k, False, True)           # (a copy: conv3 + residual as in the arms above)
+        c = e.chain
+        c.n_b, c.z, c.ldz, c.z_amax = 128, zs[k].data_ptr(), 128, amax.data_ptr() + 8192
+        c.w_b_h2, c.scale_b_h2, c.bias_b, c.cout_pad_b = plx.data_ptr(), scx.data_ptr(), px.bias.data_ptr(), px.CoutPad
+        e.B, e.H, e.W, e.y_stride = B, H, W, y_stride
+        return e
+    c3 = [desc(k, False, True) for k in range(args.sets)]
+    c1 = [conv1_desc(k) for k in range(args.sets)]
+    arms = [('chain1 (conv3 + residual)', lambda k: lib.ymi_pointwise_chain_f32(C.byref(c3[k]), s), 4.0 * M * (64 + 256 + 256)),
+            ('layer1.0.conv1 (tile %d)' % (c1[0].tile & 255), lambda k: lib.ymi_conv2d_nhwc_f32(C.byref(c1[k]), s), 4.0 * M * (256 + 128)),
+            ('chain1, then conv1', lambda k: (lib.ymi_pointwise_chain_f32(C.byref(c3[k]), s), lib.ymi_conv2d_nhwc_f32(C.byref(c1[k]), s))[1],
+             4.0 * M * (64 + 256 + 256 + 256 + 128))]
+    for ys in (2, 1):
+        xs = [exit_desc(k, ys) for k in range(args.sets)]
+        arms.append(('stage exit, y_stride %d' % ys, (lambda k, xs=xs: lib.ymi_stage_exit_chain_f32(C.byref(xs[k]), s)),
+                     4.0 * M * (64 + 256 + 128) + 4.0 * B * ((H + ys - 1) // ys) * ((W + ys - 1) // ys) * 256))
+    for name, run, nbytes in arms:
+        for k in range(args.sets):
+            L.check(run(k))
+        best = 1e30
+        for _ in range(3):
+            e0.record()
+            for r in range(args.reps):
+                run(r % args.sets)
+            e1.record()
+            e1.synchronize()
+            best = min(best, e0.elapsed_time(e1) / args.reps)
         print('%-30s M=%d  %.4f ms  %6.1f MB  %.2f TB/s' % (name, M, best, nbytes / 1e6, nbytes / best / 1e9))
 
 

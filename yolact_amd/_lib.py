@@ -242,6 +242,10 @@ class ChainDesc(C.Structure):
                 ('res_amax', C.c_void_p), ('gain_a', C.c_float), ('bias_max_a', C.c_float)]
 
 
+class StageExitDesc(C.Structure):
+    _fields_ = [('chain', ChainDesc), ('B', C.c_int32), ('H', C.c_int32), ('W', C.c_int32), ('y_stride', C.c_int32)]
+
+
 class StemDesc(C.Structure):
     _fields_ = [('x', C.c_void_p), ('y', C.c_void_p), ('B', C.c_int32), ('H', C.c_int32), ('W', C.c_int32), ('cout_pad', C.c_int32),
                 ('w_h2', C.c_void_p), ('scale_h2', C.c_void_p), ('bias', C.c_void_p), ('y_amax', C.c_void_p),
@@ -254,7 +258,7 @@ class PlanOp(C.Structure):
 
 
 (OP_NOP, OP_CONV, OP_WINO, OP_DCN, OP_CHAIN, OP_STEM, OP_INPUT, OP_BILINEAR, OP_MAXPOOL, OP_BILINEAR_ADD, OP_RECORD, OP_WAIT,
- OP_MEMSET) = range(13)
+ OP_MEMSET, OP_STAGE_EXIT) = range(14)
 SEC_NONE, SEC_BACKBONE, SEC_FPN, SEC_PROTO, SEC_HEADS = range(5)
 
 
@@ -348,6 +352,7 @@ SYMBOLS = [
     ('ymi_ap_finalize_f64', C.c_int, [C.POINTER(ApFinalizeDesc), _P]),
     ('ymi_stem_pool_f32', C.c_int, [_P, _P]),
     ('ymi_pointwise_chain_f32', C.c_int, [_P, _P]),
+    ('ymi_stage_exit_chain_f32', C.c_int, [_P, _P]),
     ('ymi_mask_rle_f32', C.c_int, [_P, _I, _I, _I, _P, _P, _I, _P]),
     ('ymi_mask_rle_upsampled_f32', C.c_int, [_P, _I, _I, _I, _I, _I, _F, _P, _P, _I, _P]),
     ('ymi_rle_to_string', C.c_int, [_P, _P, _I, _I, _P, _P, _I, _P]),

@@ -34,7 +34,7 @@ using namespace ymi_h2;
 
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int K1 = 64, N1 = 256, N2 = 64, PX = 32, NW = 8;
+constexpr int K1 = 64, N1 = 256, PX = 32, NW = 8;
 constexpr int RS1 = 2 * K1 + 16;          // bytes per LDS row of a K = 64 plane (128 + 16: the 16 lanes of a read phase hit 16 bank groups)
 constexpr int RS2 = 2 * N1 + 16;          // ... of a K = 256 plane
 constexpr int A1_PLANE = PX * RS1, A2_PLANE = PX * RS2;
@@ -43,6 +43,11 @@ constexpr int A1_PLANE = PX * RS1, A2_PLANE = PX * RS2;
 constexpr int A1_BUF = 2 * A1_PLANE, A2_BUF = 2 * A2_PLANE;
 constexpr int OFF_A1 = 0, OFF_A2 = OFF_A1 + 2 * A1_BUF, OFF_SC = OFF_A2 + 2 * A2_BUF, OFF_EP = OFF_SC + 2 * (2 * NW * 4),
               CH_LDS = OFF_EP + NW * 2 * 4 * 32;   // OFF_EP: conv3's per-lane epilogue constants (scale, bias) x (wave, j, g)
+// N2 = 128 (the stage exit, see below): the second layer's per-lane epilogue constants live in LDS too, (scale, bias) x (wave, tt, g)
+// and so does the LOW plane of its filters (64 KB, in fragment order: 1 KB = the 64 lanes' 16 bytes of one (16-channel tile,
+// 32-deep chunk), conflict-free ds_read_b128): with both planes in registers the kernel needs 256 VGPRs + 156 bytes of scratch
+constexpr int OFF_EP2 = CH_LDS, OFF_WL = OFF_EP2 + NW * 2 * 4 * 32, CH_LDS_X = OFF_WL + 128 * N1 * 2;
+static_assert(CH_LDS_X <= 160 * 1024, "LDS of a CU");
 
 struct ChainParams {
   const float *x, *res, *x_amax;
@@ -52,10 +57,34 @@ struct ChainParams {
   int M, ldx, res_ld, ldy, ldz, act_a, act_b;
   unsigned wa_plane, wb_plane;            // bytes per plane
 };
+// N2 = 128 (a type of its own: the 64-wide kernel keeps its kernel-argument layout, hence its code): y is stored only at pixels with
+// h % y_stride == 0 && w % y_stride == 0 (M == B H W); mag_w / mag_h = ceil(2^32 / W), ceil(2^32 / H): m / W == (m * mag_w) >> 32
+// exactly for every m with m * W < 2^32 (the error term is m * (W * mag_w - 2^32) / (W * 2^32) < m / 2^32, which must stay below
+// 1 / W), and (m / W) / H likewise while (m / W) * H < 2^32: the entry point refuses shapes with M * max(H, W) >= 2^32
+struct ChainParamsX : ChainParams {
+  unsigned long long mag_w, mag_h;
+  int H, W, y_stride;
+};
 
-__global__ __launch_bounds__(64 * NW) void chain_h2_k(const ChainParams p) {
+// N2 = the second layer's width.  64: the pair inside the stage (above; this instantiation's ISA is the untemplated kernel's,
+// instruction for instruction).  128: the stage EXIT, layer0.2.conv3 -> layer1.0.conv1 (256 -> 128, ymi_stage_exit_chain_f32): wave
+// (q, i) owns z channels 32 q .. 32 q + 31 of half i — NT = 2 sixteen-channel tiles that share the y fragments read from LDS (48
+// MFMAs per wave per tile in GEMM 2 instead of 24, the reads of the y planes unchanged) — and y is stored only where the stride-2
+// projection shortcut of the next stage reads it (ChainParamsX::y_stride; the bound y_amax still covers EVERY pixel, so that
+// launch's fp16x2 scale, hence its output, does not move).  Same loop: per-slice scales, one barrier per iteration, two buffers,
+// unconditional buffer operations.
+// Registers (8 waves per CU = 2 per SIMD: 256 per lane; hipcc 7.2 -Rpass-analysis=kernel-resource-usage):
+//     N2 =  64                                    246 VGPRs, 0 AGPRs, no scratch,  88 192 B of LDS
+//     N2 = 128, both planes of conv1 in registers 256 VGPRs, 0 AGPRs, 156 B of scratch per lane      (not shipped)
+//     N2 = 128, conv1's LOW plane in LDS          238 VGPRs, 0 AGPRs, no scratch, 155 776 B of LDS   (shipped)
+// 32 + 128 filter registers fit on paper, but next to the two residual sets (32), the accumulators and the addresses the allocator
+// spills 39 of them; the low plane (one of three products) costs 16 conflict-free ds_read_b128 per wave per 32 pixels instead.
+template <int N2>
+__global__ __launch_bounds__(64 * NW) void chain_h2_k(const std::conditional_t<N2 == 128, ChainParamsX, ChainParams> p) {
 #if defined(__HIP_DEVICE_COMPILE__)
-  __shared__ __attribute__((aligned(16))) char lds[CH_LDS];
+  constexpr int NT = N2 / 64;                          // 16-channel tiles of z per wave
+  constexpr bool EXIT = N2 == 128;
+  __shared__ __attribute__((aligned(16))) char lds[EXIT ? CH_LDS_X : CH_LDS];
   const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
   const int lr = lane & 15, g = lane >> 4;
   const int q2 = wave & 3, i2 = wave >> 2;             // GEMM 2: this wave's 16 z channels (16 q2 ..) and 16-pixel half of the tile
@@ -67,7 +96,7 @@ __global__ __launch_bounds__(64 * NW) void chain_h2_k(const ChainParams p) {
 
   // ---- this wave's filters -> REGISTERS, once: as MFMA A-operand fragments (row = output channel lr of a 16-channel tile, 8
   // consecutive k at 8 g of a 32-deep chunk).  GEMM 1: channels 32 wave + 16 j + lr, chunks 0 / 1; GEMM 2: channels 16 q2 + lr, chunks 0 .. 7
-  f16x8 w3h[2][2], w3l[2][2], w1h[8], w1l[8];
+  f16x8 w3h[2][2], w3l[2][2], w1h[NT][8], w1l[EXIT ? 1 : NT][EXIT ? 1 : 8];
 #pragma unroll
   for (int j = 0; j < 2; ++j)
 #pragma unroll
@@ -77,11 +106,22 @@ __global__ __launch_bounds__(64 * NW) void chain_h2_k(const ChainParams p) {
       w3l[j][c] = *reinterpret_cast<const f16x8 *>(src + p.wa_plane);
     }
 #pragma unroll
-  for (int c = 0; c < 8; ++c) {
-    const f16x8 z8 = {0, 0, 0, 0, 0, 0, 0, 0};
-    const char *src = reinterpret_cast<const char *>(p.wb) + (size_t)(16 * q2 + lr) * (2 * N1) + c * 64 + g * 16;
-    w1h[c] = two ? *reinterpret_cast<const f16x8 *>(src) : z8;
-    w1l[c] = two ? *reinterpret_cast<const f16x8 *>(src + p.wb_plane) : z8;
+  for (int tt = 0; tt < NT; ++tt)
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+      const f16x8 z8 = {0, 0, 0, 0, 0, 0, 0, 0};
+      const char *src = reinterpret_cast<const char *>(p.wb) + (size_t)(16 * NT * q2 + 16 * tt + lr) * (2 * N1) + c * 64 + g * 16;
+      w1h[tt][c] = two ? *reinterpret_cast<const f16x8 *>(src) : z8;
+      if constexpr (!EXIT) w1l[tt][c] = two ? *reinterpret_cast<const f16x8 *>(src + p.wb_plane) : z8;
+    }
+  if constexpr (EXIT) {                                // the low plane -> LDS, fragment order; published by the first iteration's barrier
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {                      // chunk (tile16 = k, c = t >> 6, lane = t & 63)
+      const int c = t >> 6;
+      const char *src = reinterpret_cast<const char *>(p.wb) + p.wb_plane + (size_t)(16 * k + lr) * (2 * N1) + c * 64 + g * 16;
+      const f16x8 z8 = {0, 0, 0, 0, 0, 0, 0, 0};
+      *reinterpret_cast<f16x8 *>(lds + OFF_WL + ((k * 8 + c) * 64 + lane) * 16) = two ? *reinterpret_cast<const f16x8 *>(src) : z8;
+    }
   }
   // per-lane epilogue constants: channels 32 wave + 16 j + 4 g .. + 3 of conv3, 16 q2 + 4 g .. + 3 of conv1
   // (conv3's live in LDS, 32 bytes per (wave, j, g), and are re-read in every epilogue: 16 registers the filter fragments need)
@@ -97,7 +137,21 @@ __global__ __launch_bounds__(64 * NW) void chain_h2_k(const ChainParams p) {
     }
   }
   f32x4 sc1 = {1.f, 1.f, 1.f, 1.f}, bi1 = {0.f, 0.f, 0.f, 0.f};
-  if (two) {
+  if constexpr (EXIT) {                                // (the registers belong to the filter fragments: constants in LDS, as conv3's)
+    if (lr == 0) {
+#pragma unroll
+      for (int tt = 0; tt < NT; ++tt) {
+        const int n = 16 * NT * q2 + 16 * tt + 4 * g;
+        f32x4 sc = sc1, bi = bi1;
+        if (two) {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) { sc[e] = p.sb[n + e]; bi[e] = p.bb ? p.bb[n + e] : 0.f; }
+        }
+        *reinterpret_cast<f32x4 *>(lds + OFF_EP2 + ((wave * 2 + tt) * 4 + g) * 32) = sc;
+        *reinterpret_cast<f32x4 *>(lds + OFF_EP2 + ((wave * 2 + tt) * 4 + g) * 32 + 16) = bi;
+      }
+    }
+  } else if (two) {
 #pragma unroll
     for (int e = 0; e < 4; ++e) { sc1[e] = p.sb[16 * q2 + 4 * g + e]; bi1[e] = p.bb ? p.bb[16 * q2 + 4 * g + e] : 0.f; }
   }
@@ -170,33 +224,66 @@ __global__ __launch_bounds__(64 * NW) void chain_h2_k(const ChainParams p) {
     if (two) {
       // P4 (tile k - 1): GEMM 2 for pixels 16 i2 + lr, z channels 16 q2 ..: the K = 256 sum one 32-channel slice (one producing
       // wave, one scale) at a time
-      f32x4 tot = {0.f, 0.f, 0.f, 0.f};
+      f32x4 tot[NT];
+#pragma unroll
+      for (int tt = 0; tt < NT; ++tt) tot[tt] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int c0 = 0; c0 < 8; c0 += 2) {               // two slices at a time: two independent accumulators interleaved
         f16x8 xh[2], xl[2];
-        f32x4 a2[2];
+        f32x4 a2[2][NT];
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
           xh[u] = *reinterpret_cast<const f16x8 *>(a2r + (16 * i2 + lr) * RS2 + (c0 + u) * 64 + g * 16);
           xl[u] = *reinterpret_cast<const f16x8 *>(a2r + A2_PLANE + (16 * i2 + lr) * RS2 + (c0 + u) * 64 + g * 16);
-          a2[u] = f32x4{0.f, 0.f, 0.f, 0.f};
-        }
 #pragma unroll
-        for (int pr = 0; pr < 3; ++pr)
+          for (int tt = 0; tt < NT; ++tt) a2[u][tt] = f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+        if constexpr (EXIT) {
+          f16x8 wl[2][NT];
 #pragma unroll
           for (int u = 0; u < 2; ++u)
-            a2[u] = ymi_mfma16(pr == 0 ? w1l[c0 + u] : w1h[c0 + u], pr == 1 ? xl[u] : xh[u], a2[u]);
 #pragma unroll
-        for (int u = 0; u < 2; ++u) tot += a2[u] * scr[i2 * NW + c0 + u];
+            for (int tt = 0; tt < NT; ++tt)
+              wl[u][tt] = *reinterpret_cast<const f16x8 *>(lds + OFF_WL + ((((NT * q2 + tt) * 8) + c0 + u) * 64 + lane) * 16);
+#pragma unroll
+          for (int pr = 0; pr < 3; ++pr)
+#pragma unroll
+            for (int u = 0; u < 2; ++u)
+#pragma unroll
+              for (int tt = 0; tt < NT; ++tt)
+                a2[u][tt] = ymi_mfma16(pr == 0 ? wl[u][tt] : w1h[tt][c0 + u], pr == 1 ? xl[u] : xh[u], a2[u][tt]);
+        } else {
+#pragma unroll
+          for (int pr = 0; pr < 3; ++pr)
+#pragma unroll
+            for (int u = 0; u < 2; ++u)
+#pragma unroll
+              for (int tt = 0; tt < NT; ++tt)
+                a2[u][tt] = ymi_mfma16(pr == 0 ? w1l[tt][c0 + u] : w1h[tt][c0 + u], pr == 1 ? xl[u] : xh[u], a2[u][tt]);
+        }
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+          const float isc = scr[i2 * NW + c0 + u];
+#pragma unroll
+          for (int tt = 0; tt < NT; ++tt) tot[tt] += a2[u][tt] * isc;
+        }
       }
       // P5: epilogue 2
       const int tp = tile - grid, m = tp * PX + 16 * i2 + lr;
       const bool ok = tp >= 0 && m < p.M;
-      f32x4 v = tot * sc1 + bi1;
 #pragma unroll
-      for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], slope_b * v[e]);
-      am_z = fmaxf(am_z, ok ? ymi_absmax4(v) : 0.f);
-      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), zrs, ok ? (unsigned)(m * p.ldz + 16 * q2 + 4 * g) * 4u : OOB, 0, 0);
+      for (int tt = 0; tt < NT; ++tt) {
+        if constexpr (EXIT) {
+          sc1 = *reinterpret_cast<const f32x4 *>(lds + OFF_EP2 + ((wave * 2 + tt) * 4 + g) * 32);
+          bi1 = *reinterpret_cast<const f32x4 *>(lds + OFF_EP2 + ((wave * 2 + tt) * 4 + g) * 32 + 16);
+        }
+        f32x4 v = tot[tt] * sc1 + bi1;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], slope_b * v[e]);
+        am_z = fmaxf(am_z, ok ? ymi_absmax4(v) : 0.f);
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), zrs,
+                                               ok ? (unsigned)(m * p.ldz + 16 * NT * q2 + 16 * tt + 4 * g) * 4u : OOB, 0, 0);
+      }
     }
     // P2 (tile k): GEMM 1 — both 16-pixel halves x this wave's two 16-channel tiles
     f32x4 acc[2][2];
@@ -225,7 +312,14 @@ __global__ __launch_bounds__(64 * NW) void chain_h2_k(const ChainParams p) {
     for (int i = 0; i < 2; ++i) {
       const int m = tile * PX + 16 * i + lr;
       const bool ok = m < p.M;
-      const unsigned yoff = ok ? (unsigned)(m * p.ldy + 32 * wave + 4 * g) * 4u : OOB;
+      bool keep = ok;
+      if constexpr (EXIT) {                             // y only where the stride-2 reader looks (no branch: the OOB offset again)
+        const unsigned r = (unsigned)(((unsigned long long)(unsigned)m * p.mag_w) >> 32);          // m / W = b H + h
+        const unsigned w = (unsigned)m - r * (unsigned)p.W;
+        const unsigned h = r - (unsigned)(((unsigned long long)r * p.mag_h) >> 32) * (unsigned)p.H;
+        keep = ok && (p.y_stride == 1 || ((h | w) & 1u) == 0);
+      }
+      const unsigned yoff = keep ? (unsigned)(m * p.ldy + 32 * wave + 4 * g) * 4u : OOB;
       float tm = 0.f;
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
@@ -287,7 +381,7 @@ extern "C" int ymi_pointwise_chain_f32(const ymi_chain_desc *d, void *stream) {
   if (!d->x || !d->w_a_h2 || !d->scale_a_h2 || !d->y || !d->x_amax) return YMI_ENULL;
   if (d->z && (!d->w_b_h2 || !d->scale_b_h2)) return YMI_ENULL;
   const bool wide = d->k_a == 128 || d->k_a == 256;
-  if (d->M <= 0 || (!wide && (d->k_a != K1 || d->n_a != N1 || (d->z && d->n_b != N2)))) return YMI_EARG;
+  if (d->M <= 0 || (!wide && (d->k_a != K1 || d->n_a != N1 || (d->z && d->n_b != 64)))) return YMI_EARG;
   if (wide && (d->n_a != 4 * d->k_a || (d->z && d->n_b != d->k_a))) return YMI_EARG;
   if (d->act_a < 0 || d->act_a > YMI_ACT_LEAKY01 || d->act_b < 0 || d->act_b > YMI_ACT_LEAKY01) return YMI_EARG;
   if (d->ldx < d->k_a || d->ldy < d->n_a || (d->z && d->ldz < d->n_b) || (d->res && d->res_ld < d->n_a)) return YMI_ESHAPE;
@@ -296,7 +390,7 @@ extern "C" int ymi_pointwise_chain_f32(const ymi_chain_desc *d, void *stream) {
     return YMI_ESHAPE;
   if (d->M * (int64_t)(d->ldy > d->res_ld ? d->ldy : d->res_ld) >= (1LL << 29) || d->M * (int64_t)d->ldx >= (1LL << 29)) return YMI_ESHAPE;   // 32-bit buffer offsets
   if (wide) return ymi_internal_chain2(d, (hipStream_t)stream);
-  if (d->cout_pad_a < N1 || (d->z && d->cout_pad_b < N2)) return YMI_ESHAPE;
+  if (d->cout_pad_a < N1 || (d->z && d->cout_pad_b < 64)) return YMI_ESHAPE;
   ChainParams p;
   p.x = d->x; p.res = d->res; p.x_amax = d->x_amax; p.wa = d->w_a_h2; p.wb = d->w_b_h2;
   p.sa = d->scale_a_h2; p.ba = d->bias_a; p.sb = d->scale_b_h2; p.bb = d->bias_b;
@@ -309,11 +403,56 @@ extern "C" int ymi_pointwise_chain_f32(const ymi_chain_desc *d, void *stream) {
   hipGetDevice(&dev);
   hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
   const long ntiles = (d->M + PX - 1) / PX;
-  hipLaunchKernelGGL(chain_h2_k, dim3((unsigned)(ntiles < cus ? ntiles : cus)), dim3(64 * NW), 0, s, p);
+  hipLaunchKernelGGL(chain_h2_k<64>, dim3((unsigned)(ntiles < cus ? ntiles : cus)), dim3(64 * NW), 0, s, p);
   const int rc = ymi_launch_status();
   ymi_internal_prof_end(pr, s);
   if (rc == YMI_OK && d->z) {
-    const int p2 = ymi_internal_prof_begin(2.0 * (double)d->M * N1 * N2, YMI_TILE_H2 | YMI_TILE_64x64, 12, s);
+    const int p2 = ymi_internal_prof_begin(2.0 * (double)d->M * N1 * 64, YMI_TILE_H2 | YMI_TILE_64x64, 12, s);
+    ymi_internal_prof_end(p2, s);
+  }
+  return rc;
+}
+
+// The stage exit (include/yolact_amd.h, ymi_stage_exit_desc): y = act_a(scale_a * (W_a x) + bias_a + res) of layer0.2.conv3, stored
+// only where the stride-2 shortcut of the next stage reads it, and z = act_b(scale_b * (W_b y) + bias_b) of layer1.0.conv1
+// (256 -> 128) from the y tile in LDS.  Profiling records as the chain's: kind 13 (conv3's FLOPs), then kind 12 (conv1's).
+extern "C" int ymi_stage_exit_chain_f32(const ymi_stage_exit_desc *e, void *stream) {
+  if (!e) return YMI_ENULL;
+  const ymi_chain_desc *d = &e->chain;
+  if (!d->x || !d->w_a_h2 || !d->scale_a_h2 || !d->y || !d->x_amax || !d->z || !d->w_b_h2 || !d->scale_b_h2) return YMI_ENULL;
+  if (d->k_a != K1 || d->n_a != N1 || d->n_b != 128 || (e->y_stride != 1 && e->y_stride != 2)) return YMI_EARG;
+  if (d->M <= 0 || e->B <= 0 || e->H <= 0 || e->W <= 0 || d->M != (int64_t)e->B * e->H * e->W) return YMI_EARG;
+  if (d->act_a < 0 || d->act_a > YMI_ACT_LEAKY01 || d->act_b < 0 || d->act_b > YMI_ACT_LEAKY01) return YMI_EARG;
+  if (d->ldx < K1 || d->ldy < N1 || d->ldz < 128 || (d->res && d->res_ld < N1)) return YMI_ESHAPE;
+  if ((d->ldx | d->ldy | d->ldz | d->res_ld) & 3) return YMI_ESHAPE;
+  if ((((uintptr_t)d->x) | ((uintptr_t)d->y) | ((uintptr_t)d->z) | ((uintptr_t)d->res) | ((uintptr_t)d->w_a_h2) | ((uintptr_t)d->w_b_h2)) & 15)
+    return YMI_ESHAPE;
+  const int64_t ldmax = d->ldy > d->res_ld ? (d->ldy > d->ldz ? d->ldy : d->ldz) : (d->res_ld > d->ldz ? d->res_ld : d->ldz);
+  if (d->M * ldmax >= (1LL << 29) || d->M * (int64_t)d->ldx >= (1LL << 29)) return YMI_ESHAPE;    // 32-bit buffer offsets
+  if (d->cout_pad_a < N1 || d->cout_pad_b < 128) return YMI_ESHAPE;
+  // the kernel decodes (h, w) of row m by multiplication with ceil(2^32 / W) and ceil(2^32 / H): exact for every m < M and every
+  // m / W < B * H only while M * W < 2^32 and B * H * H < 2^32 (M alone bounds neither: a 10 x 100 000 map has M = 10^6)
+  if (d->M * (int64_t)(e->H > e->W ? e->H : e->W) >= (1LL << 32)) return YMI_ESHAPE;
+  ChainParamsX p;
+  p.x = d->x; p.res = d->res; p.x_amax = d->x_amax; p.wa = d->w_a_h2; p.wb = d->w_b_h2;
+  p.sa = d->scale_a_h2; p.ba = d->bias_a; p.sb = d->scale_b_h2; p.bb = d->bias_b;
+  p.y = d->y; p.z = d->z; p.y_amax = d->y_amax; p.z_amax = d->z_amax;
+  p.M = (int)d->M; p.ldx = d->ldx; p.res_ld = d->res_ld; p.ldy = d->ldy; p.ldz = d->ldz; p.act_a = d->act_a; p.act_b = d->act_b;
+  p.wa_plane = (unsigned)((long)d->cout_pad_a * K1 * 2); p.wb_plane = (unsigned)((long)d->cout_pad_b * N1 * 2);
+  p.H = e->H; p.W = e->W; p.y_stride = e->y_stride;
+  p.mag_w = ((1ULL << 32) + (unsigned)e->W - 1) / (unsigned)e->W;
+  p.mag_h = ((1ULL << 32) + (unsigned)e->H - 1) / (unsigned)e->H;
+  hipStream_t s = (hipStream_t)stream;
+  const int pr = ymi_internal_prof_begin(2.0 * (double)d->M * K1 * N1, YMI_TILE_H2 | YMI_TILE_64x64, 13, s);
+  int dev = 0, cus = 256;
+  hipGetDevice(&dev);
+  hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+  const long ntiles = (d->M + PX - 1) / PX;
+  hipLaunchKernelGGL(chain_h2_k<128>, dim3((unsigned)(ntiles < cus ? ntiles : cus)), dim3(64 * NW), 0, s, p);
+  const int rc = ymi_launch_status();
+  ymi_internal_prof_end(pr, s);
+  if (rc == YMI_OK) {
+    const int p2 = ymi_internal_prof_begin(2.0 * (double)d->M * N1 * 128, YMI_TILE_H2 | YMI_TILE_64x64, 12, s);
     ymi_internal_prof_end(p2, s);
   }
   return rc;

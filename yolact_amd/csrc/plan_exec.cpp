@@ -42,6 +42,7 @@ int ymi_plan_run(const ymi_plan_op *ops, int first, int last, void *stream_a, vo
       case YMI_OP_WINO: rc = ymi_conv3x3_winograd_f32((const ymi_wino_desc *)o.desc, s); break;
       case YMI_OP_DCN: rc = ymi_dcn_v2_forward_f32((const ymi_dcn_desc *)o.desc, s); break;
       case YMI_OP_CHAIN: rc = ymi_pointwise_chain_f32((const ymi_chain_desc *)o.desc, s); break;
+      case YMI_OP_STAGE_EXIT: rc = ymi_stage_exit_chain_f32((const ymi_stage_exit_desc *)o.desc, s); break;
       case YMI_OP_STEM: rc = ymi_stem_pool_f32((const ymi_stem_desc *)o.desc, s); break;
       case YMI_OP_INPUT:       /* p0 = x NCHW (patched per call), p1 = y NHWC4, p2 = amax slot or NULL; i = B, C, H, W */
         rc = o.p[2] ? ymi_nchw_to_nhwc4_amax_f32((const float *)o.p[0], (float *)o.p[1], (int)o.i[0], (int)o.i[1], (int)o.i[2], (int)o.i[3],

@@ -400,6 +400,25 @@ class Arena:
         return sum(b.numel() * 4 for b in self.all)
 
 
+def _desc_pointers(d):
+    """Every non-NULL pointer a ctypes descriptor holds, nested structures and arrays included (Plan.stage_exit_candidates: who else
+    names a buffer).  Walks `_fields_`, so it does not depend on what a pointer field is called."""
+    out = []
+    if isinstance(d, C.Array):
+        for e in d:
+            out += _desc_pointers(e) if isinstance(e, (C.Structure, C.Array)) else ([int(e)] if isinstance(e, int) and e else [])
+        return out
+    for f in d._fields_:
+        name, typ = f[0], f[1]
+        v = getattr(d, name)
+        if typ is C.c_void_p:
+            if v:
+                out.append(int(v))
+        elif isinstance(v, (C.Structure, C.Array)) and (issubclass(typ, C.Structure) or issubclass(getattr(typ, '_type_', int), (C.Structure, C.c_void_p))):
+            out += _desc_pointers(v)
+    return out
+
+
 def out_size(n, k, s, p):
     return (n + 2 * p - k) // s + 1
 
@@ -1136,6 +1155,8 @@ class Plan:
             self.call(lib.ymi_maxpool3x3s2_nhwc_f32, stem.ptr, x.ptr, stem.B, stem.H, stem.W, stem.C, Hp, Wp, name='maxpool')
             ar.free(stem)
         outs = []
+        self._stage_out_ptr = {}
+        held = []        # buffers of a stage's last block kept until the next block's conv1 output is allocated (see below)
         for li, layer in enumerate(bb.layers):
             for bi, blk in enumerate(layer):
                 nm = 'layer%d.%d' % (li, bi)
@@ -1150,6 +1171,9 @@ class Plan:
                     self.record(nm + '.down')
                     self.on('A')
                 o1 = self.conv(nm + '.conv1', x, self._pack(blk.conv1, blk.bn1), act=L.ACT_RELU)
+                for t in held:
+                    ar.free(t)
+                held = []
                 if blk.use_dcn:
                     dcn = blk.conv2
                     om = self.conv(nm + '.offmask', o1, pack_offmask(dcn.conv_offset_mask, dev, self.om_interleave) if self.om_pad
@@ -1168,21 +1192,35 @@ class Plan:
                     res = x
                 y = self.conv(nm + '.conv3', o2, self._pack(blk.conv3, blk.bn3), act=L.ACT_RELU, res=res,
                               res_mode=L.RES_ADD)
-                ar.free(o2)
+                # the exit of a 64-plane stage may become ONE launch with the next stage's conv1 (_fuse_stage_exit), which then
+                # writes that conv1's output while it still reads o2 and the residual: the best-fit arena must not hand conv1 a
+                # buffer that contains either, so both stay allocated until conv1's output exists.  UNCONDITIONAL on purpose (also
+                # with YOLACT_AMD_CHAIN_EXIT=0 or a table decision of 0, where it only keeps two buffers alive a little longer): the
+                # buffer layout of a plan must not depend on a table lookup or a switch that is read after the plan is built
+                hold = (self.h2 and bi == len(layer) - 1 and li + 1 < len(bb.layers) and blk.downsample is None
+                        and o2.C == 64 and y.C == 256)
+                if hold:
+                    held = [o2, x]
+                else:
+                    ar.free(o2)
                 if side_down:
                     self.on('B')          # back to the side stream's pool: its next op waits for a later event of A
                     self.free(res)
                     self.on('A')
                 elif res is not x:
                     ar.free(res)
-                ar.free(x)
+                if not hold:
+                    ar.free(x)
                 x = y
                 if bi == 0:                     # behind this stage's projection shortcut on B: the previous stages' FPN laterals
                     self._flush_early_laterals()
             # stage output: still needed by the FPN, so the next stage only borrows it
             outs.append(x)
+            self._stage_out_ptr[li] = x.ptr
             self._stage_done(li, x)
             x = _Borrowed(x)
+        for t in held:
+            ar.free(t)
         return outs
 
     def _darknet(self, bb: M.DarkNetBackbone, x4: T):
@@ -1299,7 +1337,8 @@ class Plan:
         arr[0].p[0], arr[0].i[0] = self.amax.data_ptr(), 4 * self._nslots * AMAX_SLOT_FLOATS
         ev_index, det_idx, in_idx, ok = {}, None, None, True
         by_fn = {id(lib.ymi_conv2d_nhwc_f32): L.OP_CONV, id(lib.ymi_conv3x3_winograd_f32): L.OP_WINO,
-                 id(lib.ymi_dcn_v2_forward_f32): L.OP_DCN, id(lib.ymi_pointwise_chain_f32): L.OP_CHAIN}
+                 id(lib.ymi_dcn_v2_forward_f32): L.OP_DCN, id(lib.ymi_pointwise_chain_f32): L.OP_CHAIN,
+                 id(lib.ymi_stage_exit_chain_f32): L.OP_STAGE_EXIT}
         for k, (fn, args, name, where) in enumerate(self.ops):
             o = arr[k + 1]
             o.stream = 1 if where == 'B' else 0
@@ -1497,8 +1536,8 @@ class Plan:
         back); a conv3 of that shape WITHOUT such a successor (the last block of the stage) -> the same streaming kernel with its
         second layer switched off.  Either only where measured faster than the launches it replaces: the decision is a table entry
         like every other choice ('chain(B, H, W)' / 'chain1(B, H, W)': [1 | 0, ms of the plan's launches, ms of the chain launch]);
-        YOLACT_AMD_CHAIN=0 keeps the plan's launches."""
-        self.chain_table = []
+        YOLACT_AMD_CHAIN=0 keeps the plan's launches (and those of the stage exit, _fuse_stage_exit, which is tried first)."""
+        self.chain_table, self.chainx_table = [], []
         if not self.h2 or os.environ.get('YOLACT_AMD_CHAIN', '1') != '1':
             return
         lib = self.lib
@@ -1514,6 +1553,7 @@ class Plan:
                 e1.synchronize()
                 best = min(best, e0.elapsed_time(e1) / reps)
             return best
+        self._fuse_stage_exit(s, disk, measure, timed)       # (first: a 'chainx' decision of 1 takes the op before 'chain1' sees it)
         i = 0
         while i < len(self.ops):
             f3, p3, n3, w3 = self.ops[i]
@@ -1589,6 +1629,144 @@ class Plan:
                 if pair:
                     self.ops[i] = ('nop', None, n1 + '[fused into ' + n3 + ']', w1)
                     i += 1
+
+    def stage_exit_candidates(self):
+        """Op indices (conv3, conv1, [stride-2 readers]) of every stage exit ymi_stage_exit_chain_f32 can take (csrc/chain.hip,
+        chain_h2_k<128>): a 1x1 64 -> 256 + RES_ADD conv3 whose next launch on the same stream tag is a 1x1 / stride-1 256 -> 128
+        conv reading its output (so it has no 64-wide successor), whose every OTHER reader is a 1x1 stride-2 convolution — a
+        quarter of the pixels: the launch stores only those rows — and whose output is not a backbone output the FPN selects.
+        Pure shape logic on the op list (works on a dry CPU plan); DarkNet plans have no such conv3."""
+        conv = self.lib.ymi_conv2d_nhwc_f32
+        selected = {int(p) for li, p in getattr(self, '_stage_out_ptr', {}).items() if li in self.net.backbone_selected}
+        out = []
+        for i3, (f3, p3, n3, w3) in enumerate(self.ops):
+            if f3 is not conv or i3 in self.wide_ops:
+                continue
+            d3 = p3.contents
+            if not ((d3.kh, d3.kw, d3.stride, d3.pad, d3.nseg, d3.Cin, d3.Cout) == (1, 1, 1, 0, 1, 64, 256)
+                    and d3.res_mode == L.RES_ADD and not d3.res_after_act and d3.seg[0].n0 == 0 and d3.seg[0].act <= L.ACT_LEAKY01):
+                continue
+            yptr, ldy = int(d3.seg[0].ptr or 0), d3.seg[0].row_stride
+            if not yptr or yptr in selected:
+                continue
+            # the next launch on this stream tag (an event record in between only covers more; a wait does not commute)
+            i1 = None
+            for j in range(i3 + 1, len(self.ops)):
+                fj, pj, _, wj = self.ops[j]
+                if wj != w3 or fj in ('record', 'nop'):
+                    continue
+                if fj is conv and j not in self.wide_ops:
+                    d1 = pj.contents
+                    if ((d1.kh, d1.kw, d1.stride, d1.pad, d1.Cin, d1.Cout, d1.nseg) == (1, 1, 1, 0, 256, 128, 1)
+                            and d1.res_mode == L.RES_NONE and int(d1.x or 0) == yptr and d1.ldx == ldy
+                            and (d1.B, d1.H, d1.W) == (d3.B, d3.Ho, d3.Wo) and d1.seg[0].n0 == 0 and d1.seg[0].act <= L.ACT_LEAKY01):
+                        i1 = j
+                break
+            if i1 is None:
+                continue
+            # every other reader of y.  y is no selected output, so only backbone launches can read it, and its buffer is held until
+            # the backbone ends (_build frees it there): a launch of another section that names the address means the tensor the
+            # arena put there afterwards
+            downs, ok = [], True
+            for j in range(i3 + 1, len(self.ops)):
+                fj, pj, _, _ = self.ops[j]
+                if j == i1 or isinstance(fj, str) or self.sections[j] != 'backbone':
+                    continue
+                if fj is conv:
+                    dj = pj.contents
+                    if (int(dj.x or 0) == yptr and (dj.kh, dj.kw, dj.stride, dj.pad) == (1, 1, 2, 0) and dj.nseg == 1
+                            and (dj.B, dj.H, dj.W, dj.ldx) == (d3.B, d3.Ho, d3.Wo, ldy) and int(dj.res or 0) != yptr
+                            and int(dj.seg[0].ptr or 0) != yptr):
+                        downs.append(j)
+                        continue
+                    ptrs = _desc_pointers(dj)
+                elif isinstance(pj, tuple):                  # pooling / resize passes
+                    ptrs = [a for a in pj if isinstance(a, int)]
+                else:                                        # DCN / Winograd / chain descriptors: EVERY pointer field they hold, whatever
+                    ptrs = _desc_pointers(pj.contents)       # its name (a descriptor that gains an input is still seen here)
+                if yptr in ptrs:
+                    ok = False
+                    break
+            if ok:
+                out.append((i3, i1, downs))
+        return out
+
+    def _fuse_stage_exit(self, s, disk, measure, timed):
+        """layer0.2.conv3 (+ shortcut, ReLU) and layer1.0.conv1 (256 -> 128) -> ONE ymi_stage_exit_chain_f32 launch that takes y from LDS
+        for the second GEMM and, where the only other readers are stride-2 shortcuts, stores y at even rows and columns only (C2 is no
+        FPN input: 117 MB per batch-8 step that nothing reads).  Table entry 'chainx(B, H, W)': [1 | 0, ms of the two launches, ms of
+        this one], installed where t_one < 0.97 * t_plan.  YOLACT_AMD_CHAIN_EXIT = 1 (default) | 0 | force (install it whatever the
+        table says)."""
+        mode = os.environ.get('YOLACT_AMD_CHAIN_EXIT', '1')
+        self.chainx_table = []
+        if mode not in ('1', 'force'):
+            return
+        lib = self.lib
+        for i3, i1, downs in self.stage_exit_candidates():
+            f3, p3, n3, w3 = self.ops[i3]
+            f1, p1, n1, w1 = self.ops[i1]
+            d3, d1 = p3.contents, p1.contents
+            if not (d3.w_h2 and d3.x_amax and d1.w_h2):
+                continue
+            M = d3.B * d3.Ho * d3.Wo
+            if M * max(d3.seg[0].row_stride, d3.res_ld, d1.seg[0].row_stride) >= (1 << 29):
+                continue
+            xd = L.StageExitDesc()
+            cd = xd.chain
+            cd.x, cd.res, cd.y = d3.x, d3.res, d3.seg[0].ptr
+            cd.w_a_h2, cd.scale_a_h2, cd.bias_a = d3.w_h2, d3.scale_h2, d3.bias
+            cd.x_amax, cd.y_amax = d3.x_amax, d3.y_amax
+            cd.M, cd.ldx, cd.res_ld, cd.ldy = M, d3.ldx, d3.res_ld, d3.seg[0].row_stride
+            cd.k_a, cd.n_a, cd.n_b, cd.cout_pad_a, cd.cout_pad_b = 64, 256, 128, _ceil(256, 128), _ceil(128, 128)
+            cd.act_a = d3.seg[0].act
+            cd.z, cd.ldz, cd.z_amax, cd.act_b = d1.seg[0].ptr, d1.seg[0].row_stride, d1.y_amax, d1.seg[0].act
+            cd.w_b_h2, cd.scale_b_h2, cd.bias_b = d1.w_h2, d1.scale_h2, d1.bias
+            xd.B, xd.H, xd.W = d3.B, d3.Ho, d3.Wo
+            xd.y_stride = 2 if downs else 1         # (no other reader at all: y is written in full, nothing says who reads it)
+
+            # aliasing contract of ymi_stage_exit_chain_f32 (include/yolact_amd.h): z must not overlap x, the residual or y
+            def span(ptr, ld):
+                return (int(ptr or 0), int(ptr or 0) + 4 * M * int(ld))
+
+            def overlap(a, b):
+                return a[0] < b[1] and b[0] < a[1]
+            zs = span(cd.z, cd.ldz)
+            if overlap(zs, span(cd.y, cd.ldy)) or overlap(zs, span(cd.x, cd.ldx)) or (cd.res and overlap(zs, span(cd.res, cd.res_ld))):
+                continue
+            xptr = C.pointer(xd)
+            name = n3 + '+' + n1
+            shape = str((d3.B, d3.Ho, d3.Wo)) + self.mode_key
+            ent = disk.get('chainx' + shape)
+            if mode == 'force':
+                ent = [1, 0.0, 0.0]
+            if ent is None:
+                self.tune_misses += 1
+                if not measure or lib.ymi_stage_exit_chain_f32(xptr, s) != 0:
+                    continue
+                # the launches it replaces: conv3 — on the streaming kernel where the table prefers that ('chain1') — and conv1
+                run3 = lambda: f3(p3, s)
+                c1 = disk.get('chain1' + shape)
+                if c1 is not None and c1[0]:
+                    cc = L.ChainDesc.from_buffer_copy(cd)
+                    cc.z, cc.w_b_h2, cc.scale_b_h2, cc.bias_b, cc.z_amax, cc.n_b = None, None, None, None, None, 64
+                    ccp = C.pointer(cc)
+                    if lib.ymi_pointwise_chain_f32(ccp, s) == 0:
+                        run3 = lambda: lib.ymi_pointwise_chain_f32(ccp, s)
+                t_plan = timed(lambda: (run3(), f1(p1, s)))
+                t_one = timed(lambda: lib.ymi_stage_exit_chain_f32(xptr, s))
+                ent = disk['chainx' + shape] = [1 if t_one < 0.97 * t_plan else 0, round(t_plan, 4), round(t_one, 4)]
+            self.chainx_table.append((name, ent[0], ent[1], ent[2]))
+            if ent[0] and lib.ymi_stage_exit_chain_f32(xptr, s) == 0:
+                self.keepalive.append(xd)
+                self.ops[i3] = (lib.ymi_stage_exit_chain_f32, xptr, name, w3)
+                self.ops[i1] = ('nop', None, n1 + '[fused into ' + n3 + ']', w1)
+                # profile records map onto conv_meta by position (kind 13, then kind 12 = conv1): in two-stream plans the
+                # projection shortcut was appended between the two layers
+                names = [n for n, _ in self.conv_meta]
+                if n3 in names and n1 in names:
+                    a, b = names.index(n3), names.index(n1)
+                    if b > a + 1:
+                        self.conv_meta.insert(a + 1, self.conv_meta.pop(b))
 
     def _apply_choice(self, fn, dptr, where, val, s):
         """Install a table value (tile id + 256 * split_k) in a descriptor; returns the launch status of one run."""
