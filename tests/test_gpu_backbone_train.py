@@ -11,6 +11,7 @@ Every case runs twice on the same inputs and must give the same bits.  Where an 
 buffers with a NaN guard band behind them.
 """
 import ctypes as C
+import functools
 import os
 import sys
 
@@ -23,7 +24,9 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import backbone_train_ref as R  # noqa: E402
 import heads_train_ref as H  # noqa: E402
 import helpers  # noqa: E402
+import train_helpers  # noqa: E402
 from helpers import rel_err, same_bits  # noqa: E402
+from train_helpers import DEV, EXACT_BAR, STORED_SLACK, down, guarded, nan_padded, twice, unguard  # noqa: E402
 import yolact_amd  # noqa: E402
 from yolact_amd import _lib as L  # noqa: E402
 from yolact_amd import modules as M  # noqa: E402
@@ -31,10 +34,6 @@ from yolact_amd.layers import train_ops as TO  # noqa: E402
 from yolact_amd.layers.modules import MultiBoxLoss  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-DEV = 'cuda:0'
-EXACT_BAR = 8e-6
-STORED_SLACK = 1e-6
-GUARD = 256
 # (kernel, B, H, W, Cin, Cout): odd extents with every window at a border; even extents (the masked last row and column); 1x1 on odd
 # and on even extents; 2 * 37 * 41 pixels: many tiles with a ragged last one in every phase
 DG_SHAPES = [(3, 2, 5, 7, 32, 32), (3, 1, 8, 6, 64, 96), (1, 2, 7, 9, 64, 32), (1, 1, 8, 6, 32, 64), (3, 2, 37, 41, 96, 32)]
@@ -49,6 +48,7 @@ BLOCK_SPECS = {'identity': (128, 32, 1, False), 'proj_s1': (64, 32, 1, True), 'p
 BLOCK_SEEDS = {(v, bs): 1 for v in BLOCK_SPECS for bs in (False, True)}      # chosen likewise (at least 77 times)
 BLOCK_SEEDS.update({('identity', True): 5, ('proj_s1', True): 2, ('proj_s2', True): 2, ('entry', True): 7})
 _MAX = {}
+compare = functools.partial(train_helpers.compare, _MAX)
 
 
 @pytest.fixture(scope='module', autouse=True)
@@ -65,44 +65,6 @@ def _report():
 def _restore_cfg():
     yield
     yolact_amd.set_cfg('yolact_base_config')
-
-
-def compare(name, got, want64, want32, against=None, slack=0.0):
-    """The bar comes from the two oracles; `against` (default: the fp64 oracle) is what `got` is measured against."""
-    against = want64 if against is None else against
-    assert sorted(got) == sorted(want64), (sorted(got), sorted(want64))
-    errs = {k: (rel_err(got[k], against[k]), max(4 * rel_err(want32[k], want64[k]), EXACT_BAR) + slack) for k in want64}
-    _MAX[name] = errs
-    for k, (e, bar) in errs.items():
-        print('%s %s: rel_err %.3e (bar %.3e)' % (name, k, e, bar))
-    for k, (e, bar) in errs.items():
-        assert got[k].shape == against[k].shape, (name, k)
-        assert e <= bar, (name, k, e, bar)
-
-
-def twice(run):
-    """run() -> dict of CPU tensors, two times on the same inputs: the same bits."""
-    a, b = run(), run()
-    same_bits(a, b)
-    return a
-
-
-def down(n):
-    return (n - 1) // 2 + 1
-
-
-def guarded(n):
-    return torch.full((n + GUARD,), float('nan'), device=DEV)
-
-
-def unguard(buf, shape):
-    """Every element written, the band behind them untouched."""
-    n = 1
-    for s in shape:
-        n *= s
-    out = buf.cpu()
-    assert not torch.isnan(out[:n]).any() and torch.isnan(out[n:]).all()
-    return out[:n].view(*shape)
 
 
 # ---- 1. the stride-2 data gradient alone --------------------------------------------------------------------------------------------------
@@ -122,7 +84,7 @@ def dgrad_gpu(gpad, w, Hh, W):
 
 
 def zero_insert_gpu(g, w, Hh, W):
-    """The route of train_ops.ConvDown.backward: g spread over a zeroed H x W map, then the stride-1 data gradient on the engine."""
+    """The route of conv2d_down's data gradient (train_ops._data_grad with zero_insert): g spread over a zeroed H x W map, then the stride-1 data gradient on the engine."""
     Cout, Cin, k, _ = w.shape
     B = g.shape[0]
     gz = torch.zeros(B, Hh, W, Cout, device=DEV)
@@ -140,12 +102,6 @@ def dgrad_oracle(g, w, Hh, W, dtype):
     assert y.shape[2:] == g.shape[1:3]
     (dx,) = torch.autograd.grad((y * g.to(dtype).permute(0, 3, 1, 2)).sum(), [leaf])
     return dx.permute(0, 2, 3, 1)
-
-
-def nan_padded(g):
-    gpad = torch.full(tuple(g.shape[:3]) + (g.shape[3] + 32,), float('nan'))          # the padding channels are never read
-    gpad[..., :g.shape[3]] = g
-    return gpad.to(DEV)
 
 
 @pytest.mark.parametrize('shape', DG_SHAPES, ids=lambda s: '%dx%d_b%d_%dx%d_%dto%d' % (s[0], s[0], s[1], s[2], s[3], s[4], s[5]))

@@ -11,6 +11,7 @@ single-layer cases take their inputs from grids (maps in 1/256, weights in 1/204
 |pre-activation|.  Every case runs twice on the same inputs and must give the same bits.
 """
 import ctypes as C
+import functools
 import os
 import sys
 
@@ -24,7 +25,9 @@ import heads_train_ref as H  # noqa: E402
 import multibox_ref as MR  # noqa: E402
 import class_loss_ref as CR  # noqa: E402
 import helpers  # noqa: E402
+import train_helpers  # noqa: E402
 from helpers import rel_err, same_bits  # noqa: E402
+from train_helpers import DEV, EXACT_BAR, STORED_SLACK, down, grid_randn, guarded, twice, unguard  # noqa: E402
 import yolact_amd  # noqa: E402
 from yolact_amd import _lib as L  # noqa: E402
 from yolact_amd import modules as M  # noqa: E402
@@ -32,9 +35,6 @@ from yolact_amd.layers import train_ops as TO  # noqa: E402
 from yolact_amd.layers.modules import MultiBoxLoss  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-DEV = 'cuda:0'
-EXACT_BAR = 8e-6
-STORED_SLACK = 1e-6
 SEEDS = dict(up=7, wgrad=3, conv=5, real=2, e2e=4)      # chosen on the CPU: see the module docstring
 # (input size, output size): both interpolations of the golden pyramid, one pixel, x2, the identity in one axis and in both
 UP_SHAPES = [((4, 3), (7, 5)), ((7, 5), (13, 10)), ((1, 1), (2, 3)), ((5, 7), (10, 14)), ((2, 9), (2, 17)), ((3, 3), (3, 3))]
@@ -43,6 +43,7 @@ UP_SHAPES = [((4, 3), (7, 5)), ((7, 5), (13, 10)), ((1, 1), (2, 3)), ((5, 7), (1
 WG2_SHAPES = [(3, 2, 5, 7, 32, 12), (3, 1, 8, 6, 64, 40), (1, 2, 7, 9, 64, 32), (3, 2, 37, 41, 32, 96)]
 REAL_SIZES = [(5, 5), (3, 3), (2, 2)]
 _MAX = {}
+compare = functools.partial(train_helpers.compare, _MAX)
 
 
 @pytest.fixture(scope='module', autouse=True)
@@ -61,46 +62,15 @@ def _restore_cfg():
     yolact_amd.set_cfg('yolact_base_config')
 
 
-def compare(name, got, want64, want32, against=None, slack=0.0):
-    """The bar comes from the two oracles; `against` (default: the fp64 oracle) is what `got` is measured against."""
-    against = want64 if against is None else against
-    assert sorted(got) == sorted(want64)
-    errs = {k: (rel_err(got[k], against[k]), max(4 * rel_err(want32[k], want64[k]), EXACT_BAR) + slack) for k in want64}
-    _MAX[name] = errs
-    for k, (e, bar) in errs.items():
-        print('%s %s: rel_err %.3e (bar %.3e)' % (name, k, e, bar))
-    for k, (e, bar) in errs.items():
-        assert got[k].shape == against[k].shape, (name, k)
-        assert e <= bar, (name, k, e, bar)
-
-
-def twice(run):
-    """run() -> dict of CPU tensors, two times on the same inputs: the same bits."""
-    a, b = run(), run()
-    same_bits(a, b)
-    return a
-
-
-def grid_randn(g, shape, step, std=1.0, lim=4.0):
-    return H.grid((torch.randn(*shape, generator=g) * std).clamp(-lim, lim), step)
-
-
-def down(n):
-    return (n - 1) // 2 + 1          # 3x3 / pad 1 and 1x1 / pad 0 at stride 2
-
-
 # ---- 1. the size-form bilinear backward alone -------------------------------------------------------------------------------------------
 def size_bwd_gpu(dy, Hi, Wi):
     """ymi_bilinear_size_bwd_nhwc_f32 into a NaN-filled dx with a NaN guard band behind it: every element written, the band untouched."""
     B, Ho, Wo, Cc = dy.shape
-    n, guard = B * Hi * Wi * Cc, 256
-    buf = torch.full((n + guard,), float('nan'), device=DEV)
+    buf = guarded(B * Hi * Wi * Cc)
     dyd = dy.to(DEV)
     L.check(L.lib().ymi_bilinear_size_bwd_nhwc_f32(dyd.data_ptr(), buf.data_ptr(), B, Hi, Wi, Cc, Ho, Wo, L.stream_ptr()), 'size bwd')
     torch.cuda.synchronize()
-    out = buf.cpu()
-    assert not torch.isnan(out[:n]).any() and torch.isnan(out[n:]).all()
-    return out[:n].view(B, Hi, Wi, Cc)
+    return unguard(buf, (B, Hi, Wi, Cc))
 
 
 @pytest.mark.parametrize('shape', UP_SHAPES, ids=lambda s: '%dx%d_to_%dx%d' % (s[0] + s[1]))

@@ -11,6 +11,7 @@ single-layer cases take their inputs from grids on which the pre-activations are
 their deviation is 0 and the margin is the smallest non-zero |pre-activation|.  Nothing is left out of a comparison.
 """
 import ctypes as C
+import functools
 import os
 import sys
 
@@ -20,22 +21,22 @@ import torch.nn.functional as F
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import heads_train_ref as H  # noqa: E402
+import train_helpers  # noqa: E402
 from helpers import rel_err, same_bits  # noqa: E402
+from train_helpers import DEV, EXACT_BAR, STORED_SLACK, grid_randn  # noqa: E402
 import yolact_amd  # noqa: E402
 from yolact_amd import _lib as L  # noqa: E402
 from yolact_amd.layers import train_ops as TO  # noqa: E402
 from yolact_amd.layers.modules import MultiBoxLoss  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-DEV = 'cuda:0'
-EXACT_BAR = 8e-6
-STORED_SLACK = 1e-6
 SEEDS = dict(real=37, wgrad=3, conv=5, up=7)         # chosen on the CPU: see the module docstring (the golden's is in its meta)
 SMALL_PYRAMID = [(5, 5), (3, 3), (2, 2), (1, 1), (1, 1)]
 # (kernel, B, H, W, Cin, Cout): a map smaller than a tile with every pixel at a border and Cout < 32; an odd Cout over several column
 # tiles and two channel chunks; 1x1; 3 034 positions: several chunks with a ragged last one and the ordered second pass
 WG_SHAPES = [(3, 2, 5, 7, 32, 12), (3, 1, 9, 9, 64, 243), (1, 3, 6, 6, 256, 32), (3, 2, 37, 41, 32, 96)]
 _MAX = {}
+compare = functools.partial(train_helpers.compare, _MAX)
 
 
 @pytest.fixture(scope='module', autouse=True)
@@ -52,21 +53,6 @@ def _report():
 def _restore_cfg():
     yield
     yolact_amd.set_cfg('yolact_base_config')
-
-
-def compare(name, got, want64, want32, against=None, slack=0.0):
-    """The bar comes from the two oracles; `against` (default: the fp64 oracle) is what `got` is measured against."""
-    against = want64 if against is None else against
-    errs = {k: (rel_err(got[k], against[k]), max(4 * rel_err(want32[k], want64[k]), EXACT_BAR) + slack) for k in want64}
-    _MAX[name] = errs
-    for k, (e, bar) in errs.items():
-        print('%s %s: rel_err %.3e (bar %.3e)' % (name, k, e, bar))
-    for k, (e, bar) in errs.items():
-        assert e <= bar, (name, k, e, bar)
-
-
-def grid_randn(g, shape, step, std=1.0, lim=4.0):
-    return H.grid((torch.randn(*shape, generator=g) * std).clamp(-lim, lim), step)
 
 
 # ---- the weight gradient alone ----------------------------------------------------------------------------------------------------------

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Time the train-mode backbone (Yolact.forward_backbone, csrc/conv_dgrad.hip, csrc/bn_train.hip):
 
-  (a) ymi_conv_dgrad_s2_nhwc_f32 against the zero-insert route of train_ops.ConvDown.backward (g spread over a zeroed H x W buffer,
-      then the stride-1 data gradient on the conv engine; filters packed beforehand for both) on the ResNet stage entries at B = 8 and
+  (a) ymi_conv_dgrad_s2_nhwc_f32 against the zero-insert route of conv2d_down's data gradient (train_ops._data_grad: g spread over a
+      zeroed H x W buffer, then the stride-1 data gradient on the conv engine; filters packed beforehand for both) on the ResNet stage entries at B = 8 and
       550 x 550: 3x3 128 -> 128 at 138 -> 69, 256 -> 256 at 69 -> 35, 512 -> 512 at 35 -> 18, and the 1x1 projection shortcuts
       256 -> 512, 512 -> 1024, 1024 -> 2048 at the same maps.  ROUNDS alternating rounds (route, kernel, route, kernel, ..), each the
       median of REPS; reported: the median of the rounds' medians, the least time seen, and the route's own spread (largest minus

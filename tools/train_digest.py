@@ -1,0 +1,177 @@
+#!/usr/bin/env python3
+"""One SHA-256 per output tensor of the train-mode building blocks (yolact_amd/layers/train_ops.py) on fixed inputs: two trees whose
+lines are equal issue the same launches on the same operands.  Only public functions are called (conv2d_act, conv2d_multi,
+conv2d_down, conv2d_plain, bottleneck, upsample2x, upsample_add, batch_norm_act), so the script runs unchanged on an older tree.  The
+shapes are the small ones of tests/test_gpu_heads_train.py, tests/test_gpu_fpn_train.py and tests/test_gpu_backbone_train.py; the
+inputs come from seeded CPU generators.  Per case: y and every gradient (for a bottleneck the running statistics afterwards too).
+
+    python tools/train_digest.py > digests.txt
+"""
+import hashlib
+import os
+import sys
+
+import torch
+import torch.nn as nn
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, 'tests'))
+import backbone_train_ref as R  # noqa: E402
+import yolact_amd  # noqa: E402, F401
+from yolact_amd import modules as M  # noqa: E402
+from yolact_amd.layers import train_ops as TO  # noqa: E402
+
+DEV = 'cuda:0'
+ACT_SHAPES = [(3, 2, 5, 7, 32, 12), (3, 1, 9, 9, 64, 243), (1, 3, 6, 6, 256, 32)]            # (k, B, H, W, Cin, Cout)
+DOWN_SHAPES = [(3, 2, 5, 7, 32, 12), (3, 1, 8, 6, 64, 40), (1, 2, 7, 9, 64, 32)]
+PLAIN_GEOS = [(3, 1, 32, 40), (1, 1, 64, 32), (3, 2, 32, 32), (1, 2, 64, 96), (3, 2, 64, 40)]   # (k, stride, Cin, Cout) at B = 2, 9 x 7
+BLOCK_SPECS = {'identity': (128, 32, 1, False), 'proj_s1': (64, 32, 1, True), 'proj_s2': (64, 32, 2, True), 'entry': (64, 64, 1, True)}
+ACTS = (None, 'relu', 'tanh')
+
+
+def emit(case, name, t):
+    t = t.detach().cpu().contiguous()
+    print('%-30s %-26s %-7s %-18s %s' % (case, name, str(t.dtype)[6:], list(t.shape), hashlib.sha256(t.numpy().tobytes()).hexdigest()))
+
+
+def leaf(t, grad=True, dtype=None):
+    return t.to(device=DEV, dtype=dtype).requires_grad_(grad)
+
+
+def backward_and_emit(case, ys, ups, leaves):
+    """ys: the outputs that enter the loss (each with its upstream gradient); leaves: name -> tensor, those requiring grad are emitted."""
+    sum((y * u.to(DEV)).sum() for y, u in zip(ys, ups)).backward()
+    torch.cuda.synchronize()
+    for n, t in leaves.items():
+        if t.requires_grad:
+            emit(case, 'd_' + n, t.grad)
+
+
+def conv_inputs(g, k, B, H, W, Cin, Cout, Ho=None, Wo=None):
+    x = torch.randn(B, H, W, Cin, generator=g)
+    w = torch.randn(Cout, Cin, k, k, generator=g) * (2.0 / (Cin * k * k)) ** 0.5
+    b = torch.randn(Cout, generator=g) * 0.1
+    up = torch.randn(B, Ho or H, Wo or W, Cout, generator=g)
+    return x, w, b, up
+
+
+def act_case(case, shape, act, grads=(True, True, True), dtype=None):
+    k = shape[0]
+    x, w, b, up = conv_inputs(torch.Generator().manual_seed(5), *shape)
+    leaves = dict(x=leaf(x, grads[0]), w=leaf(w, grads[1], dtype), b=leaf(b, grads[2], dtype))
+    y = TO.conv2d_act(leaves['x'], leaves['w'], leaves['b'], k // 2, act)
+    emit(case, 'y', y)
+    backward_and_emit(case, [y], [up], leaves)
+
+
+def multi_case(case, n_in_loss):
+    g = torch.Generator().manual_seed(6)
+    x = torch.randn(2, 5, 7, 32, generator=g)
+    leaves, layers, ups = dict(x=leaf(x)), [], []
+    for i, (co, act) in enumerate(zip((16, 81, 32), (None, None, 'tanh'))):
+        _, w, b, up = conv_inputs(g, 3, 2, 5, 7, 32, co)
+        leaves['w%d' % i], leaves['b%d' % i] = leaf(w), leaf(b)
+        layers.append((leaves['w%d' % i], leaves['b%d' % i], act))
+        ups.append(up)
+    ys = TO.conv2d_multi(leaves['x'], layers, 1)
+    for i, y in enumerate(ys):
+        emit(case, 'y%d' % i, y)
+    backward_and_emit(case, ys[:n_in_loss], ups[:n_in_loss], leaves)
+
+
+def down(n):
+    return (n - 1) // 2 + 1
+
+
+def down_case(case, shape, act):
+    k, B, H, W, Cin, Cout = shape
+    x, w, b, up = conv_inputs(torch.Generator().manual_seed(7), *shape, Ho=down(H), Wo=down(W))
+    leaves = dict(x=leaf(x), w=leaf(w), b=leaf(b))
+    y = TO.conv2d_down(leaves['x'], leaves['w'], leaves['b'], act)
+    emit(case, 'y', y)
+    backward_and_emit(case, [y], [up], leaves)
+
+
+def plain_case(case, geo):
+    k, stride, Cin, Cout = geo
+    B, H, W = 2, 9, 7
+    Ho, Wo = (down(H), down(W)) if stride == 2 else (H, W)
+    x, w, _, up = conv_inputs(torch.Generator().manual_seed(8), k, B, H, W, Cin, Cout, Ho=Ho, Wo=Wo)
+    leaves = dict(x=leaf(x), w=leaf(w))
+    y = TO.conv2d_plain(leaves['x'], leaves['w'], stride)
+    emit(case, 'y', y)
+    backward_and_emit(case, [y], [up], leaves)
+
+
+def block_case(case, spec, batch_stats):
+    inplanes, planes, stride, projection = spec
+    x, params, _, up = R.random_case(9, (2, inplanes, 9, 7), [spec])
+    ds = nn.Sequential(nn.Conv2d(inplanes, 4 * planes, 1, stride=stride, bias=False), nn.BatchNorm2d(4 * planes)) if projection else None
+    blk = M.Bottleneck(inplanes, planes, stride, ds)
+    sd = blk.state_dict()
+    with torch.no_grad():
+        for n in sd:
+            if 'num_batches' not in n:
+                sd[n].copy_(params[n])
+    blk = blk.to(DEV).eval()
+    leaves = dict(x=leaf(x.permute(0, 2, 3, 1).contiguous()))
+    leaves.update(blk.named_parameters())
+    y = TO.bottleneck(leaves['x'], blk, batch_stats)
+    emit(case, 'y', y)
+    backward_and_emit(case, [y], [up.permute(0, 2, 3, 1)], leaves)
+    for n, t in blk.state_dict().items():
+        if 'running' in n:
+            emit(case, n, t)
+
+
+def others():
+    g = torch.Generator().manual_seed(10)
+    x, up = torch.randn(2, 5, 7, 32, generator=g), torch.randn(2, 10, 14, 32, generator=g)
+    leaves = dict(x=leaf(x))
+    y = TO.upsample2x(leaves['x'], True)
+    emit('upsample2x relu', 'y', y)
+    backward_and_emit('upsample2x relu', [y], [up], leaves)
+    top, lat, up = (torch.randn(*s, generator=g) for s in ((2, 4, 3, 32), (2, 7, 5, 32), (2, 7, 5, 32)))
+    leaves = dict(top=leaf(top), lat=leaf(lat))
+    y = TO.upsample_add(leaves['top'], leaves['lat'])
+    emit('upsample_add', 'y', y)
+    backward_and_emit('upsample_add', [y], [up], leaves)
+    x, res, up = (torch.randn(2, 5, 7, 32, generator=g) for _ in range(3))
+    bn = nn.BatchNorm2d(32)
+    with torch.no_grad():
+        bn.weight.copy_(0.5 + torch.rand(32, generator=g))
+        bn.bias.copy_(torch.randn(32, generator=g) * 0.1)
+    bn.to(DEV)
+    leaves = dict(x=leaf(x), res=leaf(res), gamma=bn.weight, beta=bn.bias)
+    y = TO.batch_norm_act(leaves['x'], bn, True, leaves['res'], True)
+    emit('batch_norm_act', 'y', y)
+    backward_and_emit('batch_norm_act', [y], [up], leaves)
+    emit('batch_norm_act', 'running_mean', bn.running_mean)
+    emit('batch_norm_act', 'running_var', bn.running_var)
+
+
+def main():
+    print('# %s, torch %s' % (torch.cuda.get_device_name(0), torch.__version__))
+    name = lambda s: '%dx%d_b%d_%dx%d_%dto%d' % (s[0], s[0], s[1], s[2], s[3], s[4], s[5])
+    for shape in ACT_SHAPES:
+        for act in ACTS:
+            act_case('act %s %s' % (name(shape), act), shape, act)
+    for what, grads in (('b', (False, False, True)), ('x', (True, False, False)), ('w', (False, True, False))):
+        act_case('act %s relu only_%s' % (name(ACT_SHAPES[0]), what), ACT_SHAPES[0], 'relu', grads)
+    act_case('act %s tanh float64' % name(ACT_SHAPES[0]), ACT_SHAPES[0], 'tanh', dtype=torch.float64)
+    multi_case('multi 16+81+32 all', 3)
+    multi_case('multi 16+81+32 first_two', 2)
+    for shape in DOWN_SHAPES:
+        for act in ACTS:
+            down_case('down %s %s' % (name(shape), act), shape, act)
+    for geo in PLAIN_GEOS:
+        plain_case('plain %dx%d_s%d_%dto%d' % (geo[0], geo[0], geo[1], geo[2], geo[3]), geo)
+    for variant, spec in BLOCK_SPECS.items():
+        for batch_stats in (False, True):
+            block_case('bottleneck %s %s' % (variant, 'stats' if batch_stats else 'frozen'), spec, batch_stats)
+    others()
+
+
+if __name__ == '__main__':
+    main()

@@ -1,35 +1,38 @@
-"""Differentiable building blocks of the train-mode heads, protonet and FPN on the HIP kernels (csrc/conv_train.hip and the conv
-engine).
+"""Differentiable building blocks of the train-mode heads, protonet, FPN and ResNet stages on the HIP kernels (csrc/conv_train.hip,
+csrc/conv_dgrad.hip, csrc/bn_train.hip and the conv engine).
 
     conv2d_act(x, weight, bias, padding, act)            -> y [B,H,W,Cout]: act(conv(x, weight) + bias), act in {None, 'relu', 'tanh'}
     conv2d_multi(x, [(weight, bias, act), ..], padding)  -> one y per entry: up to three convolutions of the SAME input as one launch
                                                             (the head's bbox / conf / mask layers, yolact.py:169-173)
-    upsample2x(x, relu)                                  -> [B,2H,2W,C]: F.interpolate(scale_factor=2, bilinear, align_corners=False)
-
     conv2d_down(x, weight, bias, act)                    -> [B,Ho,Wo,Cout]: the same at stride 2 with padding k // 2 (the FPN's
-                                                            downsample layers, yolact.py:349-351); 3x3 and 1x1, Cin % 32 == 0
+                                                            downsample layers, yolact.py:349-351)
+    conv2d_plain(x, weight, stride)                      -> [B,Ho,Wo,Cout]: a bias-free convolution with padding k // 2 at stride 1 or 2
+                                                            (the backbone's convolutions, backbone.py:19-31)
+    upsample2x(x, relu)                                  -> [B,2H,2W,C]: F.interpolate(scale_factor=2, bilinear, align_corners=False)
     upsample_add(top, lat)                               -> F.interpolate(top, size of lat, bilinear, align_corners=False) + lat (the
                                                             FPN's top-down sum, yolact.py:332-334), any size of lat >= that of top
-
-    conv2d_plain(x, weight, stride)                      -> [B,Ho,Wo,Cout]: a bias-free convolution, 3x3 / pad 1 or 1x1 / pad 0 at stride 1 or 2
-                                                            (the backbone's convolutions, backbone.py:19-31); Cin % 32 == 0
     batch_norm_act(x, bn, batch_stats, residual, relu)   -> relu(bn(x) + residual) for an nn.BatchNorm2d, batch statistics or frozen
     bottleneck(x, block, batch_stats)                    -> a modules.Bottleneck (backbone.py:37-57); bn3 + shortcut + ReLU are one launch
 
 x and the results are NHWC fp32 GPU tensors; weight and bias are nn.Conv2d parameters in torch layout.  Everything is once
 differentiable in x, every weight and every bias.  Each call packs its filters from the CURRENT parameter values (a permute; no
 cache), launches only what needs_input_grad asks for, and saves its inputs, so autograd's version check refuses a backward after an
-in-place edit.  Geometry: 3x3 / stride 1 / pad 1 and 1x1 / pad 0, Cin % 32 == 0, any Cout; anything else raises NotImplementedError
-naming it.  CPU tensors raise: there is no CPU path.
+in-place edit.  CPU tensors raise: there is no CPU path.
 
-Launches of one convolution's backward: ymi_act_bwd_f32 per output (g = dy * act'(y), side by side in one buffer whose channel stride
-is padded to a multiple of 32, padding zeroed), ymi_conv_wgrad_nhwc_f32 once over all outputs (dw, db), ymi_conv2d_nhwc_f32 once on g
-with the filters flipped in both taps and transposed in (Cin, Cout) (dx).  conv2d_down: the same with ymi_conv_wgrad_desc.stride = 2;
-its dx first spreads g over a zeroed [B,H,W,ldg] buffer (gz[:, ::2, ::2] = g) and then runs the stride-1 data gradient on it, which
-spends four times the useful FLOPs (fine for the FPN's 18 x 18 and 9 x 9 maps, not for a backbone).  upsample_add: d_lat = dy,
-d_top = ymi_bilinear_size_bwd_nhwc_f32 (a gather in a fixed order).  conv2d_plain: dw from ymi_conv_wgrad_nhwc_f32 with db = NULL; dx at
-stride 1 from the flipped-filter engine launch, at stride 2 from ymi_conv_dgrad_s2_nhwc_f32 (csrc/conv_dgrad.hip: only the taps that
-exist, no zero-filled buffer).  batch_norm_act: ymi_bn_fwd_nhwc_f32 / ymi_bn_bwd_nhwc_f32 (csrc/bn_train.hip).
+The four convolutions are one autograd.Function, Conv, behind four validators.  Geometry (_check_geometry, whose faces are check_conv,
+check_down and check_plain): 3x3 / pad 1 and 1x1 / pad 0, stride 1 or 2, dilation 1, groups 1, Cin % 32 == 0, any Cout; anything else
+raises NotImplementedError naming it.  Forward: one ymi_conv2d_nhwc_f32 launch over all outputs.  Backward:
+  g    with a bias: ymi_act_bwd_f32 per output (g = dy * act'(y), act None too), side by side in one buffer whose channel stride ldg
+       is ceil32 of the summed widths, padding zeroed by the last output's launch.  Without one (conv2d_plain): dy itself, F.pad-ed
+       to ldg only when Cout % 32 != 0, and no activation launch.
+  dw   _weight_grad: ymi_conv_wgrad_nhwc_f32 once over all outputs (dw, and db when there is a bias), then _unpack_dw per output.
+  dx   _data_grad.  Stride 1: ymi_conv2d_nhwc_f32 on g with the filters flipped in both taps and transposed in (Cin, Cout).
+       Stride 2 has two routes.  conv2d_plain: ymi_conv_dgrad_s2_nhwc_f32 (csrc/conv_dgrad.hip: only the taps that exist).
+       conv2d_down (zero_insert = True): g spread over a zeroed [B,H,W,ldg] buffer (gz[:, ::2, ::2] = g), then the stride-1 launch,
+       four times the useful FLOPs (fine for the FPN's 18 x 18 and 9 x 9 maps).  The two routes agree bit for bit only on exact
+       grids, so the FPN keeps its own until it is moved over on purpose; zero_insert and its branch then go.
+upsample_add: d_lat = dy, d_top = ymi_bilinear_size_bwd_nhwc_f32 (a gather in a fixed order).  batch_norm_act: ymi_bn_fwd_nhwc_f32 /
+ymi_bn_bwd_nhwc_f32 (csrc/bn_train.hip).
 """
 from __future__ import annotations
 
@@ -49,31 +52,60 @@ def _ceil(a, b):
     return (a + b - 1) // b * b
 
 
-def check_conv(weight, padding, stride=1, dilation=1, groups=1, who='conv2d_act'):
-    """NotImplementedError naming what of a convolution's geometry the kernels do not take -> (kh, pad)."""
+def _out_size(H, W, k, pad, stride):
+    return (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
+
+
+def _check_geometry(who, weight, stride, padding=None, dilation=1, groups=1, strides=(1, 2)):
+    """NotImplementedError naming what of a convolution's geometry the kernels do not take -> (k, pad, stride).  `strides`: what the
+    caller takes.  padding None: k // 2 is meant, and a weight that is not 4-D is refused by name (with a padding the weight is an
+    nn.Conv2d's, and its shape is unpacked before anything is looked at)."""
     pair = lambda v: (int(v), int(v)) if isinstance(v, int) else tuple(int(e) for e in v)
     if isinstance(padding, str):
         raise NotImplementedError('yolact_amd %s: padding = %r is not supported (an integer padding is)' % (who, padding))
-    stride, dilation, padding = pair(stride), pair(dilation), pair(padding)
-    Cout, Cin, kh, kw = weight.shape
-    if stride != (1, 1):
-        raise NotImplementedError('yolact_amd %s: stride = %r is not supported (stride 1 is)' % (who, stride))
+    stride, dilation = pair(stride), pair(dilation)
+    if padding is not None:
+        padding, (Cout, Cin, kh, kw) = pair(padding), weight.shape
+    if stride not in [(s, s) for s in strides]:
+        raise NotImplementedError('yolact_amd %s: stride = %r is not supported (%s %s)'
+                                  % (who, stride, ' and '.join('stride %d' % s for s in strides), 'is' if len(strides) == 1 else 'are'))
+    if padding is None:
+        if weight.dim() != 4:
+            raise NotImplementedError('yolact_amd %s: a weight of shape %s is not supported ([Cout,Cin,k,k] is)' % (who, tuple(weight.shape)))
+        Cout, Cin, kh, kw = weight.shape
+        padding = (kh // 2, kh // 2)
     if dilation != (1, 1):
         raise NotImplementedError('yolact_amd %s: dilation = %r is not supported (dilation 1 is)' % (who, dilation))
     if groups != 1:
         raise NotImplementedError('yolact_amd %s: groups = %r is not supported (groups 1 is)' % (who, groups))
-    if (kh, kw, padding) not in (((3, 3, (1, 1))), (1, 1, (0, 0))):
-        raise NotImplementedError('yolact_amd %s: a %d x %d kernel with padding = %r is not supported (3 x 3 / padding 1 and '
-                                  '1 x 1 / padding 0 are)' % (who, kh, kw, padding))
+    if (kh, kw, padding) not in ((3, 3, (1, 1)), (1, 1, (0, 0))):
+        what = 'at stride 2' if stride == (2, 2) else 'with padding = %r' % (padding,)
+        raise NotImplementedError('yolact_amd %s: a %d x %d kernel %s is not supported (3 x 3 / padding 1 and 1 x 1 / padding 0 are)'
+                                  % (who, kh, kw, what))
     if Cin % 32 != 0:
         raise NotImplementedError('yolact_amd %s: Cin = %d is not supported (a multiple of 32 input channels is)' % (who, Cin))
-    return kh, padding[0]
+    return kh, padding[0], stride[0]
+
+
+def check_conv(weight, padding, stride=1, dilation=1, groups=1, who='conv2d_act'):
+    """The geometry of a stride-1 convolution with its padding given -> (k, pad)."""
+    return _check_geometry(who, weight, stride, padding, dilation, groups, strides=(1,))[:2]
+
+
+def check_down(weight, who='conv2d_down'):
+    """The geometry of a stride-2 convolution with padding k // 2 -> (k, pad)."""
+    return _check_geometry(who, weight, 2)[:2]
+
+
+def check_plain(weight, stride, who='conv2d_plain'):
+    """The geometry of a bias-free convolution with padding k // 2 at stride 1 or 2 -> (k, pad, stride)."""
+    return _check_geometry(who, weight, stride)
 
 
 def _engine_conv(x, ldx, wpk, bias, Cin, Cout, k, pad, segs, stride=1):
     """One ymi_conv2d_nhwc_f32 launch on the exact-fp32 tiles: x [B,H,W,ldx], wpk [CoutPad][k*k*Cin], segs = (n0, n1, act, tensor)."""
     B, H, W = x.shape[:3]
-    Ho, Wo = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
+    Ho, Wo = _out_size(H, W, k, pad, stride)
     d = L.ConvDesc()
     d.x, d.w, d.bias = x.data_ptr(), wpk.data_ptr(), (None if bias is None else bias.data_ptr())
     d.B, d.H, d.W, d.Cin, d.ldx, d.Ho, d.Wo, d.Cout = B, H, W, Cin, ldx, Ho, Wo, Cout
@@ -102,87 +134,149 @@ def _pack_dgrad(wcat, ldg):
     return out
 
 
-class ConvMulti(torch.autograd.Function):
-    """apply(k, pad, acts, x, w1, b1, .., wn, bn) -> (y1, .., yn)."""
+def _pack_dgrad_s2(w, cpad):
+    """The filters of ymi_conv_dgrad_s2_nhwc_f32: [Cout,Cin,k,k] -> [k][k][cpad/4][Cin][4], Cout padded to cpad with zeros."""
+    Cout, Cin, k, _ = w.shape
+    t = F.pad(w.permute(2, 3, 0, 1), (0, 0, 0, cpad - Cout))                    # [k,k,cpad,Cin]
+    return t.reshape(k, k, cpad // 4, 4, Cin).permute(0, 1, 2, 4, 3).contiguous()
+
+
+def _cat_f32(ts):
+    """The CURRENT values of the parameters ts in fp32, along dim 0."""
+    ts = [t.detach().float() for t in ts]
+    return ts[0] if len(ts) == 1 else torch.cat(ts, 0)
+
+
+def _weight_grad(xd, g, ldg, Cin, ctot, k, pad, stride, want_w, want_b):
+    """One ymi_conv_wgrad_nhwc_f32 launch on xd [B,H,W,Cin] and g [B,Ho,Wo,ldg] -> (dw_flat [k*k*Cin, ctot], db [ctot]), None
+    where not wanted."""
+    dev = xd.device
+    B, H, W = xd.shape[:3]
+    dw = torch.empty(k * k * Cin, ctot, dtype=torch.float32, device=dev) if want_w else None
+    db = torch.empty(ctot, dtype=torch.float32, device=dev) if want_b else None
+    d = L.ConvWgradDesc()
+    d.x, d.g = xd.data_ptr(), g.data_ptr()
+    d.dw, d.db = (None if t is None else t.data_ptr() for t in (dw, db))
+    d.B, d.H, d.W, d.Cin, d.Cout, d.ldg, d.kh, d.kw, d.pad, d.stride = B, H, W, Cin, ctot, ldg, k, k, pad, stride
+    ws = LC.workspace('CONV_WGRAD', d, dev)
+    d.ws_bytes = ws.numel()
+    L.check(L.lib().ymi_conv_wgrad_nhwc_f32(C.byref(d), L.stream_ptr()), 'ymi_conv_wgrad_nhwc_f32')
+    return dw, db
+
+
+def _unpack_dw(dw_flat, k, Cin):
+    """Columns [k*k*Cin, co] of the weight gradient -> [co,Cin,k,k]."""
+    return dw_flat.reshape(k, k, Cin, dw_flat.shape[1]).permute(3, 2, 0, 1).contiguous()
+
+
+def _data_grad(g, ldg, wcat, B, H, W, k, pad, stride, zero_insert):
+    """dx [B,H,W,Cin] from g [B,Ho,Wo,ldg] and the filters wcat [ctot,Cin,k,k] (the module docstring has the routes)."""
+    dev, Cin = g.device, int(wcat.shape[1])
+    if stride == 2 and zero_insert:
+        # g with zeros between its pixels, exactly H x W (even and odd sizes), then the stride-1 data gradient: the added zeros
+        # change no bit of a sum, and a pixel no window reads (1x1) gets an exact +0.0
+        gz = torch.zeros(B, H, W, ldg, dtype=torch.float32, device=dev)
+        gz[:, ::2, ::2] = g
+        g, stride = gz, 1
+    dx = torch.empty(B, H, W, Cin, dtype=torch.float32, device=dev)
+    if stride == 1:
+        _engine_conv(g, ldg, _pack_dgrad(wcat, ldg), None, ldg, Cin, k, k - 1 - pad, [(0, Cin, L.ACT_NONE, dx)])
+    else:
+        wpk = _pack_dgrad_s2(wcat, ldg)
+        d = L.ConvDgradDesc()
+        d.g, d.w, d.dx = g.data_ptr(), wpk.data_ptr(), dx.data_ptr()
+        d.B, d.H, d.W, d.Cin, d.Cout, d.ldg, d.kh, d.kw, d.pad, d.stride = B, H, W, Cin, ldg, ldg, k, k, pad, 2
+        L.check(L.lib().ymi_conv_dgrad_s2_nhwc_f32(C.byref(d), L.stream_ptr()), 'ymi_conv_dgrad_s2_nhwc_f32')
+    return dx
+
+
+class Conv(torch.autograd.Function):
+    """apply(k, pad, stride, acts, zero_insert, x [B,H,W,Cin], w1, b1, .., wn, bn) -> (y1, .., yn), each [B,Ho,Wo,Cout_i].  Every b
+    is a tensor, or every b is None (then there is one output and no activation).  zero_insert: the route of a stride-2 dx."""
 
     @staticmethod
-    def forward(ctx, k, pad, acts, x, *params):
+    def forward(ctx, k, pad, stride, acts, zero_insert, x, *params):
         dev = x.device
         ws, bs = params[0::2], params[1::2]
+        biased = bs[0] is not None
         couts = [int(w.shape[0]) for w in ws]
         Cin = int(ws[0].shape[1])
         with torch.cuda.device(dev), torch.no_grad():
             xd = LC.f32(x, dev)
             B, H, W, _ = xd.shape
-            wcat = torch.cat([w.detach().float() for w in ws], 0) if len(ws) > 1 else ws[0].detach().float()
-            bcat = torch.cat([b.detach().float() for b in bs], 0).contiguous()
+            Ho, Wo = _out_size(H, W, k, pad, stride)
             ys, segs, n0 = [], [], 0
             for co, a in zip(couts, acts):
-                y = torch.empty(B, H, W, co, dtype=torch.float32, device=dev)
+                y = torch.empty(B, Ho, Wo, co, dtype=torch.float32, device=dev)
                 ys.append(y)
                 segs.append((n0, n0 + co, a, y))
                 n0 += co
-            _engine_conv(xd, Cin, _pack_forward(wcat), bcat, Cin, n0, k, pad, segs)
-        # the outputs are this call's own tensors; the inputs are saved too, so that autograd's version check refuses a backward
-        # after x or a parameter was edited in place
-        ctx.save_for_backward(x, *params, *ys)
-        ctx.k, ctx.pad, ctx.acts, ctx.couts = k, pad, acts, couts
-        ctx.dtypes = [x.dtype] + [p.dtype for p in params]
+            _engine_conv(xd, Cin, _pack_forward(_cat_f32(ws)), _cat_f32(bs).contiguous() if biased else None, Cin, n0, k, pad, segs,
+                         stride=stride)
+        # the inputs are saved so that autograd's version check refuses a backward after x or a parameter was edited in place; the
+        # outputs (this call's own tensors) are what an activation's backward reads
+        ctx.save_for_backward(x, *((*params, *ys) if biased else ws))
+        ctx.geo, ctx.acts, ctx.couts, ctx.biased, ctx.zero_insert = (k, pad, stride), acts, couts, biased, zero_insert
+        ctx.dtypes = [x.dtype] + [None if p is None else p.dtype for p in params]
         return tuple(ys)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, *dys):
-        need = ctx.needs_input_grad[3:]
+        need = ctx.needs_input_grad[5:]
         saved = ctx.saved_tensors                         # (the version check)
-        n = len(ctx.couts)
-        x, params, ys = saved[0], saved[1:1 + 2 * n], saved[1 + 2 * n:]
-        want_x, want_p = need[0], need[1:]
         if not any(need):
-            return (None,) * (3 + len(need))
+            return (None,) * (5 + len(need))
+        (k, pad, stride), couts, n = ctx.geo, ctx.couts, len(ctx.couts)
+        x, ws, ys = (saved[0], saved[1:1 + 2 * n:2], saved[1 + 2 * n:]) if ctx.biased else (saved[0], saved[1:], ())
+        want_x, want_p = need[0], need[1:]
         dev = x.device
-        lib, s = L.lib(), L.stream_ptr()
-        k, pad, couts = ctx.k, ctx.pad, ctx.couts
         with torch.cuda.device(dev), torch.no_grad():
             xd = LC.f32(x, dev)
             B, H, W, Cin = xd.shape
-            npos, ctot = B * H * W, sum(couts)
+            Ho, Wo = _out_size(H, W, k, pad, stride)
+            ctot = sum(couts)
             ldg = _ceil(ctot, 32)
-            g = torch.empty(B, H, W, ldg, dtype=torch.float32, device=dev)
-            n0, keep = 0, []
-            for i, (co, a, y, dy) in enumerate(zip(couts, ctx.acts, ys, dys)):
-                dyd = torch.zeros_like(y) if dy is None else LC.f32(dy, dev)
-                keep.append(dyd)
-                cpad = co + (ldg - ctot if i == len(couts) - 1 else 0)
-                L.check(lib.ymi_act_bwd_f32(y.data_ptr(), dyd.data_ptr(), g.data_ptr() + 4 * n0, npos, co, cpad, co, co, ldg, a, s),
-                        'ymi_act_bwd_f32')
-                n0 += co
-            grads = [None] * len(params)
+            if ctx.biased:
+                g = torch.empty(B, Ho, Wo, ldg, dtype=torch.float32, device=dev)
+                n0, keep = 0, []
+                for i, (co, a, y, dy) in enumerate(zip(couts, ctx.acts, ys, dys)):
+                    dyd = torch.zeros_like(y) if dy is None else LC.f32(dy, dev)
+                    keep.append(dyd)
+                    cpad = co + (ldg - ctot if i == n - 1 else 0)
+                    L.check(L.lib().ymi_act_bwd_f32(y.data_ptr(), dyd.data_ptr(), g.data_ptr() + 4 * n0, B * Ho * Wo, co, cpad, co, co,
+                                                    ldg, a, L.stream_ptr()), 'ymi_act_bwd_f32')
+                    n0 += co
+            else:
+                g = LC.f32(dys[0], dev)
+                if ldg != ctot:                            # (no backbone layer: their widths are multiples of 32)
+                    g = F.pad(g, (0, ldg - ctot))
+            grads = [None] * len(want_p)
             want_w, want_b = any(want_p[0::2]), any(want_p[1::2])
             if want_w or want_b:
-                d = L.ConvWgradDesc()
-                dw = torch.empty(k * k * Cin, ctot, dtype=torch.float32, device=dev) if want_w else None
-                db = torch.empty(ctot, dtype=torch.float32, device=dev) if want_b else None
-                d.x, d.g = xd.data_ptr(), g.data_ptr()
-                d.dw, d.db = (None if t is None else t.data_ptr() for t in (dw, db))
-                d.B, d.H, d.W, d.Cin, d.Cout, d.ldg, d.kh, d.kw, d.pad = B, H, W, Cin, ctot, ldg, k, k, pad
-                ws = LC.workspace('CONV_WGRAD', d, dev)
-                d.ws_bytes = ws.numel()
-                L.check(lib.ymi_conv_wgrad_nhwc_f32(C.byref(d), s), 'ymi_conv_wgrad_nhwc_f32')
+                dw, db = _weight_grad(xd, g, ldg, Cin, ctot, k, pad, stride, want_w, want_b)
                 n0 = 0
                 for i, co in enumerate(couts):
                     if want_p[2 * i]:
-                        grads[2 * i] = dw[:, n0:n0 + co].reshape(k, k, Cin, co).permute(3, 2, 0, 1).contiguous()
+                        grads[2 * i] = _unpack_dw(dw[:, n0:n0 + co], k, Cin)
                     if want_p[2 * i + 1]:
-                        grads[2 * i + 1] = db[n0:n0 + co].clone()
+                        grads[2 * i + 1] = db if n == 1 else db[n0:n0 + co].clone()
                     n0 += co
-            dx = None
-            if want_x:
-                wcat = torch.cat([w.detach().float() for w in params[0::2]], 0)
-                dx = torch.empty(B, H, W, Cin, dtype=torch.float32, device=dev)
-                _engine_conv(g, ldg, _pack_dgrad(wcat, ldg), None, ldg, Cin, k, k - 1 - pad, [(0, Cin, L.ACT_NONE, dx)])
+            dx = _data_grad(g, ldg, _cat_f32(ws), B, H, W, k, pad, stride, ctx.zero_insert) if want_x else None
         out = [dx] + grads
-        return (None, None, None) + tuple(None if t is None else t.to(dt) for t, dt in zip(out, ctx.dtypes))
+        return (None,) * 5 + tuple(None if t is None else t.to(dt) for t, dt in zip(out, ctx.dtypes))
+
+
+def _check_act_bias(who, act, bias):
+    if act not in ACTS:
+        raise NotImplementedError('yolact_amd %s: act = %r is not supported (None, \'relu\' and \'tanh\' are)' % (who, act))
+    if bias is None:
+        raise NotImplementedError('yolact_amd %s: bias = None is not supported (a biased convolution is)' % who)
+
+
+def _check_x(who, x, weight):
+    if x.dim() != 4 or x.shape[3] != weight.shape[1]:
+        raise ValueError('%s: x %s for a weight %s ([B,H,W,Cin] is expected)' % (who, tuple(x.shape), tuple(weight.shape)))
 
 
 def conv2d_multi(x, layers, padding, stride=1, dilation=1, groups=1):
@@ -195,10 +289,7 @@ def conv2d_multi(x, layers, padding, stride=1, dilation=1, groups=1):
     params, acts, geo = [], [], None
     for w, b, act in layers:
         L.require_cuda(w, 'conv2d_act weight')
-        if act not in ACTS:
-            raise NotImplementedError('yolact_amd conv2d_act: act = %r is not supported (None, \'relu\' and \'tanh\' are)' % (act,))
-        if b is None:
-            raise NotImplementedError('yolact_amd conv2d_act: bias = None is not supported (a biased convolution is)')
+        _check_act_bias('conv2d_act', act, b)
         g = check_conv(w, padding, stride, dilation, groups) + (int(w.shape[1]),)
         if geo is not None and g != geo:
             raise ValueError('conv2d_multi: the convolutions differ in geometry: %r and %r' % (geo, g))
@@ -209,12 +300,33 @@ def conv2d_multi(x, layers, padding, stride=1, dilation=1, groups=1):
         acts.append(ACTS[act])
     if x.shape[3] != geo[2]:
         raise ValueError('conv2d_act: x %s has %d channels, the weight takes %d' % (tuple(x.shape), x.shape[3], geo[2]))
-    return ConvMulti.apply(geo[0], geo[1], tuple(acts), x, *params)
+    return Conv.apply(geo[0], geo[1], 1, tuple(acts), False, x, *params)
 
 
 def conv2d_act(x, weight, bias, padding, act=None, stride=1, dilation=1, groups=1):
     """act(conv2d(x, weight, bias, padding)) on NHWC x -> NHWC."""
     return conv2d_multi(x, [(weight, bias, act)], padding, stride, dilation, groups)[0]
+
+
+def conv2d_down(x, weight, bias, act=None):
+    """act(conv2d(x, weight, bias, stride=2, padding=k // 2)) on NHWC x -> NHWC: 3 x 3 / pad 1 and 1 x 1 / pad 0, Cin % 32 == 0."""
+    L.require_cuda(x, 'conv2d_down x')
+    L.require_cuda(weight, 'conv2d_down weight')
+    _check_act_bias('conv2d_down', act, bias)
+    k, pad = check_down(weight)
+    _check_x('conv2d_down', x, weight)
+    if bias.numel() != weight.shape[0]:
+        raise ValueError('conv2d_down: weight %s / bias %s' % (tuple(weight.shape), tuple(bias.shape)))
+    return Conv.apply(k, pad, 2, (ACTS[act],), True, x, weight, bias)[0]
+
+
+def conv2d_plain(x, weight, stride=1):
+    """conv2d(x, weight, None, stride, padding=k // 2) on NHWC x -> NHWC: 3 x 3 / pad 1 and 1 x 1 / pad 0, stride 1 or 2, Cin % 32 == 0."""
+    L.require_cuda(x, 'conv2d_plain x')
+    L.require_cuda(weight, 'conv2d_plain weight')
+    k, pad, st = check_plain(weight, stride)
+    _check_x('conv2d_plain', x, weight)
+    return Conv.apply(k, pad, st, (L.ACT_NONE,), False, x, weight, None)[0]
 
 
 class Upsample2x(torch.autograd.Function):
@@ -256,97 +368,6 @@ def upsample2x(x, relu=False):
     if x.dim() != 4 or x.shape[3] % 4 != 0:
         raise NotImplementedError('yolact_amd upsample2x: x %s is not supported ([B,H,W,C] with C %% 4 == 0 is)' % (tuple(x.shape),))
     return Upsample2x.apply(x, bool(relu))
-
-
-def check_down(weight, who='conv2d_down'):
-    """NotImplementedError naming what of a stride-2 convolution's geometry the kernels do not take -> (k, pad = k // 2)."""
-    if weight.dim() != 4:
-        raise NotImplementedError('yolact_amd %s: a weight of shape %s is not supported ([Cout,Cin,k,k] is)' % (who, tuple(weight.shape)))
-    Cout, Cin, kh, kw = weight.shape
-    if (kh, kw) not in ((3, 3), (1, 1)):
-        raise NotImplementedError('yolact_amd %s: a %d x %d kernel at stride 2 is not supported (3 x 3 / padding 1 and 1 x 1 / '
-                                  'padding 0 are)' % (who, kh, kw))
-    if Cin % 32 != 0:
-        raise NotImplementedError('yolact_amd %s: Cin = %d is not supported (a multiple of 32 input channels is)' % (who, Cin))
-    return kh, kh // 2
-
-
-class ConvDown(torch.autograd.Function):
-    """apply(k, act, x [B,H,W,Cin], weight, bias) -> y [B,Ho,Wo,Cout], Ho = (H + 2 (k // 2) - k) // 2 + 1: a stride-2 convolution."""
-
-    @staticmethod
-    def forward(ctx, k, act, x, weight, bias):
-        dev = x.device
-        Cout, Cin = int(weight.shape[0]), int(weight.shape[1])
-        pad = k // 2
-        with torch.cuda.device(dev), torch.no_grad():
-            xd = LC.f32(x, dev)
-            B, H, W, _ = xd.shape
-            y = torch.empty(B, (H + 2 * pad - k) // 2 + 1, (W + 2 * pad - k) // 2 + 1, Cout, dtype=torch.float32, device=dev)
-            _engine_conv(xd, Cin, _pack_forward(weight.detach().float()), LC.f32(bias, dev), Cin, Cout, k, pad, [(0, Cout, act, y)],
-                         stride=2)
-        ctx.save_for_backward(x, weight, bias, y)          # (the inputs: autograd's version check)
-        ctx.k, ctx.act = k, act
-        ctx.dtypes = [x.dtype, weight.dtype, bias.dtype]
-        return y
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, dy):
-        want_x, want_w, want_b = ctx.needs_input_grad[2:]
-        x, weight, bias, y = ctx.saved_tensors
-        if not (want_x or want_w or want_b):
-            return (None,) * 5
-        dev = x.device
-        lib, s = L.lib(), L.stream_ptr()
-        k, pad = ctx.k, ctx.k // 2
-        with torch.cuda.device(dev), torch.no_grad():
-            xd = LC.f32(x, dev)
-            B, H, W, Cin = xd.shape
-            _, Ho, Wo, Cout = y.shape
-            ldg = _ceil(Cout, 32)
-            dyd = LC.f32(dy, dev)
-            g = torch.empty(B, Ho, Wo, ldg, dtype=torch.float32, device=dev)
-            L.check(lib.ymi_act_bwd_f32(y.data_ptr(), dyd.data_ptr(), g.data_ptr(), B * Ho * Wo, Cout, ldg, Cout, Cout, ldg, ctx.act, s),
-                    'ymi_act_bwd_f32')
-            dw = db = dx = None
-            if want_w or want_b:
-                d = L.ConvWgradDesc()
-                dwf = torch.empty(k * k * Cin, Cout, dtype=torch.float32, device=dev) if want_w else None
-                db = torch.empty(Cout, dtype=torch.float32, device=dev) if want_b else None
-                d.x, d.g = xd.data_ptr(), g.data_ptr()
-                d.dw, d.db = (None if t is None else t.data_ptr() for t in (dwf, db))
-                d.B, d.H, d.W, d.Cin, d.Cout, d.ldg, d.kh, d.kw, d.pad, d.stride = B, H, W, Cin, Cout, ldg, k, k, pad, 2
-                ws = LC.workspace('CONV_WGRAD', d, dev)
-                d.ws_bytes = ws.numel()
-                L.check(lib.ymi_conv_wgrad_nhwc_f32(C.byref(d), s), 'ymi_conv_wgrad_nhwc_f32')
-                if want_w:
-                    dw = dwf.reshape(k, k, Cin, Cout).permute(3, 2, 0, 1).contiguous()
-            if want_x:
-                # g with zeros between its pixels, exactly H x W (even and odd sizes), then the stride-1 data gradient: the added
-                # zeros change no bit of a sum, and a pixel no window reads (1x1) gets an exact +0.0.  Four times the useful FLOPs.
-                gz = torch.zeros(B, H, W, ldg, dtype=torch.float32, device=dev)
-                gz[:, ::2, ::2] = g
-                dx = torch.empty(B, H, W, Cin, dtype=torch.float32, device=dev)
-                _engine_conv(gz, ldg, _pack_dgrad(weight.detach().float(), ldg), None, ldg, Cin, k, k - 1 - pad, [(0, Cin, L.ACT_NONE, dx)])
-        out = [dx, dw, db]
-        return (None, None) + tuple(None if t is None else t.to(dt) for t, dt in zip(out, ctx.dtypes))
-
-
-def conv2d_down(x, weight, bias, act=None):
-    """act(conv2d(x, weight, bias, stride=2, padding=k // 2)) on NHWC x -> NHWC: 3 x 3 / pad 1 and 1 x 1 / pad 0, Cin % 32 == 0."""
-    L.require_cuda(x, 'conv2d_down x')
-    L.require_cuda(weight, 'conv2d_down weight')
-    if act not in ACTS:
-        raise NotImplementedError('yolact_amd conv2d_down: act = %r is not supported (None, \'relu\' and \'tanh\' are)' % (act,))
-    if bias is None:
-        raise NotImplementedError('yolact_amd conv2d_down: bias = None is not supported (a biased convolution is)')
-    k, _ = check_down(weight)
-    if x.dim() != 4 or x.shape[3] != weight.shape[1]:
-        raise ValueError('conv2d_down: x %s for a weight %s ([B,H,W,Cin] is expected)' % (tuple(x.shape), tuple(weight.shape)))
-    if bias.numel() != weight.shape[0]:
-        raise ValueError('conv2d_down: weight %s / bias %s' % (tuple(weight.shape), tuple(bias.shape)))
-    return ConvDown.apply(k, ACTS[act], x, weight, bias)
 
 
 class UpsampleAdd(torch.autograd.Function):
@@ -424,99 +445,6 @@ def share_params(n, params):
     params = list(params)
     flat = SharedParams.apply(n, *params)
     return [list(flat[u * len(params):(u + 1) * len(params)]) for u in range(n)]
-
-
-# ---- the backbone: bias-free convolutions, BatchNorm, the bottleneck ----------------------------------------------------------------------
-def check_plain(weight, stride, who='conv2d_plain'):
-    """NotImplementedError naming what of a bias-free convolution's geometry the kernels do not take -> (k, pad = k // 2, stride)."""
-    stride = (int(stride),) * 2 if isinstance(stride, int) else tuple(int(e) for e in stride)
-    if stride not in ((1, 1), (2, 2)):
-        raise NotImplementedError('yolact_amd %s: stride = %r is not supported (stride 1 and stride 2 are)' % (who, stride))
-    if stride == (2, 2):
-        return check_down(weight, who) + (2,)
-    if weight.dim() != 4:
-        raise NotImplementedError('yolact_amd %s: a weight of shape %s is not supported ([Cout,Cin,k,k] is)' % (who, tuple(weight.shape)))
-    k = int(weight.shape[2])
-    return check_conv(weight, k // 2, who=who) + (1,)
-
-
-def _pack_dgrad_s2(w, cpad):
-    """The filters of ymi_conv_dgrad_s2_nhwc_f32: [Cout,Cin,k,k] -> [k][k][cpad/4][Cin][4], Cout padded to cpad with zeros."""
-    Cout, Cin, k, _ = w.shape
-    t = F.pad(w.permute(2, 3, 0, 1), (0, 0, 0, cpad - Cout))                    # [k,k,cpad,Cin]
-    return t.reshape(k, k, cpad // 4, 4, Cin).permute(0, 1, 2, 4, 3).contiguous()
-
-
-class ConvPlain(torch.autograd.Function):
-    """apply(k, stride, x [B,H,W,Cin], weight) -> y [B,Ho,Wo,Cout], padding k // 2, no bias."""
-
-    @staticmethod
-    def forward(ctx, k, stride, x, weight):
-        dev = x.device
-        Cout, Cin = int(weight.shape[0]), int(weight.shape[1])
-        pad = k // 2
-        with torch.cuda.device(dev), torch.no_grad():
-            xd = LC.f32(x, dev)
-            B, H, W, _ = xd.shape
-            y = torch.empty(B, (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1, Cout, dtype=torch.float32, device=dev)
-            _engine_conv(xd, Cin, _pack_forward(weight.detach().float()), None, Cin, Cout, k, pad, [(0, Cout, L.ACT_NONE, y)],
-                         stride=stride)
-        ctx.save_for_backward(x, weight)                   # (the inputs: autograd's version check)
-        ctx.k, ctx.stride, ctx.oshape = k, stride, tuple(y.shape)
-        ctx.dtypes = [x.dtype, weight.dtype]
-        return y
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, dy):
-        want_x, want_w = ctx.needs_input_grad[2:]
-        x, weight = ctx.saved_tensors
-        if not (want_x or want_w):
-            return (None,) * 4
-        dev = x.device
-        lib, s = L.lib(), L.stream_ptr()
-        k, pad, stride = ctx.k, ctx.k // 2, ctx.stride
-        with torch.cuda.device(dev), torch.no_grad():
-            xd = LC.f32(x, dev)
-            B, H, W, Cin = xd.shape
-            _, Ho, Wo, Cout = ctx.oshape
-            ldg = _ceil(Cout, 32)
-            g = LC.f32(dy, dev)
-            if ldg != Cout:                                # (no backbone layer: their widths are multiples of 32)
-                g = F.pad(g, (0, ldg - Cout))
-            dw = dx = None
-            if want_w:
-                d = L.ConvWgradDesc()
-                dwf = torch.empty(k * k * Cin, Cout, dtype=torch.float32, device=dev)
-                d.x, d.g, d.dw, d.db = xd.data_ptr(), g.data_ptr(), dwf.data_ptr(), None
-                d.B, d.H, d.W, d.Cin, d.Cout, d.ldg, d.kh, d.kw, d.pad, d.stride = B, H, W, Cin, Cout, ldg, k, k, pad, stride
-                ws = LC.workspace('CONV_WGRAD', d, dev)
-                d.ws_bytes = ws.numel()
-                L.check(lib.ymi_conv_wgrad_nhwc_f32(C.byref(d), s), 'ymi_conv_wgrad_nhwc_f32')
-                dw = dwf.reshape(k, k, Cin, Cout).permute(3, 2, 0, 1).contiguous()
-            if want_x:
-                dx = torch.empty(B, H, W, Cin, dtype=torch.float32, device=dev)
-                wf = weight.detach().float()
-                if stride == 1:
-                    _engine_conv(g, ldg, _pack_dgrad(wf, ldg), None, ldg, Cin, k, k - 1 - pad, [(0, Cin, L.ACT_NONE, dx)])
-                else:
-                    wpk = _pack_dgrad_s2(wf, ldg)
-                    d = L.ConvDgradDesc()
-                    d.g, d.w, d.dx = g.data_ptr(), wpk.data_ptr(), dx.data_ptr()
-                    d.B, d.H, d.W, d.Cin, d.Cout, d.ldg, d.kh, d.kw, d.pad, d.stride = B, H, W, Cin, ldg, ldg, k, k, pad, 2
-                    L.check(lib.ymi_conv_dgrad_s2_nhwc_f32(C.byref(d), s), 'ymi_conv_dgrad_s2_nhwc_f32')
-        out = [dx, dw]
-        return (None, None) + tuple(None if t is None else t.to(dt) for t, dt in zip(out, ctx.dtypes))
-
-
-def conv2d_plain(x, weight, stride=1):
-    """conv2d(x, weight, None, stride, padding=k // 2) on NHWC x -> NHWC: 3 x 3 / pad 1 and 1 x 1 / pad 0, stride 1 or 2, Cin % 32 == 0."""
-    L.require_cuda(x, 'conv2d_plain x')
-    L.require_cuda(weight, 'conv2d_plain weight')
-    k, _, st = check_plain(weight, stride)
-    if x.dim() != 4 or x.shape[3] != weight.shape[1]:
-        raise ValueError('conv2d_plain: x %s for a weight %s ([B,H,W,Cin] is expected)' % (tuple(x.shape), tuple(weight.shape)))
-    return ConvPlain.apply(k, st, x, weight)
 
 
 class BnAct(torch.autograd.Function):
