@@ -894,6 +894,46 @@ typedef struct ymi_bn_desc {
 int ymi_bn_fwd_nhwc_f32(const ymi_bn_desc *d, void *stream);
 int ymi_bn_bwd_nhwc_f32(const ymi_bn_desc *d, void *stream);
 
+/* -- the backward of the train-mode ResNet stem (csrc/stem_train.hip; additive, the ABI number stays) -----------------------------------
+ * backbone.py:129-132: conv1 7x7 / stride 2 / pad 3 on 3 channels, bn1, ReLU, MaxPool2d(3, 2, 1).  The forward convolution is
+ * ymi_conv2d_nhwc_f32 with Cin = 4 (the fourth input channel of the filter zero), bn1 + ReLU are ymi_bn_fwd_nhwc_f32 / ymi_bn_bwd_nhwc_f32.
+ * No atomics; every element of every output is written exactly once; the same inputs give the same bits.
+ *
+ * ymi_stem_wgrad_nhwc_f32: dw[k,co] = sum_pos x[n, 2 oy + ky - 3, 2 ox + kx - 3, ci] g[pos,co], k = (ky*7 + kx)*3 + ci (147 rows),
+ * pos = [n, oy, ox] over the positions of g, Ho = [H - 1] / 2 + 1 and Wo likewise, reads outside the image are 0.  x is the NHWC-4 image
+ * the forward's Cin-4 loader reads; its channel 3 is padding and reaches no row of dw WHATEVER IT HOLDS (a select, never a product).
+ * On v_mfma_f32_32x32x2_f32 (fp32 in, fp32 accumulate) with the positions as its k index.  No data gradient: nothing upstream of the
+ * image needs one.
+ * SUMMATION ORDER (part of the contract, a function of the shape only): the positions n-major, then oy, then ox, are cut into chunks of
+ * per = 32 ceil(ceil(P / 32) / min(ceil(P / 32), ceil(512 / ceil(Cout / 64)))) positions, P = B Ho Wo.  A chunk's partial sum starts from
+ * +0.0 and takes its positions in ascending order two at a time: one instruction adds the two products of positions p and p + 1
+ * (p - chunk start even; a position outside the image or past the chunk contributes an exact 0 product).  The partials go to ws and a
+ * second launch adds them in chunk order from +0.0.
+ * YMI_ENULL: the descriptor, x, g, dw or ws NULL; YMI_EARG: B, H, W or Cout < 1; YMI_ESHAPE: Cout % 32, ldg < Cout, ldg % 4, x or g of
+ * 2^29 elements or more, ws not 16-byte aligned, ws_bytes too small.  No error path launches anything. */
+typedef struct ymi_stem_wgrad_desc {
+  const float *x;               /* [B,H,W,4] */
+  const float *g;               /* [B,Ho,Wo,ldg], channels [0, Cout) are read */
+  float *dw;                    /* [147, Cout] */
+  void *ws;                     /* ymi_workspace_bytes(YMI_WS_STEM_WGRAD, desc) bytes, 16-byte aligned */
+  int64_t ws_bytes;
+  int32_t B, H, W, Cout, ldg, _pad0;
+} ymi_stem_wgrad_desc;
+int ymi_stem_wgrad_nhwc_f32(const ymi_stem_wgrad_desc *d, void *stream);
+
+/* MaxPool2d(3, 2, 1) on x [B,H,W,C] NHWC fp32 and its backward, C % 4 == 0, any H, W >= 1: y, dy are [B,Hp,Wp,C], Hp = [H - 1] / 2 + 1.
+ * Padding never wins (a window always holds a real pixel).  TIE RULE (part of the contract): of equal maxima the FIRST in row-major
+ * window order (ky, then kx) is the maximum's place and takes the gradient, as PyTorch's max_pool2d does; NaN inputs are outside the
+ * contract.
+ * ymi_maxpool_bwd_nhwc_f32 is a gather that keeps no argmax plane: it RECOMPUTES the argmax of each window from x (the forward's input,
+ * unchanged since).  An input pixel lies in 1, 2, 2 or 4 windows by its row and column parity; it starts from +0.0 and adds dy of
+ * those windows whose argmax it is, output rows ascending, within a row output columns ascending.  No ReLU mask is applied here
+ * (ymi_bn_bwd_nhwc_f32 with relu = 1 applies it).
+ * YMI_ENULL: a NULL pointer; YMI_EARG: B, H, W or C < 1; YMI_ESHAPE: C % 4, 2^40 elements of x or more, a pointer not 16-byte aligned.
+ * No error path launches anything. */
+int ymi_maxpool_fwd_nhwc_f32(const float *x, float *y, int B, int H, int W, int C, void *stream);
+int ymi_maxpool_bwd_nhwc_f32(const float *x, const float *dy, float *dx, int B, int H, int W, int C, void *stream);
+
 /* -- ResNet stem in one launch (backbone.py:126-133 + the layout change of yolact.py:564) ---------------------------------
  * x [B,3,H,W] NCHW fp32 (the normalised image) -> conv 7x7 / 2 / pad 3 (3 -> 64) + folded BN + ReLU -> max-pool 3x3 / 2 / pad 1
  * -> y [B,Hp,Wp,64] NHWC fp32, Hp = ((H - 1) / 2 + 1 - 1) / 2 + 1.  The 64-channel stem output stays in LDS (csrc/stem.hip).
@@ -1029,8 +1069,9 @@ enum {
   YMI_WS_MASKIOU_HEAD = 23,     /* desc: ymi_maskiou_head_desc, N read -> its ws: N floats, padded to 16 */
   YMI_WS_CONV_WGRAD = 24,       /* desc: ymi_conv_wgrad_desc, the shape read -> its ws: chunks * kh*kw*Cin * Cout floats and chunks *
                                  * Cout floats, each part padded to 16 */
-  YMI_WS_BN = 25                /* desc: ymi_bn_desc, npos / C read -> its ws: 2 * chunks * C + 2 * C floats, chunks = ceil(npos / max(32,
+  YMI_WS_BN = 25,               /* desc: ymi_bn_desc, npos / C read -> its ws: 2 * chunks * C + 2 * C floats, chunks = ceil(npos / max(32,
                                  * ceil(npos / 1024))), each part padded to 16 */
+  YMI_WS_STEM_WGRAD = 26        /* desc: ymi_stem_wgrad_desc, the shape read -> its ws: chunks * 147 * Cout floats, padded to 16 */
 };
 typedef struct { int32_t A, B; int64_t n; } ymi_mask_iou_shape;
 typedef struct { int32_t N, h, w, cap; } ymi_rle_shape;      /* cap <= 0: the safe capacity h*w + 1 */

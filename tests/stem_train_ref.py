@@ -1,0 +1,141 @@
+"""The train-mode ResNet stem (backbone.py:77-80, 129-132: conv1 7x7 / stride 2 / padding 3 without a bias, bn1, ReLU,
+MaxPool2d(3, 2, 1)) in plain torch, written from the semantics.  The oracle of tests/test_stem_train_host.py (pinned there to what the
+reference's own ResNetBackbone object computed: tests/golden/stem_train.npz, tools/make_golden_stem_train.py) and of
+tests/test_gpu_stem_train.py.
+
+Everything works in the dtype given (fp32 or fp64) on the CPU, NCHW.  The parameters are a dict under the backbone's state-dict names:
+conv1.weight, bn1.weight, bn1.bias, bn1.running_mean, bn1.running_var.
+
+Decidability.  Two places of the stem decide something from a comparison, and a gradient goes one way or the other with it: the ReLU
+(is the pre-activation positive) and the max-pool (which element of a window is the largest).  A case is decidable when
+  (a) every ReLU pre-activation that receives gradient keeps `factor` times the fp32-versus-fp64 deviation of that tensor from 0, and
+  (b) in every pool window that receives gradient the maximum keeps `factor` times the deviation of the pool's input from the largest
+      smaller value of the window.  Equal maxima are allowed only at 0 (behind the ReLU, whose mask zeroes the gradient whichever
+      element takes it); anywhere else a tie counts as a margin of 0.
+"""
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+import helpers
+from backbone_train_ref import EPS, MOMENTUM, bn_ref  # noqa: F401
+from heads_train_ref import PARAM_GRID, assert_margins, grid, rel_err, tightest  # noqa: F401
+
+PARAM_NAMES = ('conv1.weight', 'bn1.weight', 'bn1.bias', 'bn1.running_mean', 'bn1.running_var')
+LEAVES = PARAM_NAMES[:3]
+STATS = PARAM_NAMES[3:]
+GOLDEN_X = (2, 3, 29, 23)          # conv 15 x 12, pool 8 x 6: odd and even extents
+GOLDEN_COUT = 64
+
+
+def conv_out(n):
+    return (n - 1) // 2 + 1          # 7 / 2 / 3 and 3 / 2 / 1 alike
+
+
+def stem_conv_ref(x, w):
+    return F.conv2d(x, w, None, stride=2, padding=3)
+
+
+def stem_ref(x, P, batch_stats, keep=None, new_stats=None, unbiased_running=True):
+    """backbone.py:129-132 -> the pooled map.  keep receives 'relu': (pre-activation, activation) and 'pool': (input, output);
+    new_stats the updated running statistics."""
+    z, nm, nv, _, _ = bn_ref(stem_conv_ref(x, P['conv1.weight']), P['bn1.weight'], P['bn1.bias'], P['bn1.running_mean'],
+                             P['bn1.running_var'], batch_stats, unbiased_running=unbiased_running)
+    if new_stats is not None:
+        new_stats['bn1.running_mean'], new_stats['bn1.running_var'] = nm, nv
+    a = F.relu(z)
+    y = F.max_pool2d(a, 3, 2, 1)
+    if keep is not None:
+        keep['relu'], keep['pool'] = (z, a), (a, y)
+    return y
+
+
+def run_ref(x, params, up, batch_stats, dtype, keep=None, **kw):
+    """Forward and the gradients of <y, up> -> dict('y', 'd_<name>' per parameter that takes a gradient, 'new_<name>' per running
+    statistic).  No gradient in x: the stem computes none."""
+    P = {n: params[n].detach().to(dtype) for n in PARAM_NAMES}
+    for n in LEAVES:
+        P[n].requires_grad_(True)
+    new_stats = {}
+    with helpers.oracle_threads():                       # torch's CPU summation order depends on the thread count
+        y = stem_ref(x.detach().to(dtype), P, batch_stats, keep, new_stats, **kw)
+        total = (y * up.to(dtype)).sum()
+        g = torch.autograd.grad(total, [P[n] for n in LEAVES], retain_graph=keep is not None)
+    res = {'y': y.detach()}
+    res.update({'d_' + n: t for n, t in zip(LEAVES, g)})
+    res.update({'new_' + n: t.detach() for n, t in new_stats.items()})
+    res['_total'] = total
+    return res
+
+
+def pool_gaps(a, hit):
+    """a [B,C,H,W]: the input of MaxPool2d(3, 2, 1); hit [B,C,Hp,Wp] bool: the windows that receive gradient -> the smallest gap between
+    a window's maximum and its largest smaller value over those windows (inf when there is none).  Equal maxima away from 0: 0."""
+    B, Cc, H, W = a.shape
+    win = F.unfold(F.pad(a, (1, 1, 1, 1), value=float('-inf')), 3, stride=2).view(B, Cc, 9, -1)
+    m = win.max(2, keepdim=True).values
+    below = torch.where(win < m, win, torch.full_like(win, float('-inf'))).max(2).values
+    gap = m.squeeze(2) - below                           # inf where nothing is smaller
+    tied = ((win == m).sum(2) > 1) & (m.squeeze(2) != 0)
+    gap = torch.where(tied, torch.zeros_like(gap), gap)
+    hit = hit.reshape(B, Cc, -1)
+    assert hit.shape == gap.shape
+    return gap[hit].min().item() if hit.any() else float('inf')
+
+
+def margins(x, params, up, batch_stats):
+    """[('relu', smallest |pre-activation| whose activation receives gradient (fp64), largest fp32-versus-fp64 deviation of the
+    pre-activation), ('pool', smallest gap of a window that receives gradient (fp64), largest deviation of the pool's input)]."""
+    res = {}
+    with helpers.oracle_threads():
+        for dtype in (torch.float64, torch.float32):
+            keep = {}
+            r = run_ref(x, params, up, batch_stats, dtype, keep)
+            (z, a), (_, y) = keep['relu'], keep['pool']
+            ga, gy = torch.autograd.grad(r['_total'], [a, y], allow_unused=True)
+            res[dtype] = (z.detach(), a.detach(), ga, gy)
+    z64, a64, ga, gy = res[torch.float64]
+    z32, a32 = res[torch.float32][:2]
+    hit = ga != 0
+    return [('relu', z64[hit].abs().min().item() if hit.any() else float('inf'), (z32.double() - z64).abs().max().item()),
+            ('pool', pool_gaps(a64, gy != 0), (a32.double() - a64).abs().max().item())]
+
+
+def random_params(g, cout=GOLDEN_COUT):
+    """On fp16-exact grids: conv1.weight ~ N(0, 2 / 147) in 1/2048, gamma and running_var in [0.5, 1.5] in 1/1024, beta ~ N(0, 0.1) and
+    running_mean ~ N(0, 0.25) in 1/2048: non-trivial running statistics."""
+    return {'conv1.weight': grid((torch.randn(cout, 3, 7, 7, generator=g) * (2.0 / 147) ** 0.5).clamp(-0.9, 0.9), PARAM_GRID),
+            'bn1.weight': grid(0.5 + torch.rand(cout, generator=g), 1024),
+            'bn1.bias': grid((torch.randn(cout, generator=g) * 0.1).clamp(-0.9, 0.9), PARAM_GRID),
+            'bn1.running_mean': grid((torch.randn(cout, generator=g) * 0.25).clamp(-0.9, 0.9), PARAM_GRID),
+            'bn1.running_var': grid(0.5 + torch.rand(cout, generator=g), 1024)}
+
+
+def random_case(seed, xshape=GOLDEN_X, cout=GOLDEN_COUT):
+    """-> (x, params, up): the image ~ N(0, 1) in 1/256, the upstream gradient of the pooled map in {-1, -1/2, 0, 1/2, 1}."""
+    g = torch.Generator().manual_seed(seed)
+    x = grid(torch.randn(*xshape, generator=g).clamp(-4, 4), 256)
+    params = random_params(g, cout)
+    up = torch.randint(-2, 3, (xshape[0], cout, conv_out(conv_out(xshape[2])), conv_out(conv_out(xshape[3]))), generator=g).float() / 2
+    return x, params, up
+
+
+def find_seed(xshape=GOLDEN_X, cout=GOLDEN_COUT, modes=(False, True), first=1, last=200, factor=16):
+    """The first seed whose case keeps `factor` times the fp32 deviation at the ReLU and in every pool window, in every mode ->
+    (seed, tried)."""
+    for seed in range(first, last + 1):
+        x, params, up = random_case(seed, xshape, cout)
+        if all(all(lo >= factor * dev for _, lo, dev in margins(x, params, up, m)) for m in modes):
+            return seed, seed - first + 1
+    raise AssertionError('no seed in %d .. %d keeps the margin' % (first, last))
+
+
+# ---- the stored reference results ---------------------------------------------------------------------------------------------------
+def load_golden():
+    """tests/golden/stem_train.npz -> (meta, x, params {name: fp32}, up, want {'eval' / 'train': {name: fp32}})."""
+    meta, z = helpers.load_golden('stem_train')
+    x = torch.from_numpy(z['x'].astype(np.float32))
+    params = {n: torch.from_numpy(z['p_' + n].astype(np.float32)) for n in meta['params']}
+    up = torch.from_numpy(z['up'].astype(np.float32))
+    want = {mode: {k[len(mode) + 1:]: torch.from_numpy(z[k]) for k in z if k.startswith(mode + '_')} for mode in ('eval', 'train')}
+    return meta, x, params, up, want

@@ -196,6 +196,12 @@ class BnDesc(C.Structure):
                 ('_pad0', C.c_int32)]
 
 
+class StemWgradDesc(C.Structure):
+    """include/yolact_amd.h ymi_stem_wgrad_desc."""
+    _fields_ = [('x', C.c_void_p), ('g', C.c_void_p), ('dw', C.c_void_p), ('ws', C.c_void_p), ('ws_bytes', C.c_int64),
+                ('B', C.c_int32), ('H', C.c_int32), ('W', C.c_int32), ('Cout', C.c_int32), ('ldg', C.c_int32), ('_pad0', C.c_int32)]
+
+
 class DetectDesc(C.Structure):
     _fields_ = [('conf', C.c_void_p), ('loc', C.c_void_p), ('coef', C.c_void_p), ('priors', C.c_void_p),
                 ('B', C.c_int32), ('P', C.c_int32), ('C', C.c_int32), ('D', C.c_int32),
@@ -291,7 +297,7 @@ class RleShape(C.Structure):
 (WS_WINO_V, WS_WINO_M, WS_SPLITK, WS_MASK_IOU, WS_JPEG_COEFS, WS_JPEG_PLANES, WS_DETECT_SCORES_T, WS_DETECT_PER_PRIOR,
  WS_DETECT_CAND, WS_DETECT_REC, WS_AMAX_SLOT, WS_RLE_COUNTS, WS_DETECT_GREEDY, WS_JPEG_ENC, WS_JPEG_ENC_OUT,
  WS_MASK_LOSS, WS_MATCH, WS_BOX_LOSS, WS_CLASS_LOSS, WS_SEGM_LOSS, WS_MASKIOU_INPUT, WS_CONV_BWD, WS_MASKIOU_HEAD,
- WS_CONV_WGRAD, WS_BN) = range(1, 26)
+ WS_CONV_WGRAD, WS_BN, WS_STEM_WGRAD) = range(1, 27)
 
 EFORMAT, EUNSUPPORTED = -4, -5
 UP_FLAT, UP_BAND, UP_ROWS16, UP_ROWS32 = 1, 2, 3, 4       # ymi_mask_upsample_kernel (include/yolact_amd.h YMI_UP_*)
@@ -340,6 +346,9 @@ SYMBOLS = [
     ('ymi_conv_dgrad_s2_nhwc_f32', C.c_int, [C.POINTER(ConvDgradDesc), _P]),
     ('ymi_bn_fwd_nhwc_f32', C.c_int, [C.POINTER(BnDesc), _P]),
     ('ymi_bn_bwd_nhwc_f32', C.c_int, [C.POINTER(BnDesc), _P]),
+    ('ymi_stem_wgrad_nhwc_f32', C.c_int, [C.POINTER(StemWgradDesc), _P]),
+    ('ymi_maxpool_fwd_nhwc_f32', C.c_int, [_P, _P, _I, _I, _I, _I, _P]),
+    ('ymi_maxpool_bwd_nhwc_f32', C.c_int, [_P, _P, _P, _I, _I, _I, _I, _P]),
     ('ymi_bilinear_bwd_nhwc_f32', C.c_int, [_P, _P, _P] + [_I] * 7 + [_P]),
     ('ymi_bilinear_size_bwd_nhwc_f32', C.c_int, [_P, _P] + [_I] * 6 + [_P]),
     ('ymi_composite_masks_u8', C.c_int, [_P, _P, _P, _I, _I, _I, _F, _P, _P]),

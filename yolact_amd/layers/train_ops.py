@@ -1,5 +1,5 @@
-"""Differentiable building blocks of the train-mode heads, protonet, FPN and ResNet stages on the HIP kernels (csrc/conv_train.hip,
-csrc/conv_dgrad.hip, csrc/bn_train.hip and the conv engine).
+"""Differentiable building blocks of the train-mode heads, protonet, FPN, ResNet stages and ResNet stem on the HIP kernels
+(csrc/conv_train.hip, csrc/conv_dgrad.hip, csrc/bn_train.hip, csrc/stem_train.hip and the conv engine).
 
     conv2d_act(x, weight, bias, padding, act)            -> y [B,H,W,Cout]: act(conv(x, weight) + bias), act in {None, 'relu', 'tanh'}
     conv2d_multi(x, [(weight, bias, act), ..], padding)  -> one y per entry: up to three convolutions of the SAME input as one launch
@@ -13,6 +13,9 @@ csrc/conv_dgrad.hip, csrc/bn_train.hip and the conv engine).
                                                             FPN's top-down sum, yolact.py:332-334), any size of lat >= that of top
     batch_norm_act(x, bn, batch_stats, residual, relu)   -> relu(bn(x) + residual) for an nn.BatchNorm2d, batch statistics or frozen
     bottleneck(x, block, batch_stats)                    -> a modules.Bottleneck (backbone.py:37-57); bn3 + shortcut + ReLU are one launch
+    stem_conv(x4, weight)                                -> [B,Ho,Wo,Cout]: the stem's 7x7 / stride 2 / padding 3 convolution of 3 channels
+                                                            (backbone.py:77) on the image padded to 4 channels, x4 [B,H,W,4]
+    max_pool_3x3_s2(x)                                   -> [B,Hp,Wp,C]: F.max_pool2d(x, 3, 2, 1) (backbone.py:80)
 
 x and the results are NHWC fp32 GPU tensors; weight and bias are nn.Conv2d parameters in torch layout.  Everything is once
 differentiable in x, every weight and every bias.  Each call packs its filters from the CURRENT parameter values (a permute; no
@@ -33,6 +36,11 @@ raises NotImplementedError naming it.  Forward: one ymi_conv2d_nhwc_f32 launch o
        grids, so the FPN keeps its own until it is moved over on purpose; zero_insert and its branch then go.
 upsample_add: d_lat = dy, d_top = ymi_bilinear_size_bwd_nhwc_f32 (a gather in a fixed order).  batch_norm_act: ymi_bn_fwd_nhwc_f32 /
 ymi_bn_bwd_nhwc_f32 (csrc/bn_train.hip).
+stem_conv: one ymi_conv2d_nhwc_f32 launch through the engine's Cin-4 loader with the filter's fourth input channel zero; the backward
+is ymi_stem_wgrad_nhwc_f32 on the SAME x4 (its fourth channel reaches nothing), then _unpack_dw.  It is differentiable in the weight
+only: an x4 that requires grad raises, since nothing upstream of the image needs a gradient and returning None would silently give a
+zero one.  max_pool_3x3_s2: ymi_maxpool_fwd_nhwc_f32 / ymi_maxpool_bwd_nhwc_f32 (csrc/stem_train.hip); the backward recomputes each
+window's argmax from the saved input, the first of equal maxima in row-major window order taking the gradient as in PyTorch.
 """
 from __future__ import annotations
 
@@ -103,13 +111,14 @@ def check_plain(weight, stride, who='conv2d_plain'):
 
 
 def _engine_conv(x, ldx, wpk, bias, Cin, Cout, k, pad, segs, stride=1):
-    """One ymi_conv2d_nhwc_f32 launch on the exact-fp32 tiles: x [B,H,W,ldx], wpk [CoutPad][k*k*Cin], segs = (n0, n1, act, tensor)."""
+    """One ymi_conv2d_nhwc_f32 launch on the exact-fp32 tiles: x [B,H,W,ldx], wpk [CoutPad][Kpad], Kpad = k*k*Cin or, for the Cin-4
+    loader, its ceil32; segs = (n0, n1, act, tensor)."""
     B, H, W = x.shape[:3]
     Ho, Wo = _out_size(H, W, k, pad, stride)
     d = L.ConvDesc()
     d.x, d.w, d.bias = x.data_ptr(), wpk.data_ptr(), (None if bias is None else bias.data_ptr())
     d.B, d.H, d.W, d.Cin, d.ldx, d.Ho, d.Wo, d.Cout = B, H, W, Cin, ldx, Ho, Wo, Cout
-    d.kh, d.kw, d.stride, d.pad, d.Kpad, d.tile = k, k, stride, pad, k * k * Cin, L.TILE_AUTO
+    d.kh, d.kw, d.stride, d.pad, d.Kpad, d.tile = k, k, stride, pad, int(wpk.shape[1]), L.TILE_AUTO
     d.nseg = len(segs)
     for i, (n0, n1, act, y) in enumerate(segs):
         d.seg[i] = L.ConvSeg(n0, n1, act, n1 - n0, Ho * Wo * (n1 - n0), y.data_ptr())
@@ -577,3 +586,132 @@ def bottleneck(x, block, batch_stats=None):
     if block.downsample is not None:
         res = batch_norm_act(conv2d_plain(x, block.downsample[0].weight, block.stride), block.downsample[1], batch_stats)
     return batch_norm_act(out, block.bn3, batch_stats, residual=res, relu=True)
+
+
+STEM_K, STEM_PAD, STEM_STRIDE = 7, 3, 2
+
+
+def check_stem(weight, stride=2, padding=3, dilation=1, groups=1, bias=None, who='stem_conv'):
+    """NotImplementedError naming what of the stem convolution the kernels do not take: anything but a bias-free 7 x 7 / stride 2 /
+    padding 3 / dilation 1 / groups 1 convolution of 3 input channels."""
+    pair = lambda v: (int(v), int(v)) if isinstance(v, int) else tuple(int(e) for e in v)
+    if weight.dim() != 4:
+        raise NotImplementedError('yolact_amd %s: a weight of shape %s is not supported ([Cout,3,7,7] is)' % (who, tuple(weight.shape)))
+    Cout, Cin, kh, kw = weight.shape
+    if (kh, kw) != (STEM_K, STEM_K):
+        raise NotImplementedError('yolact_amd %s: a %d x %d kernel is not supported (7 x 7 is)' % (who, kh, kw))
+    if isinstance(stride, str) or pair(stride) != (STEM_STRIDE, STEM_STRIDE):
+        raise NotImplementedError('yolact_amd %s: stride = %r is not supported (stride 2 is)' % (who, stride))
+    if isinstance(padding, str) or pair(padding) != (STEM_PAD, STEM_PAD):
+        raise NotImplementedError('yolact_amd %s: padding = %r is not supported (padding 3 is)' % (who, padding))
+    if pair(dilation) != (1, 1):
+        raise NotImplementedError('yolact_amd %s: dilation = %r is not supported (dilation 1 is)' % (who, dilation))
+    if groups != 1:
+        raise NotImplementedError('yolact_amd %s: groups = %r is not supported (groups 1 is)' % (who, groups))
+    if Cin != 3:
+        raise NotImplementedError('yolact_amd %s: Cin = %d is not supported (3 input channels are, on an input padded to 4)' % (who, Cin))
+    if bias is not None:
+        raise NotImplementedError('yolact_amd %s: a bias is not supported (a bias-free convolution is)' % who)
+    if Cout % 32 != 0:
+        raise NotImplementedError('yolact_amd %s: Cout = %d is not supported (a multiple of 32 output channels is)' % (who, Cout))
+
+
+def _pack_stem(w):
+    """[Cout,3,7,7] -> [ceil128(Cout)][224], k = (ky*7 + kx)*4 + c with c = 3 and k >= 196 zero (a permute of the CURRENT values)."""
+    Cout = int(w.shape[0])
+    out = torch.zeros(_ceil(Cout, 128), _ceil(STEM_K * STEM_K * 4, 32), dtype=torch.float32, device=w.device)
+    out[:Cout, :STEM_K * STEM_K * 4] = F.pad(w.permute(0, 2, 3, 1), (0, 1)).reshape(Cout, STEM_K * STEM_K * 4)
+    return out
+
+
+class StemConv(torch.autograd.Function):
+    """apply(x4 [B,H,W,4], weight [Cout,3,7,7]) -> [B,Ho,Wo,Cout]; differentiable in the weight."""
+
+    @staticmethod
+    def forward(ctx, x4, weight):
+        dev = x4.device
+        Cout = int(weight.shape[0])
+        with torch.cuda.device(dev), torch.no_grad():
+            xd = LC.f32(x4, dev)
+            B, H, W, _ = xd.shape
+            Ho, Wo = _out_size(H, W, STEM_K, STEM_PAD, STEM_STRIDE)
+            y = torch.empty(B, Ho, Wo, Cout, dtype=torch.float32, device=dev)
+            _engine_conv(xd, 4, _pack_stem(weight.detach().float()), None, 4, Cout, STEM_K, STEM_PAD, [(0, Cout, L.ACT_NONE, y)],
+                         stride=STEM_STRIDE)
+        ctx.save_for_backward(x4, weight)                   # (the version check)
+        ctx.dtype = weight.dtype
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        x4, weight = ctx.saved_tensors                      # (the version check)
+        if not ctx.needs_input_grad[1]:
+            return None, None
+        dev = x4.device
+        Cout = int(weight.shape[0])
+        with torch.cuda.device(dev), torch.no_grad():
+            xd, g = LC.f32(x4, dev), LC.f32(dy, dev)
+            B, H, W, _ = xd.shape
+            dw = torch.empty(STEM_K * STEM_K * 3, Cout, dtype=torch.float32, device=dev)
+            d = L.StemWgradDesc()
+            d.x, d.g, d.dw = xd.data_ptr(), g.data_ptr(), dw.data_ptr()
+            d.B, d.H, d.W, d.Cout, d.ldg = B, H, W, Cout, Cout
+            ws = LC.workspace('STEM_WGRAD', d, dev)
+            d.ws_bytes = ws.numel()
+            L.check(L.lib().ymi_stem_wgrad_nhwc_f32(C.byref(d), L.stream_ptr()), 'ymi_stem_wgrad_nhwc_f32')
+            out = _unpack_dw(dw, STEM_K, 3)
+        return None, out.to(ctx.dtype)
+
+
+def stem_conv(x4, weight, bias=None, stride=2, padding=3, dilation=1, groups=1):
+    """conv2d(x, weight, None, stride 2, padding 3) for a [Cout,3,7,7] weight on x4 [B,H,W,4], the NHWC image with a fourth channel of
+    zeros -> NHWC.  Differentiable in the weight only."""
+    L.require_cuda(x4, 'stem_conv x4')
+    L.require_cuda(weight, 'stem_conv weight')
+    check_stem(weight, stride, padding, dilation, groups, bias)
+    if x4.dim() != 4 or x4.shape[3] != 4:
+        raise ValueError('stem_conv: x4 %s ([B,H,W,4], the image padded to 4 channels, is expected)' % (tuple(x4.shape),))
+    if x4.requires_grad:
+        raise NotImplementedError('yolact_amd stem_conv: an x4 that requires grad is not supported (the gradient with respect to the '
+                                  'image is not computed; detach it)')
+    return StemConv.apply(x4, weight)
+
+
+class MaxPool3x3S2(torch.autograd.Function):
+    """apply(x [B,H,W,C]) -> [B,Hp,Wp,C]."""
+
+    @staticmethod
+    def forward(ctx, x):
+        dev = x.device
+        with torch.cuda.device(dev), torch.no_grad():
+            xd = LC.f32(x, dev)
+            B, H, W, Cc = xd.shape
+            y = torch.empty(B, (H - 1) // 2 + 1, (W - 1) // 2 + 1, Cc, dtype=torch.float32, device=dev)
+            L.check(L.lib().ymi_maxpool_fwd_nhwc_f32(xd.data_ptr(), y.data_ptr(), B, H, W, Cc, L.stream_ptr()), 'ymi_maxpool_fwd_nhwc_f32')
+        ctx.save_for_backward(x)                            # the backward finds the argmax in it again; (the version check)
+        ctx.dtype = x.dtype
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        (x,) = ctx.saved_tensors                            # (the version check)
+        if not ctx.needs_input_grad[0]:
+            return None
+        dev = x.device
+        with torch.cuda.device(dev), torch.no_grad():
+            xd, dyd = LC.f32(x, dev), LC.f32(dy, dev)
+            B, H, W, Cc = xd.shape
+            dx = torch.empty_like(xd)
+            L.check(L.lib().ymi_maxpool_bwd_nhwc_f32(xd.data_ptr(), dyd.data_ptr(), dx.data_ptr(), B, H, W, Cc, L.stream_ptr()),
+                    'ymi_maxpool_bwd_nhwc_f32')
+        return dx.to(ctx.dtype)
+
+
+def max_pool_3x3_s2(x):
+    """F.max_pool2d(x, 3, 2, 1) on NHWC x -> NHWC; of equal maxima the first in row-major window order takes the gradient."""
+    L.require_cuda(x, 'max_pool_3x3_s2 x')
+    if x.dim() != 4 or x.shape[3] % 4 != 0 or min(x.shape) < 1:
+        raise NotImplementedError('yolact_amd max_pool_3x3_s2: x %s is not supported ([B,H,W,C] with C %% 4 == 0 is)' % (tuple(x.shape),))
+    return MaxPool3x3S2.apply(x)

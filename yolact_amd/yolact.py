@@ -586,6 +586,42 @@ class Yolact(nn.Module):
                 outs.append(x.permute(0, 3, 1, 2))
         return outs
 
+    def forward_stem(self, x, batch_stats=None):
+        """The reference's ResNet stem (backbone.py:129-132: conv1, bn1, ReLU, max-pool) on x [B,3,H,W] NCHW fp32 on the GPU, the
+        normalised image forward() takes -> [B,64,Hp,Wp], what forward_backbone starts from, as a permuted view of NHWC storage (so
+        forward_backbone copies nothing).  The image is padded to NHWC with a fourth channel of zeros once, with torch operations; the
+        convolution's backward reads that same tensor.  Once differentiable in conv1.weight and in bn1's affine parameters where they
+        require grad; no gradient reaches the image.  batch_stats as in forward_backbone.  Needs no plan and reads cfg at call time; the
+        model stays in eval mode and forward() is untouched.  A DarkNet backbone raises NotImplementedError naming it."""
+        from .layers import train_ops as TO
+        from .modules import ResNetBackbone
+        bb = self.backbone
+        if not isinstance(bb, ResNetBackbone):
+            raise NotImplementedError('yolact_amd forward_stem: a %s is not supported (a ResNetBackbone is)' % type(bb).__name__)
+        c1 = bb.conv1
+        TO.check_stem(c1.weight, c1.stride, c1.padding, c1.dilation, c1.groups, c1.bias, 'forward_stem backbone.conv1')
+        L.require_cuda(x, 'forward_stem image batch')
+        if x.dim() != 4 or x.shape[1] != 3:
+            raise ValueError('forward_stem: expected [B,3,H,W], got %s' % (tuple(x.shape),))
+        with torch.cuda.device(x.device):
+            x4 = nn.functional.pad(x.detach().to(torch.float32).permute(0, 2, 3, 1), (0, 1)).contiguous()
+            y = TO.stem_conv(x4, c1.weight)
+            y = TO.batch_norm_act(y, bb.bn1, batch_stats, relu=True)
+            y = TO.max_pool_3x3_s2(y)
+        return y.permute(0, 3, 1, 2)
+
+    def forward_train(self, x, batch_stats=None):
+        """The reference's TRAIN-mode Yolact.forward (yolact.py:564-647) from the image batch x [B,3,H,W] to pred_outs, what MultiBoxLoss
+        takes as it stands: forward_heads(forward_fpn(selected(forward_backbone(forward_stem(x))))), differentiable in every parameter
+        those four are.  batch_stats as in forward_backbone.  The model stays in eval mode (train() raises)."""
+        cfg = self.cfg
+        L.require_cuda(x, 'input batch')
+        if x.dim() != 4 or x.shape[1] != 3:
+            raise ValueError('expected [B,3,H,W], got %s' % (tuple(x.shape),))
+        cfg._tmp_img_h, cfg._tmp_img_w = int(x.shape[2]), int(x.shape[3])
+        outs = self.forward_backbone(self.forward_stem(x, batch_stats), batch_stats)
+        return self.forward_heads(self.forward_fpn([outs[i] for i in cfg.backbone.selected_layers]))
+
     def forward_raw(self, x):
         """Head outputs before Detect (for parity tests): loc, conf (logits), mask, priors, proto — clones."""
         L.require_cuda(x, 'input batch')
