@@ -26,7 +26,7 @@ import heads_train_ref as H  # noqa: E402
 import helpers  # noqa: E402
 import train_helpers  # noqa: E402
 from helpers import rel_err, same_bits  # noqa: E402
-from train_helpers import DEV, EXACT_BAR, STORED_SLACK, down, guarded, nan_padded, twice, unguard  # noqa: E402
+from train_helpers import DEV, EXACT_BAR, STORED_SLACK, down, guarded, nan_padded, twice, unguard, zero_insert_gpu  # noqa: E402
 import yolact_amd  # noqa: E402
 from yolact_amd import _lib as L  # noqa: E402
 from yolact_amd import modules as M  # noqa: E402
@@ -81,18 +81,6 @@ def dgrad_gpu(gpad, w, Hh, W):
     L.check(L.lib().ymi_conv_dgrad_s2_nhwc_f32(C.byref(d), L.stream_ptr()), 'dgrad s2')
     torch.cuda.synchronize()
     return unguard(buf, (B, Hh, W, Cin))
-
-
-def zero_insert_gpu(g, w, Hh, W):
-    """The route of conv2d_down's data gradient (train_ops._data_grad with zero_insert): g spread over a zeroed H x W map, then the stride-1 data gradient on the engine."""
-    Cout, Cin, k, _ = w.shape
-    B = g.shape[0]
-    gz = torch.zeros(B, Hh, W, Cout, device=DEV)
-    gz[:, ::2, ::2] = g.to(DEV)
-    dx = torch.empty(B, Hh, W, Cin, device=DEV)
-    TO._engine_conv(gz, Cout, TO._pack_dgrad(w.to(DEV), Cout), None, Cout, Cin, k, k - 1 - k // 2, [(0, Cin, L.ACT_NONE, dx)])
-    torch.cuda.synchronize()
-    return dx.cpu()
 
 
 def dgrad_oracle(g, w, Hh, W, dtype):

@@ -27,7 +27,7 @@ import class_loss_ref as CR  # noqa: E402
 import helpers  # noqa: E402
 import train_helpers  # noqa: E402
 from helpers import rel_err, same_bits  # noqa: E402
-from train_helpers import DEV, EXACT_BAR, STORED_SLACK, down, grid_randn, guarded, twice, unguard  # noqa: E402
+from train_helpers import DEV, EXACT_BAR, STORED_SLACK, down, grid_randn, guarded, twice, unguard, zero_insert_gpu  # noqa: E402
 import yolact_amd  # noqa: E402
 from yolact_amd import _lib as L  # noqa: E402
 from yolact_amd import modules as M  # noqa: E402
@@ -41,6 +41,9 @@ UP_SHAPES = [((4, 3), (7, 5)), ((7, 5), (13, 10)), ((1, 1), (2, 3)), ((5, 7), (1
 # (kernel, B, H, W, Cin, Cout) at stride 2: odd extents with every window at a border and Cout < 32; even extents; 1x1; 2 * 19 * 21 =
 # 798 positions: several chunks with a ragged last one
 WG2_SHAPES = [(3, 2, 5, 7, 32, 12), (3, 1, 8, 6, 64, 40), (1, 2, 7, 9, 64, 32), (3, 2, 37, 41, 32, 96)]
+# conv2d_down: the first three, and mixed parity with a padded width: odd H, even W (the last odd column has a masked tap), ldg 64 with
+# 24 zero channels that must contribute nothing (SEEDS['conv'] keeps the ReLU margin here too: checked on the CPU)
+DOWN_SHAPES = WG2_SHAPES[:3] + [(3, 1, 5, 6, 32, 40)]
 REAL_SIZES = [(5, 5), (3, 3), (2, 2)]
 _MAX = {}
 compare = functools.partial(train_helpers.compare, _MAX)
@@ -175,7 +178,7 @@ def down_oracle(x, w, b, up, k, act, dtype):
 
 
 @pytest.mark.parametrize('act', [None, 'relu', 'tanh'], ids=['none', 'relu', 'tanh'])
-@pytest.mark.parametrize('shape', WG2_SHAPES[:3], ids=['3x3_5x7_32to12', '3x3_8x6_64to40', '1x1_7x9_64to32'])
+@pytest.mark.parametrize('shape', DOWN_SHAPES, ids=['3x3_5x7_32to12', '3x3_8x6_64to40', '1x1_7x9_64to32', '3x3_5x6_32to40'])
 def test_conv2d_down_through_autograd(shape, act):
     k = shape[0]
     x, w, b, up = down_case(shape, SEEDS['conv'])
@@ -194,6 +197,9 @@ def test_conv2d_down_through_autograd(shape, act):
         return dict(y=y.detach().cpu(), dx=gr[0].cpu(), dw=gr[1].cpu(), db=gr[2].cpu())
     got = twice(run)
     compare('down_%s_%dx%d_%dx%d' % (act, k, k, shape[2], shape[3]), got, o64, o32)
+    if act != 'tanh':      # exact grids (up in halves, a ReLU mask): dx has the bits of the spread-then-stride-1 route on this g
+        g = up if act is None else up * (got['y'] > 0)
+        same_bits(got['dx'], zero_insert_gpu(g, w, shape[2], shape[3]), 'the zero-insert route')
     if k == 1:      # the pixels no window reads: an exact +0.0
         unread = torch.ones(shape[2], shape[3], dtype=torch.bool)
         unread[::2, ::2] = False

@@ -4,6 +4,8 @@ import torch
 
 import heads_train_ref as H
 from helpers import rel_err, same_bits
+from yolact_amd import _lib as L
+from yolact_amd.layers import train_ops as TO
 
 DEV = 'cuda:0'
 EXACT_BAR = 8e-6
@@ -59,3 +61,19 @@ def nan_padded(g):
     gpad = torch.full(tuple(g.shape[:3]) + (g.shape[3] + 32,), float('nan'))          # the padding channels are never read
     gpad[..., :g.shape[3]] = g
     return gpad.to(DEV)
+
+
+def zero_insert_gpu(g, w, Hh, W):
+    """The route of conv2d_down's data gradient (train_ops._data_grad with zero_insert), built here from its parts, and what
+    ymi_conv_dgrad_s2_nhwc_f32 is compared with: g [B,Ho,Wo,Cout] spread over a zeroed H x W map, then the stride-1 data gradient
+    with the flipped filter on the engine -> dx on the CPU.  The added zeros change no bit of a sum, and a pixel no window reads
+    (1x1) gets an exact +0.0."""
+    Cout, Cin, k, _ = w.shape
+    B = g.shape[0]
+    ld = (Cout + 31) // 32 * 32                      # the engine takes multiples of 32 channels: zero channels, zero filter columns
+    gz = torch.zeros(B, Hh, W, ld, device=DEV)
+    gz[:, ::2, ::2, :Cout] = g.to(DEV)
+    dx = torch.empty(B, Hh, W, Cin, device=DEV)
+    TO._engine_conv(gz, ld, TO._pack_dgrad(w.to(DEV), ld), None, ld, Cin, k, k - 1 - k // 2, [(0, Cin, L.ACT_NONE, dx)])
+    torch.cuda.synchronize()
+    return dx.cpu()

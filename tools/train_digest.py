@@ -1,9 +1,12 @@
 #!/usr/bin/env python3
 """One SHA-256 per output tensor of the train-mode building blocks (yolact_amd/layers/train_ops.py) on fixed inputs: two trees whose
 lines are equal issue the same launches on the same operands.  Only public functions are called (conv2d_act, conv2d_multi,
-conv2d_down, conv2d_plain, bottleneck, upsample2x, upsample_add, batch_norm_act), so the script runs unchanged on an older tree.  The
-shapes are the small ones of tests/test_gpu_heads_train.py, tests/test_gpu_fpn_train.py and tests/test_gpu_backbone_train.py; the
-inputs come from seeded CPU generators.  Per case: y and every gradient (for a bottleneck the running statistics afterwards too).
+conv2d_down, conv2d_plain, bottleneck, upsample2x, upsample_add, batch_norm_act, stem_conv, max_pool_3x3_s2 and Yolact.forward_stem /
+forward_backbone / forward_fpn / forward_heads / forward_train), so the script runs unchanged on an older tree.  The shapes are the
+small ones of tests/test_gpu_heads_train.py, tests/test_gpu_fpn_train.py and tests/test_gpu_backbone_train.py; the inputs come from
+seeded CPU generators.  Per case: y and every gradient (for a bottleneck the running statistics afterwards too).  The net-level cases
+run on the model of tests/test_gpu_stem_train.py::test_multibox_loss_from_the_images (seeded ResNet-50 stages, 32 features, 96 x 96
+images) with random inputs: every output and every parameter gradient, with frozen and with batch statistics.
 
     python tools/train_digest.py > digests.txt
 """
@@ -18,6 +21,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, 'tests'))
 import backbone_train_ref as R  # noqa: E402
+import heads_train_ref as H  # noqa: E402
 import yolact_amd  # noqa: E402, F401
 from yolact_amd import modules as M  # noqa: E402
 from yolact_amd.layers import train_ops as TO  # noqa: E402
@@ -151,6 +155,86 @@ def others():
     emit('batch_norm_act', 'running_var', bn.running_var)
 
 
+def stem_cases():
+    g = torch.Generator().manual_seed(12)
+    x4 = torch.nn.functional.pad(torch.randn(2, 13, 11, 3, generator=g), (0, 1)).to(DEV)
+    w, up = torch.randn(32, 3, 7, 7, generator=g) * (2.0 / 147) ** 0.5, torch.randn(2, 7, 6, 32, generator=g)
+    leaves = dict(w=leaf(w))
+    y = TO.stem_conv(x4, leaves['w'])
+    emit('stem_conv', 'y', y)
+    backward_and_emit('stem_conv', [y], [up], leaves)
+    x, up = torch.randn(2, 7, 6, 32, generator=g), torch.randn(2, 4, 3, 32, generator=g)
+    leaves = dict(x=leaf(x))
+    y = TO.max_pool_3x3_s2(leaves['x'])
+    emit('max_pool_3x3_s2', 'y', y)
+    backward_and_emit('max_pool_3x3_s2', [y], [up], leaves)
+
+
+def small_net():
+    """The model of test_multibox_loss_from_the_images: yolact_resnet50_config at 32 features, seeded stages, all on the GPU."""
+    yolact_amd.set_cfg('yolact_resnet50_config')
+    cfg = yolact_amd.config.cfg
+    o = H.golden_cfg_overrides()
+    cfg.fpn = cfg.fpn.copy({'num_features': o.pop('num_features')})
+    cfg.update(o)
+    from yolact_amd.yolact import Yolact
+    torch.manual_seed(3)
+    net = Yolact()
+    gen = torch.Generator().manual_seed(3)
+    with torch.no_grad():
+        for si, layer in enumerate(net.backbone.layers):
+            for bi, blk in enumerate(layer):
+                prefix = 'layers.%d.%d.' % (si, bi)
+                vals = R.random_block_params(gen, blk.conv1.in_channels, blk.conv1.out_channels, blk.downsample is not None, prefix)
+                for n, t in blk.state_dict().items():
+                    if 'num_batches' not in n:
+                        t.copy_(vals[prefix + n])
+    for m in (net.backbone, net.fpn, net.proto_net, net.prediction_layers, net.semantic_seg_conv):
+        m.to(DEV)
+    return net, cfg
+
+
+def net_case(case, net, run, inputs):
+    """run(*leaves) -> dict or list of outputs; the loss is sum(output * seeded upstream gradient).  Emits every output, the gradient of
+    every input and of every parameter that received one, and the running statistics; leaves the model as it found it."""
+    state = {n: t.clone() for n, t in net.state_dict().items()}
+    net.zero_grad(set_to_none=True)
+    leaves = [leaf(t) for t in inputs]
+    out = run(*leaves)
+    out = out if isinstance(out, dict) else {'out%d' % i: o for i, o in enumerate(out)}
+    g = torch.Generator().manual_seed(13)
+    for n, o in out.items():
+        emit(case, n, o)
+    out = {n: o for n, o in out.items() if o.requires_grad}
+    backward_and_emit(case, list(out.values()), [torch.randn(*o.shape, generator=g) for o in out.values()],
+                      {'in%d' % i: t for i, t in enumerate(leaves)})
+    for n, p in net.named_parameters():
+        if p.grad is not None:
+            emit(case, 'd_' + n, p.grad)
+    for n, t in net.state_dict().items():
+        if 'running' in n and not torch.equal(t, state[n]):
+            emit(case, n, t)
+    net.load_state_dict(state)
+    net.zero_grad(set_to_none=True)
+
+
+def net_cases():
+    net, cfg = small_net()
+    g = torch.Generator().manual_seed(14)
+    images = torch.randn(2, 3, 96, 96, generator=g)
+    pooled = torch.randn(2, 64, 24, 24, generator=g)
+    chans = [net.backbone.channels[i] for i in cfg.backbone.selected_layers]
+    convouts = [torch.randn(2, c, s, s, generator=g) for c, s in zip(chans, (12, 6, 3))]
+    maps = [torch.randn(2, cfg.fpn.num_features, s, s, generator=g) for s in (12, 6, 3, 2, 1)]
+    for bs in (False, True):
+        mode = 'stats' if bs else 'frozen'
+        net_case('forward_stem ' + mode, net, lambda: [net.forward_stem(images.to(DEV), bs)], [])
+        net_case('forward_backbone ' + mode, net, lambda x: net.forward_backbone(x, bs), [pooled])
+        net_case('forward_train ' + mode, net, lambda: net.forward_train(images.to(DEV), bs), [])
+    net_case('forward_fpn', net, lambda *c: net.forward_fpn(list(c)), convouts)
+    net_case('forward_heads', net, lambda *m: net.forward_heads(list(m)), maps)
+
+
 def main():
     print('# %s, torch %s' % (torch.cuda.get_device_name(0), torch.__version__))
     name = lambda s: '%dx%d_b%d_%dx%d_%dto%d' % (s[0], s[0], s[1], s[2], s[3], s[4], s[5])
@@ -171,6 +255,8 @@ def main():
         for batch_stats in (False, True):
             block_case('bottleneck %s %s' % (variant, 'stats' if batch_stats else 'frozen'), spec, batch_stats)
     others()
+    stem_cases()
+    net_cases()
 
 
 if __name__ == '__main__':

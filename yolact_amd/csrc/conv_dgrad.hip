@@ -1,6 +1,6 @@
 // The data gradient of a STRIDE-2 convolution (3x3 / pad 1 and 1x1 / pad 0), NHWC fp32, for the backbone's stage entries (each stage's
 // first conv2 and the projection shortcuts, backbone.py:28-29, 94-99), whose maps reach 138 x 138: the zero-insert route of
-// train_ops.ConvDown.backward spends four times the useful FLOPs there.
+// train_ops._data_grad (zero_insert, which conv2d_down keeps for the FPN's small maps) spends four times the useful FLOPs there.
 //
 //   ymi_conv_dgrad_s2_nhwc_f32   dx[n,y,x,ci] = sum over the taps (ky, kx) that EXIST for this pixel, sum_co g[n,oy,ox,co] w[co,ci,ky,kx]
 //                                with oy = (y + pad - ky) / 2 where that division is exact and 0 <= oy < Ho (the same in x).

@@ -32,8 +32,10 @@ raises NotImplementedError naming it.  Forward: one ymi_conv2d_nhwc_f32 launch o
   dx   _data_grad.  Stride 1: ymi_conv2d_nhwc_f32 on g with the filters flipped in both taps and transposed in (Cin, Cout).
        Stride 2 has two routes.  conv2d_plain: ymi_conv_dgrad_s2_nhwc_f32 (csrc/conv_dgrad.hip: only the taps that exist).
        conv2d_down (zero_insert = True): g spread over a zeroed [B,H,W,ldg] buffer (gz[:, ::2, ::2] = g), then the stride-1 launch,
-       four times the useful FLOPs (fine for the FPN's 18 x 18 and 9 x 9 maps).  The two routes agree bit for bit only on exact
-       grids, so the FPN keeps its own until it is moved over on purpose; zero_insert and its branch then go.
+       four times the useful FLOPs.  The two routes agree bit for bit only on exact grids.  The FPN keeps its own because it is the
+       faster one there: at 3x3 256 -> 256, B = 8, 18 x 18 and 9 x 9 the kernel's grid is 48 and 16 blocks for 256 CUs, and
+       forward_fpn forward + backward measured 4712 us with the kernel against 4637 us with this route, the parent's own spread
+       being 62 us (profiles/train_net_ab.txt).
 upsample_add: d_lat = dy, d_top = ymi_bilinear_size_bwd_nhwc_f32 (a gather in a fixed order).  batch_norm_act: ymi_bn_fwd_nhwc_f32 /
 ymi_bn_bwd_nhwc_f32 (csrc/bn_train.hip).
 stem_conv: one ymi_conv2d_nhwc_f32 launch through the engine's Cin-4 loader with the filter's fourth input channel zero; the backward
@@ -64,16 +66,19 @@ def _out_size(H, W, k, pad, stride):
     return (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
 
 
+def _pair(v):
+    return (int(v), int(v)) if isinstance(v, int) else tuple(int(e) for e in v)
+
+
 def _check_geometry(who, weight, stride, padding=None, dilation=1, groups=1, strides=(1, 2)):
     """NotImplementedError naming what of a convolution's geometry the kernels do not take -> (k, pad, stride).  `strides`: what the
     caller takes.  padding None: k // 2 is meant, and a weight that is not 4-D is refused by name (with a padding the weight is an
     nn.Conv2d's, and its shape is unpacked before anything is looked at)."""
-    pair = lambda v: (int(v), int(v)) if isinstance(v, int) else tuple(int(e) for e in v)
     if isinstance(padding, str):
         raise NotImplementedError('yolact_amd %s: padding = %r is not supported (an integer padding is)' % (who, padding))
-    stride, dilation = pair(stride), pair(dilation)
+    stride, dilation = _pair(stride), _pair(dilation)
     if padding is not None:
-        padding, (Cout, Cin, kh, kw) = pair(padding), weight.shape
+        padding, (Cout, Cin, kh, kw) = _pair(padding), weight.shape
     if stride not in [(s, s) for s in strides]:
         raise NotImplementedError('yolact_amd %s: stride = %r is not supported (%s %s)'
                                   % (who, stride, ' and '.join('stride %d' % s for s in strides), 'is' if len(strides) == 1 else 'are'))
@@ -594,17 +599,16 @@ STEM_K, STEM_PAD, STEM_STRIDE = 7, 3, 2
 def check_stem(weight, stride=2, padding=3, dilation=1, groups=1, bias=None, who='stem_conv'):
     """NotImplementedError naming what of the stem convolution the kernels do not take: anything but a bias-free 7 x 7 / stride 2 /
     padding 3 / dilation 1 / groups 1 convolution of 3 input channels."""
-    pair = lambda v: (int(v), int(v)) if isinstance(v, int) else tuple(int(e) for e in v)
     if weight.dim() != 4:
         raise NotImplementedError('yolact_amd %s: a weight of shape %s is not supported ([Cout,3,7,7] is)' % (who, tuple(weight.shape)))
     Cout, Cin, kh, kw = weight.shape
     if (kh, kw) != (STEM_K, STEM_K):
         raise NotImplementedError('yolact_amd %s: a %d x %d kernel is not supported (7 x 7 is)' % (who, kh, kw))
-    if isinstance(stride, str) or pair(stride) != (STEM_STRIDE, STEM_STRIDE):
+    if isinstance(stride, str) or _pair(stride) != (STEM_STRIDE, STEM_STRIDE):
         raise NotImplementedError('yolact_amd %s: stride = %r is not supported (stride 2 is)' % (who, stride))
-    if isinstance(padding, str) or pair(padding) != (STEM_PAD, STEM_PAD):
+    if isinstance(padding, str) or _pair(padding) != (STEM_PAD, STEM_PAD):
         raise NotImplementedError('yolact_amd %s: padding = %r is not supported (padding 3 is)' % (who, padding))
-    if pair(dilation) != (1, 1):
+    if _pair(dilation) != (1, 1):
         raise NotImplementedError('yolact_amd %s: dilation = %r is not supported (dilation 1 is)' % (who, dilation))
     if groups != 1:
         raise NotImplementedError('yolact_amd %s: groups = %r is not supported (groups 1 is)' % (who, groups))

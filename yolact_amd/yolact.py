@@ -20,9 +20,15 @@ import torch.nn as nn
 
 from . import _lib as L
 from . import modules as M
-from .config import active_cfg, backbone_kind, is_lincomb
+from . import train_net as TN
+from .config import act_name, active_cfg, backbone_kind, is_lincomb
 from .engine import Plan
+from .layers import train_ops as TO
 from .layers.detection import Detect
+
+
+def _nhwc(t):      # of a permuted view of NHWC fp32 storage, what the train-mode methods return, it is that storage: no copy
+    return t.to(torch.float32).permute(0, 2, 3, 1).contiguous()
 
 
 class Yolact(nn.Module):
@@ -411,122 +417,33 @@ class Yolact(nn.Module):
         return parallel.assemble_sharded(rec, mine, lo, hi, self.mask_dim, self, bits=bits,
                                          mask_size=(hh, ww) if masks == 'bits' else None)
 
-    # ---- train-mode heads -------------------------------------------------------------------------------
-    @staticmethod
-    def _apply_net(seq, x, last_act=None, params=None):
-        """A make_net Sequential (utils/functions.py:163-213) on NHWC x through layers/train_ops: Conv2d (+ the ReLU behind it),
-        InterpolateModule (+ the ReLU behind it).  last_act: the activation applied after a final layer that has no ReLU of its own.
-        params: [w, b, w, b, ..] to use in place of the convolutions' own parameters (aliases of a shared head)."""
-        from .layers import train_ops as TO
-        mods = list(seq)
-        params = None if params is None else list(params)
-        for i, m in enumerate(mods):
-            if isinstance(m, nn.ReLU):
-                continue
-            relu = i + 1 < len(mods) and isinstance(mods[i + 1], nn.ReLU)
-            act = 'relu' if relu else (last_act if i == len(mods) - 1 else None)
-            if isinstance(m, nn.Conv2d):
-                w, b = (m.weight, m.bias) if params is None else (params.pop(0), params.pop(0))
-                x = TO.conv2d_act(x, w, b, m.padding, act, stride=m.stride, dilation=m.dilation, groups=m.groups)
-            elif isinstance(m, M.InterpolateModule):
-                if m.scale_factor != 2 or act not in (None, 'relu'):
-                    raise NotImplementedError('yolact_amd forward_heads: an interpolation by %r followed by %r is not supported '
-                                              '(x2 bilinear with or without ReLU is)' % (m.scale_factor, act))
-                x = TO.upsample2x(x, relu=act == 'relu')
-            else:
-                raise NotImplementedError('yolact_amd forward_heads: layer %r is not implemented' % (m,))
-        return x
-
+    # ---- train mode: validation and layout around train_net.py -----------------------------------------------------------------------
+    # Each _check_* raises what its method raises, in that order; without tensors (forward_train) only the model and cfg are looked at.
     def _train_priors(self, sizes, cfg, device):
-        """The priors of forward_heads: built on the host once per (level sizes, every cfg value they are made from, device) and
-        kept on the device, as the reference keeps them per map size (yolact.py:214-263); cfg is still read at every call."""
-        from .config import make_priors_host
-        bbc = cfg.backbone
-        nlev = len(sizes)
-        freeze = lambda v: tuple(freeze(e) for e in v) if isinstance(v, (list, tuple)) else v
-        key = (tuple(sizes), freeze(list(bbc.pred_scales[:nlev])), freeze(list(bbc.pred_aspect_ratios[:nlev])), cfg.max_size,
-               bool(bbc.use_pixel_scales), bool(bbc.preapply_sqrt), bool(bbc.use_square_anchors), str(device))
-        cache = self.__dict__.setdefault('_train_prior_cache', {})
-        pri = cache.get(key)
-        if pri is None:
-            data = []
-            for lvl, (h, w) in enumerate(sizes):
-                data += make_priors_host(h, w, bbc.pred_scales[lvl], bbc.pred_aspect_ratios[lvl], cfg.max_size, bbc)
-            if len(cache) >= 8:
-                cache.clear()
-            pri = cache[key] = torch.tensor(data, dtype=torch.float32).view(-1, 4).to(device)
-        return pri
+        return TN.priors(self, sizes, cfg, device)
 
-    def forward_heads(self, outs):
-        """The reference's TRAIN-mode pred_outs (yolact.py:579-647) from the FPN maps `outs` ([B,nf,h_i,w_i] NCHW fp32 on the GPU,
-        one per prediction level, as yolact.py:577 yields them): {'loc' [B,P,4], 'conf' [B,P,C] raw logits, 'mask' [B,P,mask_dim]
-        after the coefficient activation, 'priors' [P,4], 'proto' [B,2h_0,2w_0,mask_dim] after the prototype activation, and
-        'segm' [B,C-1,h_0,w_0] under cfg.use_semantic_segmentation_loss}: what MultiBoxLoss takes.  Once differentiable in `outs`
-        and in the parameters of proto_net, prediction_layers[0] and semantic_seg_conv (layers/train_ops.py on the HIP kernels;
-        the shared head's gradients are summed over the levels in level order).  Needs no plan and reads cfg at call time; the
-        model stays in eval mode (train() raises) and forward() is untouched."""
-        from .layers import train_ops as TO
-        from .config import act_name
+    def _check_heads(self, outs=None):
         cfg = self.cfg
-        outs = list(outs)
-        if len(outs) != len(self.selected_layers):
+        if outs is not None and len(outs) != len(self.selected_layers):
             raise ValueError('forward_heads: %d FPN maps for %d prediction levels' % (len(outs), len(self.selected_layers)))
         if not bool(getattr(cfg, 'eval_mask_branch', True)):
             raise NotImplementedError('yolact_amd forward_heads: cfg.eval_mask_branch = False is not supported')
-        for o in outs:
+        for o in outs or ():
             L.require_cuda(o, 'forward_heads FPN map')
             if o.dim() != 4 or o.shape[0] != outs[0].shape[0]:
                 raise ValueError('forward_heads: expected [B,C,h,w] maps of one batch, got %s' % (tuple(o.shape),))
-        feats = [o.to(torch.float32).permute(0, 2, 3, 1).contiguous() for o in outs]
-        B = feats[0].shape[0]
-        pm = self.prediction_layers[0]
-        coef_act = act_name(cfg.mask_proto_coeff_activation)
-        proto_act = act_name(cfg.mask_proto_prototype_activation)
-        for what, a in (('mask_proto_coeff_activation', coef_act), ('mask_proto_prototype_activation', proto_act)):
+        for what in ('mask_proto_coeff_activation', 'mask_proto_prototype_activation'):
+            a = act_name(getattr(cfg, what))
             if a not in TO.ACTS:
                 raise NotImplementedError('yolact_amd forward_heads: cfg.%s = %s is not supported (none, relu and tanh are)' % (what, a))
-        with torch.cuda.device(feats[0].device):
-            proto = self._apply_net(self.proto_net, feats[self.proto_src], last_act=None if proto_act == 'none' else proto_act)
-            loc, conf, mask = [], [], []
-            up = [m for m in pm.upfeature if isinstance(m, nn.Conv2d)] if hasattr(pm, 'upfeature') else []
-            hl = pm.bbox_layer
-            # one set of weights on every level: each level works on aliases whose gradients are added in level order
-            shared = TO.share_params(len(feats), [t for m in up + [pm.bbox_layer, pm.conf_layer, pm.mask_layer]
-                                                  for t in (m.weight, m.bias)])
-            for lvl, x in enumerate(feats):
-                hp = shared[lvl]
-                if up:
-                    x = self._apply_net(pm.upfeature, x, params=hp[:2 * len(up)])
-                wb, bb_, wc, bc, wm, bm = hp[2 * len(up):]
-                b, c, m = TO.conv2d_multi(x, [(wb, bb_, None), (wc, bc, None), (wm, bm, coef_act)],
-                                          hl.padding, stride=hl.stride, dilation=hl.dilation, groups=hl.groups)
-                loc.append(b.reshape(B, -1, 4))
-                conf.append(c.reshape(B, -1, cfg.num_classes))
-                mask.append(m.reshape(B, -1, self.mask_dim))
-            pred = {'loc': torch.cat(loc, 1), 'conf': torch.cat(conf, 1), 'mask': torch.cat(mask, 1),
-                    'priors': self._train_priors([tuple(f.shape[1:3]) for f in feats], cfg, feats[0].device), 'proto': proto}
-            if cfg.use_semantic_segmentation_loss:
-                sc = self.semantic_seg_conv
-                segm = TO.conv2d_act(feats[0], sc.weight, sc.bias, sc.padding, None, stride=sc.stride, dilation=sc.dilation,
-                                     groups=sc.groups)
-                pred['segm'] = segm.permute(0, 3, 1, 2)
-        return pred
 
-    def forward_fpn(self, convouts):
-        """The reference's FPN.forward (yolact.py:311-360) on the backbone's selected maps `convouts` ([B,C_j,h_j,w_j] NCHW fp32 on the
-        GPU, finest first, one per entry of fpn.lat_layers) -> the len(selected_layers) maps [B,nf,h,w] that forward_heads takes, for
-        the variant __init__ insists on (conv downsample, relu_pred_layers, no relu_downsample_layers, bilinear).  Once differentiable
-        in every convout and in every parameter of self.fpn (layers/train_ops.py on the HIP kernels).  Each result is a permuted view
-        of NHWC storage, so forward_heads' .permute(0, 2, 3, 1).contiguous() copies nothing.  Needs no plan and reads cfg at call
-        time; the model stays in eval mode and forward() is untouched."""
-        from .layers import train_ops as TO
-        cfg = self.cfg
-        fpn = self.fpn
-        convouts = list(convouts)
-        if not cfg.fpn.pad:
+    def _check_fpn(self, convouts=None):
+        if not self.cfg.fpn.pad:
             raise NotImplementedError('yolact_amd forward_fpn: cfg.fpn.pad = False is not supported (padded pred layers are)')
-        if len(convouts) != len(fpn.lat_layers):
-            raise ValueError('forward_fpn: %d backbone maps for %d lateral layers' % (len(convouts), len(fpn.lat_layers)))
+        if convouts is None:
+            return
+        if len(convouts) != len(self.fpn.lat_layers):
+            raise ValueError('forward_fpn: %d backbone maps for %d lateral layers' % (len(convouts), len(self.fpn.lat_layers)))
         for j, c in enumerate(convouts):
             if c.dim() != 4 or c.shape[0] != convouts[0].shape[0]:
                 raise ValueError('forward_fpn: expected [B,C,h,w] maps of one batch, got %s' % (tuple(c.shape),))
@@ -535,92 +452,88 @@ class Yolact(nn.Module):
                                  'first' % (j, c.shape[2], c.shape[3], convouts[j - 1].shape[2], convouts[j - 1].shape[3]))
         for c in convouts:
             L.require_cuda(c, 'forward_fpn backbone map')
-        feats = [c.to(torch.float32).permute(0, 2, 3, 1).contiguous() for c in convouts]
-        n = len(feats)
-        conv = lambda x, m, act: TO.conv2d_act(x, m.weight, m.bias, m.padding, act, stride=m.stride, dilation=m.dilation, groups=m.groups)
-        with torch.cuda.device(feats[0].device):
-            # lat_layers and pred_layers are stored deepest level first (yolact.py:286-296, 324-341)
-            out, x = [None] * n, None
-            for i, lat in enumerate(fpn.lat_layers):
-                j = n - 1 - i
-                lateral = conv(feats[j], lat, None)
-                x = lateral if x is None else TO.upsample_add(x, lateral)
-                out[j] = x
-            for i, pred in enumerate(fpn.pred_layers):
-                j = n - 1 - i
-                out[j] = conv(out[j], pred, 'relu')
-            for down in fpn.downsample_layers:
-                if tuple(down.stride) != (2, 2) or tuple(down.padding) != (down.kernel_size[0] // 2,) * 2 or \
-                        tuple(down.dilation) != (1, 1) or down.groups != 1:
-                    raise NotImplementedError('yolact_amd forward_fpn: downsample layer %r is not supported (stride 2, padding k // 2 is)'
-                                              % (down,))
-                out.append(TO.conv2d_down(out[-1], down.weight, down.bias))
-        return [o.permute(0, 3, 1, 2) for o in out]
 
-    def forward_backbone(self, x, batch_stats=None):
-        """The reference's ResNetBackbone.forward behind the stem (backbone.py:135-142): x [B,64,h,w] NCHW fp32 on the GPU, the
-        max-pool's output -> the four stage outputs [B,256 .. 2048,h_i,w_i].  Each result is a permuted view of NHWC storage, so
-        forward_fpn([outs[i] for i in cfg.backbone.selected_layers]) copies nothing.  Once differentiable in x, in every convolution of
-        backbone.layers and in the BatchNorm affine parameters that require grad (layers/train_ops.py on the HIP kernels).
-        batch_stats None follows each BatchNorm's own .training (False while the model is in eval mode: the reference's freeze_bn());
-        True normalises with the batch statistics and updates the running ones.  Needs no plan; the model stays in eval mode and
-        forward() is untouched.  A DarkNet backbone or a DCN block raises NotImplementedError naming it."""
-        from .layers import train_ops as TO
-        from .modules import ResNetBackbone
-        if not isinstance(self.backbone, ResNetBackbone):
+    def _check_backbone(self, x=None):
+        if not isinstance(self.backbone, M.ResNetBackbone):
             raise NotImplementedError('yolact_amd forward_backbone: a %s is not supported (a ResNetBackbone is)'
                                       % type(self.backbone).__name__)
         for si, layer in enumerate(self.backbone.layers):
             for bi, block in enumerate(layer):
                 TO.check_bottleneck(block, 'backbone.layers.%d.%d' % (si, bi))
-        L.require_cuda(x, 'forward_backbone stem map')
-        cin = self.backbone.layers[0][0].conv1.in_channels
-        if x.dim() != 4 or x.shape[1] != cin:
-            raise ValueError('forward_backbone: expected the stem\'s output [B,%d,h,w], got %s' % (cin, tuple(x.shape)))
-        x = x.to(torch.float32).permute(0, 2, 3, 1).contiguous()
-        outs = []
-        with torch.cuda.device(x.device):
-            for layer in self.backbone.layers:
-                for block in layer:
-                    x = TO.bottleneck(x, block, batch_stats)
-                outs.append(x.permute(0, 3, 1, 2))
-        return outs
+        if x is not None:
+            L.require_cuda(x, 'forward_backbone stem map')
+            cin = self.backbone.layers[0][0].conv1.in_channels
+            if x.dim() != 4 or x.shape[1] != cin:
+                raise ValueError('forward_backbone: expected the stem\'s output [B,%d,h,w], got %s' % (cin, tuple(x.shape)))
+
+    def _check_stem(self, x=None):
+        bb = self.backbone
+        if not isinstance(bb, M.ResNetBackbone):
+            raise NotImplementedError('yolact_amd forward_stem: a %s is not supported (a ResNetBackbone is)' % type(bb).__name__)
+        c1 = bb.conv1
+        TO.check_stem(c1.weight, c1.stride, c1.padding, c1.dilation, c1.groups, c1.bias, 'forward_stem backbone.conv1')
+        if x is not None:
+            L.require_cuda(x, 'forward_stem image batch')
+            if x.dim() != 4 or x.shape[1] != 3:
+                raise ValueError('forward_stem: expected [B,3,H,W], got %s' % (tuple(x.shape),))
+
+    def forward_heads(self, outs):
+        """The reference's TRAIN-mode pred_outs (yolact.py:579-647) from the FPN maps `outs` ([B,nf,h_i,w_i] NCHW fp32 on the GPU,
+        one per prediction level, as yolact.py:577 yields them): {'loc' [B,P,4], 'conf' [B,P,C] raw logits, 'mask' [B,P,mask_dim]
+        after the coefficient activation, 'priors' [P,4], 'proto' [B,2h_0,2w_0,mask_dim] after the prototype activation, and
+        'segm' [B,C-1,h_0,w_0] under cfg.use_semantic_segmentation_loss}: what MultiBoxLoss takes.  Once differentiable in `outs`
+        and in the parameters of proto_net, prediction_layers[0] and semantic_seg_conv (train_net.heads on the HIP kernels;
+        the shared head's gradients are summed over the levels in level order).  Needs no plan and reads cfg at call time; the
+        model stays in eval mode (train() raises) and forward() is untouched."""
+        outs = list(outs)
+        self._check_heads(outs)
+        return TN.heads(self, [_nhwc(o) for o in outs])
+
+    def forward_fpn(self, convouts):
+        """The reference's FPN.forward (yolact.py:311-360) on the backbone's selected maps `convouts` ([B,C_j,h_j,w_j] NCHW fp32 on the
+        GPU, finest first, one per entry of fpn.lat_layers) -> the len(selected_layers) maps [B,nf,h,w] that forward_heads takes, for
+        the variant __init__ insists on (conv downsample, relu_pred_layers, no relu_downsample_layers, bilinear).  Once differentiable
+        in every convout and in every parameter of self.fpn (train_net.fpn on the HIP kernels).  Each result is a permuted view of
+        NHWC storage, so forward_heads' layout change copies nothing.  Needs no plan and reads cfg at call time; the model stays in
+        eval mode and forward() is untouched."""
+        convouts = list(convouts)
+        self._check_fpn(convouts)
+        return [o.permute(0, 3, 1, 2) for o in TN.fpn(self, [_nhwc(c) for c in convouts])]
+
+    def forward_backbone(self, x, batch_stats=None):
+        """The reference's ResNetBackbone.forward behind the stem (backbone.py:135-142): x [B,64,h,w] NCHW fp32 on the GPU, the
+        max-pool's output -> the four stage outputs [B,256 .. 2048,h_i,w_i].  Each result is a permuted view of NHWC storage, so
+        forward_fpn([outs[i] for i in cfg.backbone.selected_layers]) copies nothing.  Once differentiable in x, in every convolution of
+        backbone.layers and in the BatchNorm affine parameters that require grad (train_net.backbone on the HIP kernels).
+        batch_stats None follows each BatchNorm's own .training (False while the model is in eval mode: the reference's freeze_bn());
+        True normalises with the batch statistics and updates the running ones.  Needs no plan; the model stays in eval mode and
+        forward() is untouched.  A DarkNet backbone or a DCN block raises NotImplementedError naming it."""
+        self._check_backbone(x)
+        return [o.permute(0, 3, 1, 2) for o in TN.backbone(self, _nhwc(x), batch_stats)]
 
     def forward_stem(self, x, batch_stats=None):
         """The reference's ResNet stem (backbone.py:129-132: conv1, bn1, ReLU, max-pool) on x [B,3,H,W] NCHW fp32 on the GPU, the
         normalised image forward() takes -> [B,64,Hp,Wp], what forward_backbone starts from, as a permuted view of NHWC storage (so
-        forward_backbone copies nothing).  The image is padded to NHWC with a fourth channel of zeros once, with torch operations; the
-        convolution's backward reads that same tensor.  Once differentiable in conv1.weight and in bn1's affine parameters where they
-        require grad; no gradient reaches the image.  batch_stats as in forward_backbone.  Needs no plan and reads cfg at call time; the
-        model stays in eval mode and forward() is untouched.  A DarkNet backbone raises NotImplementedError naming it."""
-        from .layers import train_ops as TO
-        from .modules import ResNetBackbone
-        bb = self.backbone
-        if not isinstance(bb, ResNetBackbone):
-            raise NotImplementedError('yolact_amd forward_stem: a %s is not supported (a ResNetBackbone is)' % type(bb).__name__)
-        c1 = bb.conv1
-        TO.check_stem(c1.weight, c1.stride, c1.padding, c1.dilation, c1.groups, c1.bias, 'forward_stem backbone.conv1')
-        L.require_cuda(x, 'forward_stem image batch')
-        if x.dim() != 4 or x.shape[1] != 3:
-            raise ValueError('forward_stem: expected [B,3,H,W], got %s' % (tuple(x.shape),))
-        with torch.cuda.device(x.device):
-            x4 = nn.functional.pad(x.detach().to(torch.float32).permute(0, 2, 3, 1), (0, 1)).contiguous()
-            y = TO.stem_conv(x4, c1.weight)
-            y = TO.batch_norm_act(y, bb.bn1, batch_stats, relu=True)
-            y = TO.max_pool_3x3_s2(y)
-        return y.permute(0, 3, 1, 2)
+        forward_backbone copies nothing).  Once differentiable in conv1.weight and in bn1's affine parameters where they require grad;
+        no gradient reaches the image (train_net.stem on the HIP kernels).  batch_stats as in forward_backbone.  Needs no plan and
+        reads cfg at call time; the model stays in eval mode and forward() is untouched.  A DarkNet backbone raises
+        NotImplementedError naming it."""
+        self._check_stem(x)
+        return TN.stem(self, x, batch_stats).permute(0, 3, 1, 2)
 
     def forward_train(self, x, batch_stats=None):
         """The reference's TRAIN-mode Yolact.forward (yolact.py:564-647) from the image batch x [B,3,H,W] to pred_outs, what MultiBoxLoss
-        takes as it stands: forward_heads(forward_fpn(selected(forward_backbone(forward_stem(x))))), differentiable in every parameter
-        those four are.  batch_stats as in forward_backbone.  The model stays in eval mode (train() raises)."""
+        takes as it stands: forward_heads(forward_fpn(selected(forward_backbone(forward_stem(x))))) bit for bit, gradients included,
+        without their layout changes (train_net.forward); differentiable in every parameter those four are.  batch_stats as in
+        forward_backbone.  The model stays in eval mode (train() raises)."""
         cfg = self.cfg
         L.require_cuda(x, 'input batch')
         if x.dim() != 4 or x.shape[1] != 3:
             raise ValueError('expected [B,3,H,W], got %s' % (tuple(x.shape),))
         cfg._tmp_img_h, cfg._tmp_img_w = int(x.shape[2]), int(x.shape[3])
-        outs = self.forward_backbone(self.forward_stem(x, batch_stats), batch_stats)
-        return self.forward_heads(self.forward_fpn([outs[i] for i in cfg.backbone.selected_layers]))
+        for check in (self._check_stem, self._check_backbone, self._check_fpn, self._check_heads):
+            check()
+        return TN.forward(self, x, batch_stats)
 
     def forward_raw(self, x):
         """Head outputs before Detect (for parity tests): loc, conf (logits), mask, priors, proto — clones."""
