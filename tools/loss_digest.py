@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """One SHA-256 per output tensor of the MultiBoxLoss kernels on fixed inputs: two trees whose lines are equal add in the same order
-(csrc/loss_common.h).  Only public functions are called (match_targets, box_loss, ohem_terms, segm_terms, mask_loss_terms and
-gather_instances), so the script runs unchanged on an older tree.  Per term the smallest shapes of the GPU tests and one shape at
-which B * tiles > 256, where the strided loop of the final sum takes more than one trip (mask loss: N > 256).
+(csrc/loss_common.h, csrc/lincomb_common.h).  Only public functions are called (match_targets, box_loss, ohem_terms, segm_terms,
+mask_loss_terms, gather_instances and maskiou_loss.MaskIouInput), so the script runs unchanged on an older tree.  Per term the
+smallest shapes of the GPU tests and one shape at which B * tiles > 256, where the strided loop of the final sum takes more than one
+trip (mask loss: N > 256); for the two lincomb terms also the smallest shapes at which their shared skeleton takes another path.
 
     python tools/loss_digest.py > digests.txt
 """
@@ -21,6 +22,7 @@ import match_ref as R  # noqa: E402
 import yolact_amd  # noqa: E402
 from yolact_amd.layers import class_loss as CL  # noqa: E402
 from yolact_amd.layers import mask_loss as ML  # noqa: E402
+from yolact_amd.layers import maskiou_loss as MIL  # noqa: E402
 from yolact_amd.layers import match as M  # noqa: E402
 from yolact_amd.layers import segm_loss as SL  # noqa: E402
 
@@ -75,9 +77,43 @@ def segm_case(case, g, B, K, mh, mw, counts):
     emit(case, 'd_segm', d)
 
 
-def mask_terms(case, *args):
-    for name, t in zip(('M', 'loss_inst', 'd_proto', 'd_coef'), ML.mask_loss_terms(*[a.to(DEV) for a in args], alpha=6.125)):
+def mask_terms(case, *args, **switches):
+    for name, t in zip(('M', 'loss_inst', 'd_proto', 'd_coef'), ML.mask_loss_terms(*[a.to(DEV) for a in args], alpha=6.125, **switches)):
         emit(case, name, t)
+
+
+def lincomb_inputs(g, B, mh, mw, counts, n_gt=3):
+    """proto, coef, box, gt, gt_idx, img_off for counts[b] instances in image b.  Every fourth box is a corner of the map a few
+    pixels wide, which only the first (or last) wave of a tile reaches: the other waves skip that instance; every fourth has its
+    corners swapped; the rest are of all sizes."""
+    N = sum(counts)
+    proto = torch.relu(torch.randn(B, mh, mw, 32, generator=g)) * 0.5
+    coef = torch.tanh(torch.randn(N, 32, generator=g)) * 0.5
+    c = 0.05 + 0.9 * torch.rand(N, 2, generator=g)
+    half = 0.02 + 0.4 * torch.rand(N, 2, generator=g) ** 2
+    box = torch.cat([c - half, c + half], 1).clamp(0.0, 1.0)
+    j = torch.arange(N)
+    box[j % 4 == 0] = torch.tensor([0.0, 0.0, 0.12, 0.1])
+    box[j % 8 == 4] = torch.tensor([0.9, 0.92, 1.0, 1.0])
+    swap = j % 4 == 1
+    box[swap] = box[swap][:, [2, 3, 0, 1]]
+    gt = (torch.rand(B * n_gt, mh, mw, generator=g) > 0.7).to(torch.uint8)
+    image = torch.arange(B).repeat_interleave(torch.tensor(counts))
+    gt_idx = (torch.randint(0, n_gt, (N,), generator=g) + image * n_gt).to(torch.int32)
+    img_off = torch.tensor([sum(counts[:b]) for b in range(B + 1)], dtype=torch.int32)
+    return proto, coef, box, gt, gt_idx, img_off
+
+
+def maskiou_input(case, g, inputs, want_proto=True, want_coef=True):
+    proto, coef, box, gt, gt_idx, img_off = inputs
+    proto, coef = proto.to(DEV).requires_grad_(want_proto), coef.to(DEV).requires_grad_(want_coef)
+    x0, iou_t = MIL.MaskIouInput.apply(proto, coef, box.to(DEV), gt.to(DEV), gt_idx.to(DEV), img_off)
+    x0.backward(torch.randn(x0.shape, generator=g).to(DEV))
+    emit(case, 'x0', x0)
+    emit(case, 'iou_t', iou_t)
+    for name, t in (('d_proto', proto), ('d_coef', coef)):
+        if t.grad is not None:
+            emit(case, name, t.grad)
 
 
 def main():
@@ -127,6 +163,21 @@ def main():
     gt_idx = (torch.randint(0, n_gt, (N,), generator=g) + torch.arange(B).repeat_interleave(n) * n_gt).to(torch.int32)
     img_off = torch.tensor([b * n for b in range(B + 1)], dtype=torch.int32)
     mask_terms('mask 8x138x138', proto, coef, box, gt, gt_idx, img_off, torch.ones(N))
+
+    # the lincomb skeleton's paths (csrc/lincomb_common.h): two LDS rounds with a last group of 2 of 8 (the mask loss stages 320
+    # instances at once, the mask-IoU input 128), one ragged tile, an image without instances, five tiles with the last ragged and
+    # d_proto or d_coef not wanted, the switches off
+    g = torch.Generator().manual_seed(104)
+    mask_terms('mask 2x12x10 n330', *lincomb_inputs(g, 2, 12, 10, [330, 5]), 0.5 + torch.rand(335, generator=g))
+    mask_terms('mask 3x13x11 plain', *lincomb_inputs(g, 3, 13, 11, [7, 0, 5]), 0.5 + torch.rand(12, generator=g), crop=False, roi_norm=False)
+    maskiou_input('miou 2x15x15', g, lincomb_inputs(g, 2, 15, 15, [130, 3]))
+    maskiou_input('miou 3x13x11', g, lincomb_inputs(g, 3, 13, 11, [7, 0, 5]))
+    inputs = lincomb_inputs(g, 2, 33, 35, [9, 17])
+    maskiou_input('miou 2x33x35 p', g, inputs, want_coef=False)
+    maskiou_input('miou 2x33x35 c', g, inputs, want_proto=False)
+    maskiou_input('miou 2x33x35 pc', g, inputs)
+    # the inputs of tools/maskiou_loss_probe.py --batch 8 (those of the mask loss above)
+    maskiou_input('miou 8x138x138', torch.Generator().manual_seed(1), (proto, coef, box, gt, gt_idx, img_off))
 
 
 if __name__ == '__main__':

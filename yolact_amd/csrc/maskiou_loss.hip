@@ -3,11 +3,9 @@
 //
 //   ymi_maskiou_input_f32       x0[j] = inside_j ? sigmoid(proto[b] . coef[j]) : 0 (the net's input) and iou_t[j] = inter / (a1 + a2 -
 //                               inter) from three integer counts.  One block per instance; a thread walks the pixels t, t + 256, ..
-//                               and evaluates the logit only inside the crop window (mask_loss.hip's window: padding 1).
-//   ymi_maskiou_input_bwd_f32   d_proto, d_coef from d_x0: mask_loss_k's structure with g = inside ? d_x0 p (1 - p) : 0 supplied from
-//                               outside: a thread keeps its pixel's 32 prototype values and 32 d_proto sums in registers, the
-//                               image's instances are staged in LDS, a wave transpose-reduces g * proto[k], the four waves are added
-//                               in wave order, the tile partials go to the workspace and are summed in tile order.
+//                               and evaluates the logit only inside the crop window (ymi_crop_window: padding 1).
+//   ymi_maskiou_input_bwd_f32   d_proto, d_coef from d_x0: lincomb_common.h's ymi_lincomb_bwd with g = inside ? d_x0 p (1 - p) : 0
+//                               supplied from outside; miou_dcoef_k sums the tile partials in tile order.
 //   ymi_conv2d_bwd_nhwc_f32     the backward of ymi_conv2d_direct_nhwc_f32 (+ ReLU) for any kernel size, stride and padding:
 //                               dx as a gather (an input pixel sums the output pixels that read it, taps in (ky, kx) order, channels
 //                               in order; pixels no window reaches get exact zeros); dw and db as dw[k,co] = sum_pos im2col[pos,k]
@@ -18,14 +16,12 @@
 //                               a second launch adds the chunk partials in chunk order.
 //   ymi_global_maxpool_bwd_nhwc_f32   routes d_pool[n,c] to the FIRST maximum of y[n,:,c] in row-major order (torch's CPU max_pool2d).
 //   ymi_maskiou_head_f32        p = pool[n,label[n]], loss = alpha sum_n smooth_l1(p - iou_t[n]), d_pool (zero off the label).
-#include "loss_common.h"
+#include "lincomb_common.h"
 #include "../../include/yolact_amd.h"
 
 namespace {
 
 // ---- the net's input and the IoU targets --------------------------------------------------------------------------------------
-constexpr int TP = 256;         // pixels per block of the backward (one per thread)
-constexpr int JC = 8;           // instances between two cross-wave combines
 constexpr int CAP_MAX = 128;    // instances staged in LDS at once (more take further rounds)
 
 struct MiParams {
@@ -36,19 +32,6 @@ struct MiParams {
   int B, mh, mw, npix, N, G, cap, ntiles, want_dc;
 };
 
-// sanitize_coordinates(_x1, _x2, img_size, padding=1, cast=False) in both directions: x1, x2, y1, y2
-__device__ __forceinline__ f32x4 crop_window(const float *b4, int mh, int mw) {
-  const float a = b4[0] * (float)mw, c = b4[2] * (float)mw;
-  float x1 = fminf(a, c) - 1.f; x1 = x1 < 0.f ? 0.f : x1;
-  float x2 = fmaxf(a, c) + 1.f; x2 = x2 > (float)mw ? (float)mw : x2;
-  const float d = b4[1] * (float)mh, e = b4[3] * (float)mh;
-  float y1 = fminf(d, e) - 1.f; y1 = y1 < 0.f ? 0.f : y1;
-  float y2 = fmaxf(d, e) + 1.f; y2 = y2 > (float)mh ? (float)mh : y2;
-  return f32x4{x1, x2, y1, y2};
-}
-
-__device__ __forceinline__ int clamp_row(int g, int G) { return g < 0 ? 0 : (g >= G ? G - 1 : g); }
-
 __global__ __launch_bounds__(256) void miou_input_k(const MiParams p) {
   __shared__ __attribute__((aligned(16))) float cs[32];
   __shared__ int cw[3][4];
@@ -56,8 +39,8 @@ __global__ __launch_bounds__(256) void miou_input_k(const MiParams p) {
   int b = 0;                                         // the last image whose first instance is <= j
   for (int i = 1; i < p.B; ++i) b = p.img_off[i] <= j ? i : b;
   if (t < 32) cs[t] = p.coef[(size_t)j * 32 + t];
-  const f32x4 w4 = crop_window(p.box + (size_t)j * 4, p.mh, p.mw);
-  const uint8_t *gt = p.gt + (size_t)clamp_row(p.gt_idx[j], p.G) * p.npix;
+  const f32x4 w4 = ymi_crop_window(p.box + (size_t)j * 4, p.mh, p.mw);
+  const uint8_t *gt = p.gt + (size_t)ymi_clamp_row(p.gt_idx[j], p.G) * p.npix;
   const float *proto = p.proto + (size_t)b * p.npix * 32;
   float *x0 = p.x0 + (size_t)j * p.npix;
   __syncthreads();
@@ -66,7 +49,7 @@ __global__ __launch_bounds__(256) void miou_input_k(const MiParams p) {
     const int py = pix / p.mw, px = pix - py * p.mw;
     const float fx = (float)px, fy = (float)py;
     const bool tgt = gt[pix] != 0;
-    const bool inside = fx >= w4[0] && fx < w4[1] && fy >= w4[2] && fy < w4[3];
+    const bool inside = ymi_in_window(w4, fx, fy);
     float v = 0.f;
     if (inside) {
       const float *src = proto + (size_t)pix * 32;
@@ -77,9 +60,7 @@ __global__ __launch_bounds__(256) void miou_input_k(const MiParams p) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) x = fmaf(pv[e], cs[4 * q + e], x);
       }
-      const float e = expf(-fabsf(x));
-      const float r = 1.f / (1.f + e);
-      v = x >= 0.f ? r : e * r;
+      v = ymi_sigmoid_split(x).p;
       a1 += x > 0.f;
       in += x > 0.f && tgt;
     }
@@ -96,109 +77,24 @@ __global__ __launch_bounds__(256) void miou_input_k(const MiParams p) {
   }
 }
 
+struct MiTerm {
+  static constexpr int STAGED = 0, TAIL = 0;
+  const MiParams &p;
+  __device__ __forceinline__ MiTerm(const MiParams &p_, float *, float *) : p(p_) {}
+  __device__ __forceinline__ bool crop() const { return true; }
+  __device__ __forceinline__ void stage(int, int) {}
+  __device__ __forceinline__ void pixel(int, int, bool) {}
+  __device__ __forceinline__ float grad(float, const ymi_sigmoid &s, int j, int pix) const {
+    return p.d_x0[(size_t)j * p.npix + pix] * s.p * s.om;
+  }
+  __device__ __forceinline__ float mult(float g, int) const { return g; }
+  __device__ __forceinline__ void instance_end(int) {}
+  __device__ __forceinline__ void combine(size_t, int) const {}
+};
+
 __global__ __launch_bounds__(256) void miou_input_bwd_k(const MiParams p) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  float *cs = lds;                                   // [cap][32] coefficient rows
-  float *win = cs + p.cap * 32;                      // [cap][4]  crop window x1, x2, y1, y2
-  float *red = win + p.cap * 4;                      // [4][JC][32] per-wave sums of g * proto[k]
-
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const int b = blockIdx.y, tile = blockIdx.x;
-  const int pix = tile * TP + t;
-  const bool ok = pix < p.npix;
-  const int py = ok ? pix / p.mw : 0, px = ok ? pix - py * p.mw : 0;
-  const float fx = (float)px, fy = (float)py;
-
-  int j0, nj;
-  ymi_image_range(p.img_off, b, p.N, j0, nj);
-  const int j1 = j0 + nj;
-
-  float P[32], dp[32];
-  {
-    const float *src = p.proto + ((size_t)b * p.npix + (ok ? pix : 0)) * 32;
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-      const f32x4 v = *reinterpret_cast<const f32x4 *>(src + 4 * q);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) { P[4 * q + e] = ok ? v[e] : 0.f; dp[4 * q + e] = 0.f; }
-    }
-  }
-
-  for (int c0 = j0; c0 < j1; c0 += p.cap) {
-    const int cnt = j1 - c0 < p.cap ? j1 - c0 : p.cap;
-    __syncthreads();                                 // the previous round's rows have been read
-    for (int i = t; i < cnt * 32; i += 256) cs[i] = p.coef[(size_t)c0 * 32 + i];
-    for (int i = t; i < cnt; i += 256)
-      *reinterpret_cast<f32x4 *>(win + 4 * i) = crop_window(p.box + (size_t)(c0 + i) * 4, p.mh, p.mw);
-    __syncthreads();
-
-    for (int jj0 = 0; jj0 < cnt; jj0 += JC) {
-#pragma unroll 1
-      for (int u = 0; u < JC; ++u) {
-        const int jj = jj0 + u;
-        if (jj >= cnt) break;                        // block-uniform
-        const float *c = cs + jj * 32;
-        const f32x4 w4 = *reinterpret_cast<const f32x4 *>(win + 4 * jj);
-        const bool inside = ok && fx >= w4[0] && fx < w4[1] && fy >= w4[2] && fy < w4[3];
-        const bool any_in = __any(inside) != 0;      // wave-uniform
-        float g = 0.f;
-        if (any_in) {
-          float x = 0.f;
-#pragma unroll
-          for (int k = 0; k < 32; ++k) x = fmaf(P[k], c[k], x);
-          const float e = expf(-fabsf(x));
-          const float r = 1.f / (1.f + e), er = e * r;
-          const float pr = x >= 0.f ? r : er, om = x >= 0.f ? er : r;      // p, 1 - p
-          if (inside) g = p.d_x0[(size_t)(c0 + jj) * p.npix + pix] * pr * om;
-#pragma unroll
-          for (int k = 0; k < 32; ++k) dp[k] = fmaf(g, c[k], dp[k]);
-        }
-        if (p.want_dc) {
-          float v0 = 0.f;
-          if (any_in) {
-            // mask_loss_k's transpose-reduce: after five halving steps lane l holds channel l >> 1 over the 32 lanes that share
-            // its bit 0, the last step adds the other 32
-            float v[32];
-#pragma unroll
-            for (int k = 0; k < 32; ++k) v[k] = g * P[k];
-#pragma unroll
-            for (int s = 0; s < 5; ++s) {
-              const int half = 16 >> s, m = 32 >> s;
-              const bool up = (lane & m) != 0;
-#pragma unroll
-              for (int i = 0; i < half; ++i) {
-                const float keep = up ? v[i + half] : v[i];
-                const float send = up ? v[i] : v[i + half];
-                v[i] = keep + __shfl_xor(send, m);
-              }
-            }
-            v0 = v[0] + __shfl_xor(v[0], 1);
-          }
-          if (!(lane & 1)) red[(wave * JC + u) * 32 + (lane >> 1)] = v0;
-        }
-      }
-      __syncthreads();
-      if (p.want_dc) {
-        // thread = (instance u, channel k): the four waves in order, then the tile's partial
-        const int u = t >> 5, k = t & 31, jj = jj0 + u;
-        if (jj < cnt)
-          p.ws_dc[((size_t)tile * p.N + (c0 + jj)) * 32 + k] =
-              ((red[(0 * JC + u) * 32 + k] + red[(1 * JC + u) * 32 + k]) + red[(2 * JC + u) * 32 + k]) + red[(3 * JC + u) * 32 + k];
-      }
-      __syncthreads();
-    }
-  }
-
-  if (p.d_proto && ok) {
-    float *dst = p.d_proto + ((size_t)b * p.npix + pix) * 32;
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-      f32x4 v;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) v[e] = dp[4 * q + e];
-      *reinterpret_cast<f32x4 *>(dst + 4 * q) = v;
-    }
-  }
+  ymi_lincomb_bwd<MiTerm>(p, lds);
 }
 
 // thread = (instance j, channel k): the tile partials in tile order
@@ -224,16 +120,13 @@ int validate_input_ptrs(const ymi_maskiou_input_desc *d) {
   return ymi_validate_offsets(d->img_off_host, d->B, d->N, 0, d->N);
 }
 
-int ntiles_of(const ymi_maskiou_input_desc *d) { return (d->mh * d->mw + TP - 1) / TP; }
-
 MiParams mi_params(const ymi_maskiou_input_desc *d) {
   MiParams p;
   p.proto = d->proto; p.coef = d->coef; p.box = d->box; p.d_x0 = d->d_x0; p.gt = d->gt; p.gt_idx = d->gt_idx; p.img_off = d->img_off;
   p.x0 = d->x0; p.iou_t = d->iou_t; p.d_proto = d->d_proto; p.d_coef = d->d_coef; p.ws_dc = static_cast<float *>(d->ws);
   p.B = d->B; p.mh = d->mh; p.mw = d->mw; p.npix = d->mh * d->mw; p.N = d->N; p.G = d->G;
-  p.ntiles = ntiles_of(d); p.want_dc = d->d_coef != nullptr;
-  const int n8 = (d->N + 7) / 8 * 8;
-  p.cap = n8 > CAP_MAX ? CAP_MAX : n8;
+  p.ntiles = ymi_lincomb_ntiles(d->mh, d->mw); p.want_dc = d->d_coef != nullptr;
+  p.cap = 0;                                         // the backward's (ymi_lincomb_lds)
   return p;
 }
 
@@ -476,7 +369,7 @@ int validate_head(const ymi_maskiou_head_desc *d) {
 extern "C" int64_t ymi_maskiou_input_ws_bytes(const ymi_maskiou_input_desc *d) {
   const int rc = validate_input(d);
   if (rc) return rc;
-  return ymi_ws_part((int64_t)ntiles_of(d) * d->N * 32);
+  return ymi_ws_part((int64_t)ymi_lincomb_ntiles(d->mh, d->mw) * d->N * 32);
 }
 
 extern "C" int ymi_maskiou_input_f32(const ymi_maskiou_input_desc *d, void *stream) {
@@ -496,8 +389,8 @@ extern "C" int ymi_maskiou_input_bwd_f32(const ymi_maskiou_input_desc *d, void *
   if (!d->d_x0 || (!d->d_proto && !d->d_coef) || (d->d_coef && !d->ws)) return YMI_ENULL;
   if (((uintptr_t)d->d_proto | (uintptr_t)d->ws) & 15) return YMI_ESHAPE;
   if (d->ws_bytes < (d->d_coef ? ymi_maskiou_input_ws_bytes(d) : 0)) return YMI_ESHAPE;
-  const MiParams p = mi_params(d);
-  const size_t lds = ((size_t)p.cap * (32 + 4) + 4 * JC * 32) * sizeof(float);      // <= 22 KB
+  MiParams p = mi_params(d);
+  const size_t lds = ymi_lincomb_lds<MiTerm>(d->N, CAP_MAX, p.cap);                // <= 22 KB
   rc = ymi_launch(miou_input_bwd_k, dim3(p.ntiles, d->B), dim3(256), lds, stream, p);
   if (!rc && d->d_coef) rc = ymi_launch(miou_dcoef_k, dim3((int)(((long)d->N * 32 + 255) / 256)), dim3(256), 0, stream, p);
   return rc;
