@@ -6,10 +6,13 @@ forward_backbone / forward_fpn / forward_heads / forward_train), so the script r
 small ones of tests/test_gpu_heads_train.py, tests/test_gpu_fpn_train.py and tests/test_gpu_backbone_train.py; the inputs come from
 seeded CPU generators.  Per case: y and every gradient (for a bottleneck the running statistics afterwards too).  The net-level cases
 run on the model of tests/test_gpu_stem_train.py::test_multibox_loss_from_the_images (seeded ResNet-50 stages, 32 features, 96 x 96
-images) with random inputs: every output and every parameter gradient, with frozen and with batch statistics.
+images) with random inputs: every output and every parameter gradient, with frozen and with batch statistics.  The weight-gradient
+entries ymi_conv_wgrad_nhwc_f32 and ymi_stem_wgrad_nhwc_f32 are also called on their own (WGRAD_SHAPES, STEM_WGRAD_SHAPES) at the edges
+of their position walk and chunk plan; the C ABI they are called through is that of every tree with these entries.
 
     python tools/train_digest.py > digests.txt
 """
+import ctypes as C
 import hashlib
 import os
 import sys
@@ -23,6 +26,7 @@ sys.path.insert(0, os.path.join(ROOT, 'tests'))
 import backbone_train_ref as R  # noqa: E402
 import heads_train_ref as H  # noqa: E402
 import yolact_amd  # noqa: E402, F401
+from yolact_amd import _lib as L  # noqa: E402
 from yolact_amd import modules as M  # noqa: E402
 from yolact_amd.layers import train_ops as TO  # noqa: E402
 
@@ -32,6 +36,11 @@ DOWN_SHAPES = [(3, 2, 5, 7, 32, 12), (3, 1, 8, 6, 64, 40), (1, 2, 7, 9, 64, 32)]
 PLAIN_GEOS = [(3, 1, 32, 40), (1, 1, 64, 32), (3, 2, 32, 32), (1, 2, 64, 96), (3, 2, 64, 40)]   # (k, stride, Cin, Cout) at B = 2, 9 x 7
 BLOCK_SPECS = {'identity': (128, 32, 1, False), 'proj_s1': (64, 32, 1, True), 'proj_s2': (64, 32, 2, True), 'entry': (64, 64, 1, True)}
 ACTS = (None, 'relu', 'tanh')
+# (k, stride, B, H, W, Cin, Cout): a map one pixel wide (the walk wraps twice per step) at both strides; 1 058 positions in 12 chunks of 96,
+# the last of 2; two and four column tiles per wave at stride 2
+WGRAD_SHAPES = [(3, 1, 3, 5, 1, 32, 32), (3, 2, 3, 5, 1, 32, 32), (3, 1, 2, 23, 23, 256, 32), (3, 2, 2, 5, 7, 32, 160),
+                (3, 2, 2, 5, 7, 32, 288)]
+STEM_WGRAD_SHAPES = [(1, 9, 9, 32)]                                                            # (B, H, W, Cout)
 
 
 def emit(case, name, t):
@@ -170,6 +179,47 @@ def stem_cases():
     backward_and_emit('max_pool_3x3_s2', [y], [up], leaves)
 
 
+def wgrad_cases():
+    """The two weight-gradient entries on their own: dw [K, Cout] as the kernels leave it, and db."""
+    lib = L.lib()
+    for k, stride, B, H, W, Cin, Cout in WGRAD_SHAPES:
+        case = 'wgrad %dx%d_s%d_b%d_%dx%d_%dto%d' % (k, k, stride, B, H, W, Cin, Cout)
+        g = torch.Generator().manual_seed(15)
+        Ho, Wo = (down(H), down(W)) if stride == 2 else (H, W)
+        x = torch.randn(B, H, W, Cin, generator=g).to(DEV)
+        gy = torch.zeros(B, Ho, Wo, (Cout + 31) // 32 * 32)
+        gy[..., :Cout] = torch.randn(B, Ho, Wo, Cout, generator=g)
+        gy = gy.to(DEV)
+        dw, db = torch.zeros(k * k * Cin, Cout, device=DEV), torch.zeros(Cout, device=DEV)
+        d = L.ConvWgradDesc()
+        d.x, d.g, d.dw, d.db = x.data_ptr(), gy.data_ptr(), dw.data_ptr(), db.data_ptr()
+        d.B, d.H, d.W, d.Cin, d.Cout, d.ldg, d.kh, d.kw, d.pad, d.stride = B, H, W, Cin, Cout, gy.shape[3], k, k, k // 2, stride
+        nbytes = lib.ymi_workspace_bytes(L.WS_CONV_WGRAD, C.byref(d))
+        assert nbytes > 0, nbytes
+        ws = torch.zeros(nbytes // 4, device=DEV)
+        d.ws, d.ws_bytes = ws.data_ptr(), nbytes
+        L.check(lib.ymi_conv_wgrad_nhwc_f32(C.byref(d), L.stream_ptr()), case)
+        torch.cuda.synchronize()
+        emit(case, 'dw', dw)
+        emit(case, 'db', db)
+    for B, H, W, Cout in STEM_WGRAD_SHAPES:
+        case = 'stem_wgrad b%d_%dx%d_to%d' % (B, H, W, Cout)
+        g = torch.Generator().manual_seed(16)
+        x4 = torch.nn.functional.pad(torch.randn(B, H, W, 3, generator=g), (0, 1)).to(DEV)
+        gy = torch.randn(B, down(H), down(W), Cout, generator=g).to(DEV)
+        dw = torch.zeros(147, Cout, device=DEV)
+        d = L.StemWgradDesc()
+        d.x, d.g, d.dw = x4.data_ptr(), gy.data_ptr(), dw.data_ptr()
+        d.B, d.H, d.W, d.Cout, d.ldg = B, H, W, Cout, Cout
+        nbytes = lib.ymi_workspace_bytes(L.WS_STEM_WGRAD, C.byref(d))
+        assert nbytes > 0, nbytes
+        ws = torch.zeros(nbytes // 4, device=DEV)
+        d.ws, d.ws_bytes = ws.data_ptr(), nbytes
+        L.check(lib.ymi_stem_wgrad_nhwc_f32(C.byref(d), L.stream_ptr()), case)
+        torch.cuda.synchronize()
+        emit(case, 'dw', dw)
+
+
 def small_net():
     """The model of test_multibox_loss_from_the_images: yolact_resnet50_config at 32 features, seeded stages, all on the GPU."""
     yolact_amd.set_cfg('yolact_resnet50_config')
@@ -256,6 +306,7 @@ def main():
             block_case('bottleneck %s %s' % (variant, 'stats' if batch_stats else 'frozen'), spec, batch_stats)
     others()
     stem_cases()
+    wgrad_cases()
     net_cases()
 
 

@@ -139,7 +139,7 @@ template <bool K3> __global__ __launch_bounds__(256, 2) void dgrad_s2_k(const Dg
     }
   }
 
-  // lane (i, h) holds of pixel i the channels (r & 3) + 8 (r >> 2) + 4 h of each row tile: four 16-byte stores per tile
+  // lane (i, h) holds of pixel i the channels (r & 3) + 8 (r >> 2) + 4 h of each row tile (grad_common.h ymi_acc_row): four 16-byte stores
   char *db = reinterpret_cast<char *>(p.dx);
 #pragma unroll
   for (int m = 0; m < 2; ++m) {

@@ -4,16 +4,14 @@
 //
 //   ymi_act_bwd_f32             g[pos,c] = dy[pos,c] * act'(y[pos,c]) from the layer's OUTPUT y (ReLU: y > 0, tanh: 1 - y^2), written
 //                               with the channel stride the consumers want; the padding channels get exact zeros.
-//   ymi_conv_wgrad_nhwc_f32     dw[k,co] = sum_pos im2col(x)[pos,k] g[pos,co], db[co] = sum_pos g[pos,co] on the exact-fp32 matrix
-//                               instruction (v_mfma_f32_32x32x2_f32: fp32 in, fp32 accumulate).  The POSITIONS are the instruction's k
-//                               index, so both operands are read in their natural NHWC layout: lane = channel, the two halves of a
-//                               wave = two consecutive positions.  A block owns one (tap, 32 input channels), a chunk of positions and
-//                               NT * 128 output channels (each wave NT column tiles of 32); the tap only shifts the address of x, a
-//                               shifted pixel outside the image contributes 0.  Every instruction needs one 4-byte load per lane
-//                               and operand, so the loads of 32 positions are issued as a group, one group ahead of the MFMAs that use
-//                               them (two waves per SIMD for NT <= 2, one for NT = 4: 198 / 250 / 357 registers, no spills).  db
-//                               falls out of the g fragments of the blocks of (tap 0, chunk 0 of the channels).  The chunk partial
-//                               sums go to the workspace, a second launch adds them in chunk order.
+//   ymi_conv_wgrad_nhwc_f32     dw[k,co] = sum_pos im2col(x)[pos,k] g[pos,co], db[co] = sum_pos g[pos,co] in the structure of
+//                               grad_common.h (positions = the matrix instruction's k index, chunk partials, an ordered sum).  A
+//                               block owns one (tap, 32 input channels), a chunk of positions and NT * 128 output channels (each wave
+//                               NT column tiles of 32); the tap only shifts the address of x, a shifted pixel outside the image
+//                               contributes 0.  Every instruction needs one 4-byte load per lane and operand, so the loads of 32
+//                               positions are issued as a group, one group ahead of the MFMAs that use them (two waves per SIMD for
+//                               NT <= 2, one for NT = 4: 198 / 250 / 357 registers, no spills).  db falls out of the g fragments of
+//                               the blocks of (tap 0, chunk 0 of the channels).
 //   ymi_bilinear_bwd_nhwc_f32   the backward of ymi_bilinear_nhwc_f32 for Ho = 2 Hi, Wo = 2 Wi as a gather: an input pixel (iy, ix)
 //                               walks the output rows 2 iy - 2 .. 2 iy + 2 and columns 2 ix - 2 .. 2 ix + 2 in order, asks
 //                               upsample_math.h which of them read it and with what weight, and sums.
@@ -23,7 +21,7 @@
 //   ymi_bilinear_size_bwd_nhwc_f32   the backward of the size-form interpolation for any Ho >= Hi, Wo >= Wi (the pyramid of a 550 x 550
 //                               image is 69 -> 35 -> 18: neither step is x2), the same gather with the candidate outputs found by
 //                               inverting the coordinate map.
-#include "loss_common.h"
+#include "grad_common.h"
 #include "upsample_math.h"
 #include "../../include/yolact_amd.h"
 
@@ -65,9 +63,6 @@ struct WgParams {
   int Ho, Wo;                                          // the map of g (stride 2; H, W at stride 1)
 };
 
-// row of a 32 x 32 accumulator held in register r by this lane (column = lane & 31)
-__device__ __forceinline__ int acc_row(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
-
 // NT: 32-column output-channel tiles per wave (a block covers NT * 128 output channels, gridDim.z such groups)
 // S: the convolution's stride, 1 or 2.  A template parameter, so that the stride-1 instantiation carries nothing of stride 2: the
 // positions are those of g, [B, Ho, Wo]; at stride 2 tap (ky, kx) of position (n, oy, ox) reads x at (2 oy + ky - pad, 2 ox + kx - pad).
@@ -104,7 +99,7 @@ template <int NT, int S> __global__ __launch_bounds__(256, NT == 4 ? 1 : 2) void
     gc[j] = 4u * (unsigned)(col[j] ? o : 0);
   }
 
-  // this lane's positions: pos0 + kk, + 2, + 4, ..; their pixel coordinates are carried along
+  // this lane's positions: pos0 + kk, + 2, + 4, ..; their pixel coordinates are carried along (grad_common.h: why not ymi_pos_walk)
   long pos = pos0 + kk;
   const int PW = S == 1 ? p.W : p.Wo, PH = S == 1 ? p.H : p.Ho;   // the map the positions run over
   int ox = (int)(pos % PW), oy = (int)((pos / PW) % PH);
@@ -178,7 +173,7 @@ template <int NT, int S> __global__ __launch_bounds__(256, NT == 4 ? 1 : 2) void
       const int o = ob + (wave + 4 * j) * 32 + ln;
       if (j < nact && o < p.Cout) {
 #pragma unroll
-        for (int r = 0; r < 16; ++r) dst[(size_t)acc_row(r, kk) * p.Cout + o] = acc[j][r];
+        for (int r = 0; r < 16; ++r) dst[(size_t)ymi_acc_row(r, kk) * p.Cout + o] = acc[j][r];
       }
     }
   }
@@ -193,20 +188,16 @@ template <int NT, int S> __global__ __launch_bounds__(256, NT == 4 ? 1 : 2) void
 #endif
 }
 
-// thread = one element of dw [K, Cout], then of db [Cout]: the chunk partials in chunk order
+// thread = one element of dw [K, Cout], then of db [Cout]
 __global__ __launch_bounds__(256) void wgrad_sum_k(const WgParams p) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x, nw = (long)p.K * p.Cout;
   if (i < nw) {
     if (!p.want_w) return;
-    float s = 0.f;
-    for (int c = 0; c < p.nchunks; ++c) s += p.ws_w[(size_t)c * nw + i];
-    p.dw[i] = s;
+    p.dw[i] = ymi_chunk_sum(p.ws_w, nw, p.nchunks, i);
   } else if (i < nw + p.Cout) {
     if (!p.want_b) return;
     const int o = (int)(i - nw);
-    float s = 0.f;
-    for (int c = 0; c < p.nchunks; ++c) s += p.ws_b[(size_t)c * p.Cout + o];
-    p.db[o] = s;
+    p.db[o] = ymi_chunk_sum(p.ws_b, p.Cout, p.nchunks, o);
   }
 }
 
@@ -227,20 +218,12 @@ int validate_wgrad(const ymi_conv_wgrad_desc *d) {
 
 struct WgPlan { int nt, gx, gz, nchunks; long per; };
 
-// the decomposition for a validated shape: about 1024 blocks, chunks of a multiple of 32 positions (of g)
+// the decomposition for a validated shape: about 1024 blocks, the (tap, 32 input channels) blocks counted even for a bias alone
 WgPlan wgrad_plan(const ymi_conv_wgrad_desc *d) {
-  WgPlan w;
-  const long P = wgrad_positions(d);
-  const int tiles = (d->Cout + 31) / 32;
-  w.nt = tiles <= 4 ? 1 : (tiles <= 8 ? 2 : 4);
-  w.gz = (d->Cout + w.nt * 128 - 1) / (w.nt * 128);
-  w.gx = d->kh * d->kw * (d->Cin / 32);
-  const long mb = (P + 31) / 32;
-  long sp = (1024 + (long)w.gx * w.gz - 1) / ((long)w.gx * w.gz);
-  sp = sp < 1 ? 1 : (sp > mb ? mb : sp);
-  w.per = (mb + sp - 1) / sp * 32;
-  w.nchunks = (int)((P + w.per - 1) / w.per);
-  return w;
+  const ymi_wgrad_tiles t = ymi_wgrad_nt(d->Cout);
+  const int gx = d->kh * d->kw * (d->Cin / 32);
+  const ymi_chunks c = ymi_chunk_plan(wgrad_positions(d), 1024, (long)gx * t.gz);
+  return {t.nt, gx, t.gz, c.nchunks, c.per};
 }
 
 // ---- x2 bilinear upsample backward ----------------------------------------------------------------------------------------------------
@@ -386,14 +369,8 @@ extern "C" int ymi_conv_wgrad_nhwc_f32(const ymi_conv_wgrad_desc *d, void *strea
   p.ws_w = static_cast<float *>(d->ws);
   p.ws_b = reinterpret_cast<float *>(static_cast<char *>(d->ws) + ymi_ws_part((int64_t)w.nchunks * p.K * d->Cout));
   const dim3 grid(d->dw ? w.gx : 1, w.nchunks, w.gz);     // bias alone: the blocks of tap 0, channels 0 .. 31
-  int rl;
-  if (d->stride == 2) {
-    rl = w.nt == 1 ? ymi_launch(wgrad_k<1, 2>, grid, dim3(256), 0, stream, p)
-                   : (w.nt == 2 ? ymi_launch(wgrad_k<2, 2>, grid, dim3(256), 0, stream, p) : ymi_launch(wgrad_k<4, 2>, grid, dim3(256), 0, stream, p));
-  } else {
-    rl = w.nt == 1 ? ymi_launch(wgrad_k<1, 1>, grid, dim3(256), 0, stream, p)
-                   : (w.nt == 2 ? ymi_launch(wgrad_k<2, 1>, grid, dim3(256), 0, stream, p) : ymi_launch(wgrad_k<4, 1>, grid, dim3(256), 0, stream, p));
-  }
+  void (*const kernels[2][3])(WgParams) = {{wgrad_k<1, 1>, wgrad_k<2, 1>, wgrad_k<4, 1>}, {wgrad_k<1, 2>, wgrad_k<2, 2>, wgrad_k<4, 2>}};
+  int rl = ymi_launch(kernels[d->stride == 2][w.nt >> 1], grid, dim3(256), 0, stream, p);      // nt = 1, 2, 4
   if (!rl) rl = ymi_launch(wgrad_sum_k, dim3((unsigned)(((long)p.K * d->Cout + d->Cout + 255) / 256)), dim3(256), 0, stream, p);
   return rl;
 }

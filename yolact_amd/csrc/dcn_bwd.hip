@@ -29,7 +29,7 @@
 //
 // NOT bit-reproducible from run to run: gx, gW, gbias (and goff / gmask on small maps) are sums of float atomics, whose order of
 // arrival varies.  The error of any order is that of an fp32 sum of the same terms.
-#include "common.h"
+#include "grad_common.h"
 #include "../../include/yolact_amd.h"
 
 namespace {
@@ -69,9 +69,6 @@ __device__ __forceinline__ Pt dcn_point(const BwdParams &p, int m, int tap) {
   g.fl = (unsigned)(t_ && l_) | ((unsigned)(t_ && r_) << 1) | ((unsigned)(b_ && l_) << 2) | ((unsigned)(b_ && r_) << 3);
   return g;
 }
-
-// row of a 32 x 32 accumulator held in register r by this lane (column = lane & 31)
-__device__ __forceinline__ int acc_row(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
 
 __global__ __launch_bounds__(256) void dcn_bwd_data_k(const BwdParams p) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -137,12 +134,12 @@ __global__ __launch_bounds__(256) void dcn_bwd_data_k(const BwdParams p) {
         }
       }
       if (act) {
-        // the gcol tile is in registers: register r = pixel acc_row(r, kk), lane = channel c0 + ln
+        // the gcol tile is in registers: register r = pixel ymi_acc_row(r, kk), lane = channel c0 + ln
         const float *xc = p.x + c0 + ln;
         float *gxc = p.gx ? p.gx + c0 + ln : nullptr;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int i = acc_row(r, kk);
+          const int i = ymi_acc_row(r, kk);
           const unsigned fl = g_fl[i];
           if (fl) {
             const int o1 = g_o1[i];
@@ -179,7 +176,7 @@ __global__ __launch_bounds__(256) void dcn_bwd_data_k(const BwdParams p) {
           pw[r] += __shfl_xor(pw[r], d);
         }
         if (ln == r) {
-          const int i = acc_row(r, kk);
+          const int i = ymi_acc_row(r, kk);
           red[0][wave][i] = pm[r]; red[1][wave][i] = ph[r]; red[2][wave][i] = pw[r];
         }
       }
@@ -267,7 +264,7 @@ __global__ __launch_bounds__(256) void dcn_bwd_weight_k(const BwdParams p) {
     for (int j = 0; j < NT; ++j)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int o = ob + (wave + 4 * j) * 32 + acc_row(r, kk);
+        const int o = ob + (wave + 4 * j) * 32 + ymi_acc_row(r, kk);
         if (o < p.Cout) atomicAdd(p.gw + ((size_t)o * 9 + tap) * p.Cin + c0 + ln, acc[j][r]);
       }
   }
@@ -303,6 +300,7 @@ extern "C" int ymi_dcn_v2_backward_f32(const ymi_dcn_bwd_desc *d, void *stream) 
   if (((uintptr_t)d->x | (uintptr_t)d->gy | (uintptr_t)d->gx) & 15) return YMI_ESHAPE;
 
   hipStream_t s = (hipStream_t)stream;
+  int rc = YMI_OK;
   BwdParams p;
   p.x = d->x; p.offmask = d->offmask; p.w = d->w; p.gy = d->gy;
   p.gx = d->gx; p.goff = d->g_offset; p.gmask = d->g_mask; p.gw = d->gw; p.gbias = d->gbias;
@@ -324,28 +322,17 @@ extern "C" int ymi_dcn_v2_backward_f32(const ymi_dcn_bwd_desc *d, void *stream) 
       if (d->g_offset && hipMemsetAsync(d->g_offset, 0, (size_t)M * 18 * sizeof(float), s) != hipSuccess) return ymi_launch_status();
       if (d->g_mask && hipMemsetAsync(d->g_mask, 0, (size_t)M * 9 * sizeof(float), s) != hipSuccess) return ymi_launch_status();
     }
-    hipLaunchKernelGGL(dcn_bwd_data_k, dim3(bm, cs), dim3(256), 0, s, p);
-    const int rc = ymi_launch_status();
-    if (rc) return rc;
+    rc = ymi_launch(dcn_bwd_data_k, dim3(bm, cs), dim3(256), 0, stream, p);
   }
-  if (want_w) {
+  if (!rc && want_w) {
     if (d->gw && hipMemsetAsync(d->gw, 0, (size_t)d->Cout * 9 * d->Cin * sizeof(float), s) != hipSuccess) return ymi_launch_status();
     if (d->gbias && hipMemsetAsync(d->gbias, 0, (size_t)d->Cout * sizeof(float), s) != hipSuccess) return ymi_launch_status();
-    const int gx_ = d->gw ? 9 * p.ncc : 1;
-    const int tiles = (d->Cout + 31) / 32;
-    const int nt = tiles <= 4 ? 1 : (tiles <= 8 ? 2 : 4);
-    const int gz = (d->Cout + nt * 128 - 1) / (nt * 128);
-    // ranges of m: about 1024 blocks in all, at least 32 pixels each
-    const int mb = (int)((M + 31) / 32);
-    int sp = (1024 + gx_ * gz - 1) / (gx_ * gz);
-    sp = sp < 1 ? 1 : (sp > mb ? mb : sp);
-    p.m_per_blk = ((mb + sp - 1) / sp) * 32;
-    const int gy_ = (int)((M + p.m_per_blk - 1) / p.m_per_blk);
-    const dim3 grid(gx_, gy_, gz);
-    if (nt == 1) hipLaunchKernelGGL(dcn_bwd_weight_k<1>, grid, dim3(256), 0, s, p);
-    else if (nt == 2) hipLaunchKernelGGL(dcn_bwd_weight_k<2>, grid, dim3(256), 0, s, p);
-    else hipLaunchKernelGGL(dcn_bwd_weight_k<4>, grid, dim3(256), 0, s, p);
-    return ymi_launch_status();
+    const int gx_ = d->gw ? 9 * p.ncc : 1;              // bias alone: the blocks of tap 0, channels 0 .. 31
+    const ymi_wgrad_tiles t = ymi_wgrad_nt(d->Cout);
+    const ymi_chunks c = ymi_chunk_plan(M, 1024, (long)gx_ * t.gz);       // ranges of m
+    p.m_per_blk = (int)c.per;
+    void (*const kernels[3])(BwdParams) = {dcn_bwd_weight_k<1>, dcn_bwd_weight_k<2>, dcn_bwd_weight_k<4>};
+    rc = ymi_launch(kernels[t.nt >> 1], dim3(gx_, c.nchunks, t.gz), dim3(256), 0, stream, p);      // nt = 1, 2, 4
   }
-  return YMI_OK;
+  return rc;
 }

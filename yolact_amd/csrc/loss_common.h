@@ -6,6 +6,7 @@
 //                 integer counts: c0 + c1, (c0 + c1) + (c2 + c3)                                     (ymi_waves_count)
 //   the loss      256 threads: thread t adds src[t], src[t + 256], .. in that order, then a tree over distances 128, 64, .. 1 in
 //                 which slot t takes slot t + d                                                      (ymi_sum256)
+//   chunk / tile partials: ascending index from +0.0                                                  (ymi_chunk_sum)
 // What a term does to the total (alpha, alpha / mh / mw, a precomputed alpha / HW) stays in its own *_sum_k: those roundings differ.
 #pragma once
 #include "common.h"
@@ -53,6 +54,13 @@ __device__ __forceinline__ float ymi_sum256(const float *src, long total) {
     __syncthreads();
   }
   return part[0];
+}
+
+// element i of the n partials ws[c * stride + i] that an earlier launch left in the workspace, one per chunk or tile c
+__device__ __forceinline__ float ymi_chunk_sum(const float *ws, size_t stride, int n, size_t i) {
+  float s = 0.f;
+  for (int c = 0; c < n; ++c) s += ws[c * stride + i];
+  return s;
 }
 
 // image b's rows [g0, g0 + n) from device offsets nobody validated on the device: never outside [0, total), never more than cap

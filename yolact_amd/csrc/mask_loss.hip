@@ -91,15 +91,9 @@ __global__ __launch_bounds__(256) void mask_loss_dcoef_k(const MlParams p) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   if (i >= (long)p.N * 32) return;
   const int j = (int)(i >> 5), k = (int)(i & 31);
-  if (p.d_coef) {
-    float s = 0.f;
-    for (int tl = 0; tl < p.ntiles; ++tl) s += p.ws_dc[((size_t)tl * p.N + j) * 32 + k];
-    p.d_coef[i] = s * inst_scale(p, j);
-  }
+  if (p.d_coef) p.d_coef[i] = ymi_chunk_sum(p.ws_dc, (size_t)p.N * 32, p.ntiles, i) * inst_scale(p, j);
   if (k == 0) {
-    float s = 0.f;
-    for (int tl = 0; tl < p.ntiles; ++tl) s += p.ws_l[(size_t)tl * p.N + j];
-    const float L = roi_normalise(p, p.box + (size_t)j * 4, s);
+    const float L = roi_normalise(p, p.box + (size_t)j * 4, ymi_chunk_sum(p.ws_l, p.N, p.ntiles, j));
     if (p.loss_inst) p.loss_inst[j] = L;
     p.ws_wl[j] = L * p.weight[j];
   }

@@ -101,9 +101,7 @@ __global__ __launch_bounds__(256) void miou_input_bwd_k(const MiParams p) {
 __global__ __launch_bounds__(256) void miou_dcoef_k(const MiParams p) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   if (i >= (long)p.N * 32) return;
-  float s = 0.f;
-  for (int tl = 0; tl < p.ntiles; ++tl) s += p.ws_dc[(size_t)tl * p.N * 32 + i];
-  p.d_coef[i] = s;
+  p.d_coef[i] = ymi_chunk_sum(p.ws_dc, (size_t)p.N * 32, p.ntiles, i);
 }
 
 int validate_input(const ymi_maskiou_input_desc *d) {
@@ -274,8 +272,7 @@ template <int RK, int RC> __global__ __launch_bounds__(256) void conv_dw_k(const
 __global__ __launch_bounds__(256) void conv_dw_sum_k(const CbParams p) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x, n = (long)(p.K + 1) * p.ldw;
   if (i >= n) return;
-  float s = 0.f;
-  for (int c = 0; c < p.nchunks; ++c) s += p.ws[(size_t)c * n + i];
+  const float s = ymi_chunk_sum(p.ws, n, p.nchunks, i);
   const long k = i / p.ldw;
   const int co = (int)(i - k * p.ldw);
   if (k < p.K) { if (p.dw) p.dw[i] = s; }

@@ -2,22 +2,20 @@
 // NHWC fp32, without atomics (the same inputs give the same bits).  The forward convolution runs on ymi_conv2d_nhwc_f32 (the Cin-4
 // loader), BatchNorm + ReLU on csrc/bn_train.hip; what is new here:
 //
-//   ymi_stem_wgrad_nhwc_f32     dw[k,co] = sum_pos x[n, 2 oy + ky - 3, 2 ox + kx - 3, ci] g[pos,co], k = (ky*7 + kx)*3 + ci, on the exact-fp32
-//                               matrix instruction (v_mfma_f32_32x32x2_f32) with the POSITIONS as its k index, as csrc/conv_train.hip
-//                               does.  x is the NHWC-4 image the forward reads, so for one output pixel and one ky the 8 pixels from
+//   ymi_stem_wgrad_nhwc_f32     dw[k,co] = sum_pos x[n, 2 oy + ky - 3, 2 ox + kx - 3, ci] g[pos,co], k = (ky*7 + kx)*3 + ci, in the structure
+//                               of grad_common.h (positions = the matrix instruction's k index, chunk partials, an ordered sum).
+//                               x is the NHWC-4 image the forward reads, so for one output pixel and one ky the 8 pixels from
 //                               column 2 ox - 3 on are 32 CONSECUTIVE floats: the rows (kx, c4) of one 32-row tile, of which kx = 7 and
-//                               c4 = 3 are discarded (28 * 3 / 4 = 21 of 32 rows are used).  lane = row, the two halves of a wave = two
-//                               consecutive positions; the B operand is 32 consecutive channels of g.  A block owns a chunk of positions
-//                               and 64 output channels; its wave w owns ky = w and ky = w + 4 (wave 3: ky = 3 alone), at most
-//                               2 x 2 accumulator tiles = 64 registers.  A lane outside the image (left / right border, a row above or
-//                               below), in a discarded row or past the chunk is masked to 0 by a select, never by a product, so the
-//                               padding channel may hold anything.  The chunk partial sums go to the workspace, a second launch adds
-//                               them in chunk order.
+//                               c4 = 3 are discarded (28 * 3 / 4 = 21 of 32 rows are used); the B operand is 32 consecutive channels
+//                               of g.  A block owns a chunk of positions and 64 output channels; its wave w owns ky = w and
+//                               ky = w + 4 (wave 3: ky = 3 alone), at most 2 x 2 accumulator tiles = 64 registers.  A lane outside the
+//                               image (left / right border, a row above or below), in a discarded row or past the chunk is masked
+//                               to 0 by a select, never by a product, so the padding channel may hold anything.
 //   ymi_maxpool_fwd_nhwc_f32    3x3 / 2 / pad 1, -inf outside, `v > m ? v : m` in row-major window order.
 //   ymi_maxpool_bwd_nhwc_f32    a gather: an input pixel looks at the 1, 2, 2 or 4 windows that hold it (by its row and column parity),
 //                               RECOMPUTES each window's argmax from x (greater than everything before it in row-major window order,
 //                               not smaller than anything after it: the first of equal maxima) and adds dy where it is its own.
-#include "loss_common.h"
+#include "grad_common.h"
 #include "../../include/yolact_amd.h"
 
 namespace {
@@ -32,9 +30,6 @@ struct SwParams {
 
 constexpr int SW_K = 147;                              // 7 * 7 * 3 rows of dw
 constexpr int SW_G = 8;                                // instructions per load group (16 positions)
-
-// row of a 32 x 32 accumulator held in register r by this lane (column = lane & 31)
-__device__ __forceinline__ int sw_acc_row(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
 
 __global__ __launch_bounds__(256, 2) void stem_wgrad_k(const SwParams p) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -56,9 +51,7 @@ __global__ __launch_bounds__(256, 2) void stem_wgrad_k(const SwParams p) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
-  // this lane's positions: pos0 + kk, + 2, + 4, ..; their pixel coordinates are carried along
-  long pos = pos0 + kk;
-  int ox = (int)(pos % p.Wo), oy = (int)((pos / p.Wo) % p.Ho), n = (int)(pos / ((long)p.Wo * p.Ho));
+  ymi_pos_walk at(pos0 + kk, p.Wo, p.Ho);      // this lane's positions: pos0 + kk, + 2, + 4, ..
   // element offsets fit 32 bits (validate_stem_wgrad)
   const float *xb = p.x, *gb = p.g;
 
@@ -67,27 +60,23 @@ __global__ __launch_bounds__(256, 2) void stem_wgrad_k(const SwParams p) {
     G.am[0] = 0u; G.am[1] = 0u;
 #pragma unroll
     for (int s = 0; s < SW_G; ++s) {
-      const bool live = pos < pos1;
-      const int ix = 2 * ox - 3 + dxl;
+      const bool live = at.pos < pos1;
+      const int ix = 2 * at.ox - 3 + dxl;
       const bool colok = live && row_used && (unsigned)ix < (unsigned)p.W;
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
-        const int iy = 2 * oy + wave + 4 * i - 3;
+        const int iy = 2 * at.oy + wave + 4 * i - 3;
         const bool inside = i < nky && colok && (unsigned)iy < (unsigned)p.H;
         G.am[i] |= (inside ? 1u : 0u) << s;
         // the lane's own element: pixel (n, iy, ix), channel ln & 3; element 0 where it is masked (never read out of bounds)
-        const unsigned xo = inside ? (unsigned)(((n * p.H + iy) * p.W + ix) * 4 + (ln & 3)) : 0u;
+        const unsigned xo = inside ? (unsigned)(((at.n * p.H + iy) * p.W + ix) * 4 + (ln & 3)) : 0u;
         G.a[i][s] = i < nky ? xb[xo] : 0.f;
       }
       // a position past the chunk loads nothing and contributes 0
-      const unsigned gi = (unsigned)pos * (unsigned)p.ldg + (unsigned)(ob + ln);
+      const unsigned gi = (unsigned)at.pos * (unsigned)p.ldg + (unsigned)(ob + ln);
 #pragma unroll
       for (int j = 0; j < 2; ++j) G.b[j][s] = (j < nct && live) ? gb[gi + 32u * j] : 0.f;
-      pos += 2; ox += 2;
-      if (ox >= p.Wo) { ox -= p.Wo; ++oy; }             // twice: Wo may be 1
-      if (ox >= p.Wo) { ox -= p.Wo; ++oy; }
-      if (oy >= p.Ho) { oy -= p.Ho; ++n; }
-      if (oy >= p.Ho) { oy -= p.Ho; ++n; }
+      at.step2(p.Wo, p.Ho);
     }
   };
   auto consume = [&](const Grp &G) {
@@ -129,7 +118,7 @@ __global__ __launch_bounds__(256, 2) void stem_wgrad_k(const SwParams p) {
           const int o = ob + 32 * j + ln;
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
-            const int row = sw_acc_row(r, kk), kx = row >> 2, c = row & 3;
+            const int row = ymi_acc_row(r, kk), kx = row >> 2, c = row & 3;
             if (kx < 7 && c < 3) dst[(size_t)((ky * 7 + kx) * 3 + c) * p.Cout + o] = acc[i][j][r];
           }
         }
@@ -139,13 +128,11 @@ __global__ __launch_bounds__(256, 2) void stem_wgrad_k(const SwParams p) {
 #endif
 }
 
-// thread = one element of dw [147, Cout]: the chunk partials in chunk order from +0.0
+// thread = one element of dw [147, Cout]
 __global__ __launch_bounds__(256) void stem_wgrad_sum_k(const SwParams p) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x, nw = (long)SW_K * p.Cout;
   if (i >= nw) return;
-  float s = 0.f;
-  for (int c = 0; c < p.nchunks; ++c) s += p.ws[(size_t)c * nw + i];
-  p.dw[i] = s;
+  p.dw[i] = ymi_chunk_sum(p.ws, nw, p.nchunks, i);
 }
 
 inline int stem_out(int size) { return (size - 1) / 2 + 1; }
@@ -160,15 +147,8 @@ int validate_stem_wgrad(const ymi_stem_wgrad_desc *d) {
   return YMI_OK;
 }
 
-// the chunks of a validated shape: about 512 / ceil(Cout / 64) of them, each a multiple of 32 positions (a function of the shape only)
-void stem_wgrad_plan(const ymi_stem_wgrad_desc *d, long &per, int &nchunks) {
-  const long P = stem_positions(d), mb = (P + 31) / 32;
-  const int gz = (d->Cout + 63) / 64;
-  long sp = (512 + gz - 1) / gz;
-  sp = sp > mb ? mb : sp;
-  per = (mb + sp - 1) / sp * 32;
-  nchunks = (int)((P + per - 1) / per);
-}
+// the chunks of a validated shape: about 512 blocks over the ceil(Cout / 64) channel groups
+ymi_chunks stem_wgrad_plan(const ymi_stem_wgrad_desc *d) { return ymi_chunk_plan(stem_positions(d), 512, (d->Cout + 63) / 64); }
 
 // ---- max-pool 3x3 / 2 / pad 1 ------------------------------------------------------------------------------------------------------------
 struct MpParams {
@@ -257,9 +237,7 @@ int validate_maxpool(int B, int H, int W, int C) {
 extern "C" int64_t ymi_stem_wgrad_ws_bytes(const ymi_stem_wgrad_desc *d) {
   const int rc = validate_stem_wgrad(d);
   if (rc) return rc;
-  long per; int nchunks;
-  stem_wgrad_plan(d, per, nchunks);
-  return ymi_ws_part((int64_t)nchunks * SW_K * d->Cout);
+  return ymi_ws_part((int64_t)stem_wgrad_plan(d).nchunks * SW_K * d->Cout);
 }
 
 extern "C" int ymi_stem_wgrad_nhwc_f32(const ymi_stem_wgrad_desc *d, void *stream) {
@@ -271,8 +249,8 @@ extern "C" int ymi_stem_wgrad_nhwc_f32(const ymi_stem_wgrad_desc *d, void *strea
   SwParams p;
   p.x = d->x; p.g = d->g; p.dw = d->dw; p.ws = static_cast<float *>(d->ws);
   p.H = d->H; p.W = d->W; p.Ho = stem_out(d->H); p.Wo = stem_out(d->W); p.Cout = d->Cout; p.ldg = d->ldg;
-  p.P = stem_positions(d);
-  stem_wgrad_plan(d, p.per, p.nchunks);
+  const ymi_chunks c = stem_wgrad_plan(d);
+  p.P = stem_positions(d); p.per = c.per; p.nchunks = c.nchunks;
   int rl = ymi_launch(stem_wgrad_k, dim3(1, p.nchunks, (d->Cout + 63) / 64), dim3(256), 0, stream, p);
   if (!rl) rl = ymi_launch(stem_wgrad_sum_k, dim3((unsigned)(((long)SW_K * d->Cout + 255) / 256)), dim3(256), 0, stream, p);
   return rl;
