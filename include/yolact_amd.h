@@ -365,6 +365,60 @@ int ymi_boxes_to_pixels(const float *box, int64_t *out, int N, int w, int h, voi
 int ymi_fast_base_transform_f32(const float *img, float *out, int N, int H, int W, int oh, int ow,
                                 const float *mean_bgr, const float *std_bgr, int mode, int out_nhwc4, void *stream);
 
+/* -- SSDAugmentation (utils/augmentations.py:667-688; csrc/augment.hip; additive, the ABI number stays) --------------------------------
+ * The training transform's pixels for B images in two launches: one gather per output pixel of the S x S images, one per pixel of
+ * every KEPT ground-truth mask.  Every random decision was made on the host (yolact_amd.utils.augmentations.draw_augmentation) and
+ * arrives in one ymi_augment_rec per image; no canvas exists anywhere.  For output pixel (y, x):
+ *   1. cv2.resize's INTER_LINEAR sample coordinate in the cropped image (ch, cw) = (crop_y1 - crop_y0, crop_x1 - crop_x0):
+ *      f = (float)((x + 0.5) * ((double)cw / S) - 0.5), i = floor(f), f -= i; i < 0: i = 0, f = 0; i >= cw - 1: i = cw - 1, f = 0; the
+ *      second tap is min(i + 1, cw - 1).  Rows likewise.
+ *   2. each of the four taps: undo the mirror (cw - 1 - x), add the crop origin, subtract the expand offset.  Outside the source the
+ *      tap is the fill colour mean_bgr, NOT distorted; inside it is the source pixel as float through the photometric chain.
+ *   3. the chain, fp32, no clamping anywhere, a stage whose YMI_AUG_* bit is clear is SKIPPED: + delta; * alpha (unless
+ *      CONTRAST_LAST); with YMI_AUG_PHOTOMETRIC the BGR -> HSV -> BGR round trip of OpenCV's float cvtColor, always: V = max,
+ *      S = (V - min) / (|V| + FLT_EPSILON), H = (g - b | b - r | r - g) * (60 / (V - min + FLT_EPSILON)) + 0 | 120 | 240 by the
+ *      channel that is the max (r first, then g), + 360 if negative; S *= sat; H += hue, then - 360 if above 360, then + 360 if below 0;
+ *      back: h = H * (6 / 360), wrapped once into [0, 6), sector = floor(h), f = h - sector (a sector outside 0..5: sector 0, f 0),
+ *      tab = {V, V(1 - S), V(1 - S f), V(1 - S(1 - f))}, (b, g, r) = tab[{1,3,0} | {1,0,2} | {3,0,1} | {0,2,1} | {0,1,3} | {2,1,0}];
+ *      * alpha (with CONTRAST_LAST).
+ *   4. bilinear in fp32, the horizontal pair first: (t00 (1 - fx) + t01 fx) (1 - fy) + (t10 (1 - fx) + t11 fx) fy; then mode (as
+ *      ymi_fast_base_transform_f32: 0 (t - mean) / std, 1 t - mean, 2 t / 255, 3 none), BGR -> RGB, and out_nhwc4 as there:
+ *      out [B,3,S,S], or [B,S,S,4] RGB0 (16-byte aligned: one store per pixel).  Image b of the table goes to slot out_slot.
+ *   Masks: the same geometry, taps outside the source are 0, interpolated in integers as cv2's 8-bit path does: ax1 = rint(2048 fx),
+ *   ax0 = 2048 - ax1, ay likewise, (ay0 (ax0 m00 + ax1 m01) + ay1 (ax0 m10 + ax1 m11) + 2^21) >> 22.  Output mask mask_first + j of
+ *   image b is its instance kept[kept_first + j]; masks_out is [n_masks,S,S] float32, or uint8 with masks_u8.  Instances that are not
+ *   listed are never read.
+ * The table (records, one (image, instance) pair per output mask, each image's two resize scales as doubles, divided on the host: the
+ * same IEEE quotient a pixel would compute) reaches the device in ONE copy into ws, enqueued on `stream`
+ * from pageable host memory, so the caller's host arrays may be reused when the call returns.  No atomics; every output element is
+ * written exactly once; the same inputs give the same bits.
+ * YMI_ENULL: the descriptor, recs, out, ws, a record's src, kept / masks_out with n_masks > 0, a record's masks with n_kept > 0;
+ * YMI_EARG: B, S < 1, n_masks < 0, mode outside 0..3, a source or canvas size < 1, an empty crop; YMI_ESHAPE: the expand offset
+ * puts the source outside the canvas, the crop leaves the canvas, an instance index outside [0, n_inst), out_slot outside [0, B) or
+ * used twice, the images' mask ranges not tiling [0, n_masks) exactly, ws_bytes too small, ws not 16-byte aligned, out not 16-byte aligned with out_nhwc4, S * S >= 2^31.  No error path launches or copies anything. */
+enum { YMI_AUG_PHOTOMETRIC = 1, YMI_AUG_BRIGHTNESS = 2, YMI_AUG_CONTRAST = 4, YMI_AUG_CONTRAST_LAST = 8, YMI_AUG_SATURATION = 16,
+       YMI_AUG_HUE = 32, YMI_AUG_MIRROR = 64, YMI_AUG_SRC_F32 = 128 };
+typedef struct ymi_augment_rec {
+  const void *src;              /* [h,w,3] BGR on the device: uint8, or float32 with YMI_AUG_SRC_F32 */
+  const uint8_t *masks;         /* [n_inst,h,w] uint8 on the device (may be NULL when n_kept == 0) */
+  int32_t h, w, n_inst, flags;  /* flags: YMI_AUG_* */
+  int32_t canvas_h, canvas_w, off_x, off_y;          /* Expand's canvas and the source's corner in it (h, w, 0, 0 without one) */
+  int32_t crop_x0, crop_y0, crop_x1, crop_y1;        /* RandomSampleCrop's rect in the canvas (0, 0, canvas_w, canvas_h without one) */
+  float delta, alpha, sat, hue;
+  int32_t out_slot, mask_first, n_kept, kept_first;  /* kept_first: this image's first entry of ymi_augment_desc.kept */
+} ymi_augment_rec;
+typedef struct ymi_augment_desc {
+  const ymi_augment_rec *recs;  /* HOST [B] */
+  const int32_t *kept;          /* HOST: the instance indices of every image's kept masks */
+  float *out;                   /* [B,3,S,S] | [B,S,S,4] */
+  void *masks_out;              /* [n_masks,S,S] float32 | uint8 */
+  void *ws;                     /* DEVICE, ymi_workspace_bytes(YMI_WS_AUGMENT, desc) bytes, 16-byte aligned */
+  int64_t ws_bytes;
+  int32_t B, S, n_masks, mode, out_nhwc4, masks_u8;
+  float mean_bgr[3], std_bgr[3];   /* the fill colour is mean_bgr in every mode */
+} ymi_augment_desc;
+int ymi_ssd_augment_f32(const ymi_augment_desc *d, void *stream);
+
 /* -- mask_iou (layers/box_utils.py:98-113; consumer: eval.py:376-384,435-440 prep_metrics) --------------------------
  * masks_a [A,n], masks_b [B,n] float32 (n = h*w) -> iou [A,B] = inter / (area_a + area_b - inter), or inter / area_a when
  * iscrowd.  ws: caller-allocated workspace of A*B + A + B floats.  Exact for 0/1 masks (integer partial sums). */
@@ -1071,7 +1125,9 @@ enum {
                                  * Cout floats, each part padded to 16 */
   YMI_WS_BN = 25,               /* desc: ymi_bn_desc, npos / C read -> its ws: 2 * chunks * C + 2 * C floats, chunks = ceil(npos / max(32,
                                  * ceil(npos / 1024))), each part padded to 16 */
-  YMI_WS_STEM_WGRAD = 26        /* desc: ymi_stem_wgrad_desc, the shape read -> its ws: chunks * 147 * Cout floats, padded to 16 */
+  YMI_WS_STEM_WGRAD = 26,       /* desc: ymi_stem_wgrad_desc, the shape read -> its ws: chunks * 147 * Cout floats, padded to 16 */
+  YMI_WS_AUGMENT = 27           /* desc: ymi_augment_desc, B / n_masks read -> its ws: B records, n_masks (image, instance) pairs and B
+                                 * pairs of resize scales, B * sizeof(ymi_augment_rec) + 8 n_masks + 16 B bytes, each part padded to 16 */
 };
 typedef struct { int32_t A, B; int64_t n; } ymi_mask_iou_shape;
 typedef struct { int32_t N, h, w, cap; } ymi_rle_shape;      /* cap <= 0: the safe capacity h*w + 1 */

@@ -202,6 +202,29 @@ class StemWgradDesc(C.Structure):
                 ('B', C.c_int32), ('H', C.c_int32), ('W', C.c_int32), ('Cout', C.c_int32), ('ldg', C.c_int32), ('_pad0', C.c_int32)]
 
 
+# ymi_augment_rec.flags (include/yolact_amd.h YMI_AUG_*)
+AUG_PHOTOMETRIC, AUG_BRIGHTNESS, AUG_CONTRAST, AUG_CONTRAST_LAST, AUG_SATURATION, AUG_HUE, AUG_MIRROR, AUG_SRC_F32 = (
+    1, 2, 4, 8, 16, 32, 64, 128)
+
+
+class AugmentRec(C.Structure):
+    """include/yolact_amd.h ymi_augment_rec."""
+    _fields_ = [('src', C.c_void_p), ('masks', C.c_void_p),
+                ('h', C.c_int32), ('w', C.c_int32), ('n_inst', C.c_int32), ('flags', C.c_int32),
+                ('canvas_h', C.c_int32), ('canvas_w', C.c_int32), ('off_x', C.c_int32), ('off_y', C.c_int32),
+                ('crop_x0', C.c_int32), ('crop_y0', C.c_int32), ('crop_x1', C.c_int32), ('crop_y1', C.c_int32),
+                ('delta', C.c_float), ('alpha', C.c_float), ('sat', C.c_float), ('hue', C.c_float),
+                ('out_slot', C.c_int32), ('mask_first', C.c_int32), ('n_kept', C.c_int32), ('kept_first', C.c_int32)]
+
+
+class AugmentDesc(C.Structure):
+    """include/yolact_amd.h ymi_augment_desc."""
+    _fields_ = [('recs', C.POINTER(AugmentRec)), ('kept', C.c_void_p), ('out', C.c_void_p), ('masks_out', C.c_void_p),
+                ('ws', C.c_void_p), ('ws_bytes', C.c_int64),
+                ('B', C.c_int32), ('S', C.c_int32), ('n_masks', C.c_int32), ('mode', C.c_int32), ('out_nhwc4', C.c_int32),
+                ('masks_u8', C.c_int32), ('mean_bgr', C.c_float * 3), ('std_bgr', C.c_float * 3)]
+
+
 class DetectDesc(C.Structure):
     _fields_ = [('conf', C.c_void_p), ('loc', C.c_void_p), ('coef', C.c_void_p), ('priors', C.c_void_p),
                 ('B', C.c_int32), ('P', C.c_int32), ('C', C.c_int32), ('D', C.c_int32),
@@ -297,7 +320,7 @@ class RleShape(C.Structure):
 (WS_WINO_V, WS_WINO_M, WS_SPLITK, WS_MASK_IOU, WS_JPEG_COEFS, WS_JPEG_PLANES, WS_DETECT_SCORES_T, WS_DETECT_PER_PRIOR,
  WS_DETECT_CAND, WS_DETECT_REC, WS_AMAX_SLOT, WS_RLE_COUNTS, WS_DETECT_GREEDY, WS_JPEG_ENC, WS_JPEG_ENC_OUT,
  WS_MASK_LOSS, WS_MATCH, WS_BOX_LOSS, WS_CLASS_LOSS, WS_SEGM_LOSS, WS_MASKIOU_INPUT, WS_CONV_BWD, WS_MASKIOU_HEAD,
- WS_CONV_WGRAD, WS_BN, WS_STEM_WGRAD) = range(1, 27)
+ WS_CONV_WGRAD, WS_BN, WS_STEM_WGRAD, WS_AUGMENT) = range(1, 28)
 
 EFORMAT, EUNSUPPORTED = -4, -5
 UP_FLAT, UP_BAND, UP_ROWS16, UP_ROWS32 = 1, 2, 3, 4       # ymi_mask_upsample_kernel (include/yolact_amd.h YMI_UP_*)
@@ -366,6 +389,7 @@ SYMBOLS = [
     ('ymi_mask_rle_upsampled_f32', C.c_int, [_P, _I, _I, _I, _I, _I, _F, _P, _P, _I, _P]),
     ('ymi_rle_to_string', C.c_int, [_P, _P, _I, _I, _P, _P, _I, _P]),
     ('ymi_fast_base_transform_f32', C.c_int, [_P, _P, _I, _I, _I, _I, _I, C.POINTER(C.c_float), C.POINTER(C.c_float), _I, _I, _P]),
+    ('ymi_ssd_augment_f32', C.c_int, [C.POINTER(AugmentDesc), _P]),
     ('ymi_jpeg_parse', C.c_int, [_P, C.c_size_t, C.POINTER(JpegInfo)]),
     ('ymi_jpeg_decode_coefs', C.c_int, [_P, C.c_size_t, _P, C.c_int64, _P, C.POINTER(JpegInfo)]),
     ('ymi_jpeg_reconstruct_bgr_u8', C.c_int, [C.POINTER(JpegInfo), _P, _P, _P, _P, _P]),

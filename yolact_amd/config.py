@@ -1,9 +1,11 @@
-"""Configuration for the YOLACT inference hot path.
+"""Configuration for the YOLACT hot path.
 
-Only the fields that `Yolact.forward`, `Detect`, `postprocess` and `lincomb_mask_loss` READ
+Only the fields that `Yolact.forward`, `Detect`, `postprocess`, the loss terms and `SSDAugmentation` READ
 are modelled here (reference: data/config.py:61-100 `Config`, :417-648 `coco_base_config`,
-:656-806 shipped model configs, :810-825 `cfg`/`set_cfg`).  Training, dataset and
-augmentation fields are out of scope for this tier.
+:656-806 shipped model configs, :810-825 `cfg`/`set_cfg`).  The augmentation switches of
+data/config.py:489-503 are here with the reference's defaults (`augment_random_flip`, `use_gt_bboxes` and
+`preserve_aspect_ratio` are refused when set: no shipped config sets them); optimiser, schedule and
+dataset fields are out of scope for this tier.
 
 Two ways to get a config:
   * stand-alone: `set_cfg('yolact_resnet50_config')` on this module's global `cfg`;
@@ -91,6 +93,10 @@ _common = Cfg(
     # layers/modules/multibox_loss.py; data/config.py:442,468,517,528,545,574,599)
     conf_alpha=1, ohem_negpos_ratio=3, ohem_use_most_confident=False, use_class_balanced_conf=False,
     semantic_segmentation_alpha=1, mask_proto_loss=None, train_masks=True,
+    # the training transform (utils/augmentations.py SSDAugmentation; data/config.py:489-503,603,608)
+    augment_photometric_distort=True, augment_expand=True, augment_random_sample_crop=True, augment_random_mirror=True,
+    augment_random_flip=False, augment_random_rot90=False, discard_box_width=4 / 550, discard_box_height=4 / 550,
+    use_gt_bboxes=False, preserve_aspect_ratio=False,
 )
 
 _R50 = ([3, 4, 6, 3],)

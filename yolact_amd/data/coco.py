@@ -203,3 +203,14 @@ class COCODetection(torch.utils.data.Dataset):
 
     def __repr__(self):
         return '%s(%d images, root=%r, has_gt=%s)' % (type(self).__name__, len(self), self.root, self.has_gt)
+
+
+def detection_collate(batch):
+    """data/coco.py:260-284, the collate_fn of the reference's DataLoader: a list of `dataset[i]` = (image, (target, masks,
+    num_crowds)) -> (images, (targets, masks, num_crowds)), every part a list with one entry per item; targets and masks become
+    float32 tensors (the reference's torch.FloatTensor), an array on the host, a device tensor where it is."""
+    images = [item[0] for item in batch]
+    targets = [torch.as_tensor(item[1][0], dtype=torch.float32) for item in batch]
+    masks = [torch.as_tensor(item[1][1], dtype=torch.float32) for item in batch]
+    num_crowds = [item[1][2] for item in batch]
+    return images, (targets, masks, num_crowds)
