@@ -32,7 +32,6 @@ The largest errors sit on the K = 2304 prediction heads and the merged P3 launch
 on the K = 2304 / 4608 dense 3x3s; the edges (1x1 maps, ragged Cout and M, ragged split-K, ldx > Cin, a zero image between loud
 ones) stay below 1e-6.
 """
-import ast
 import collections
 import ctypes as C
 import json
@@ -46,6 +45,7 @@ import conv_ref as R
 pytestmark = pytest.mark.gpu
 
 from yolact_amd import _lib as L  # noqa: E402
+from yolact_amd import tune_table as TT  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BARS = R.BARS
@@ -102,13 +102,9 @@ def _shipped():
         entries = json.load(f)['entries']
     out = []
     for k, v in entries.items():
-        if not k.startswith('('):
-            continue
-        body, _, mode = k.partition('|')
-        key = ast.literal_eval(body)
-        if len(key) != 12:                                  # ('dcn'-tagged keys: tests/test_gpu_dcn_kat.py)
-            continue
-        out.append((key, mode, int(v)))
+        kind, key, mode = TT.parse(k)
+        if kind == 'conv':                                  # ('dcn'-tagged keys: tests/test_gpu_dcn_kat.py)
+            out.append((key, mode, int(v)))
     return sorted(out)
 
 

@@ -12,7 +12,6 @@ with batch 3 (a read across an image boundary changes the answer by O(|x|)), sam
 modulation, ragged row / column tiles, split-K 2 / 3 / 6 / 9 with ranges that start inside a tap, and every DCN launch the tune
 table ships (yolact_amd/tune/gfx950.json), rebuilt as the plan builds it.
 """
-import ast
 import json
 import os
 
@@ -24,6 +23,7 @@ from dcn_ref import const_offmask, dcn_ref, edge_offsets, fractional_taps, integ
 pytestmark = pytest.mark.gpu
 
 from yolact_amd import _lib as L  # noqa: E402
+from yolact_amd import tune_table as TT  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 RS_EXACT = sorted(L.BASIC_TILES)                                                   # register-staged loader, exact fp32
@@ -176,9 +176,9 @@ def _shipped():
         entries = json.load(f)['entries']
     out = []
     for k, v in sorted(entries.items()):
-        if k.endswith("'dcn')|h2"):
-            key = ast.literal_eval(k[:-len('|h2')])
-            out.append((key, v & 255, v >> 8))
+        kind, key, mode = TT.parse(k)
+        if kind == 'dcn' and mode == 'h2':
+            out.append((key,) + TT.direct_parts(v))
     return out
 
 

@@ -469,19 +469,17 @@ def test_pointwise_chain_matches_fp64(M, mode):
 
 def _shipped_chains():
     """(kind, B, H, W) of every 'chain' / 'chain1' entry of yolact_amd/tune/gfx950.json the plan installs (decision 1)."""
-    import ast
     import json
     import os
+    from yolact_amd import tune_table as TT
     path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'yolact_amd', 'tune', 'gfx950.json')
     with open(path) as f:
         entries = json.load(f)['entries']
     out = []
     for k, v in sorted(entries.items()):
-        kind, _, rest = k.partition('(')
-        if kind in ('chain', 'chain1') and v[0] == 1:
-            key = ast.literal_eval('(' + rest.partition('|')[0])
-            if len(key) == 3:                                 # (P = 64: csrc/chain.hip)
-                out.append((kind,) + key)
+        kind, key, _ = TT.parse(k)
+        if kind in ('chain', 'chain1') and v[0] == 1 and len(key) == 3:       # (P = 64: csrc/chain.hip)
+            out.append((kind,) + key)
     return out
 
 

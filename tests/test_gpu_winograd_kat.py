@@ -29,7 +29,6 @@ F(4x4) is an order of magnitude above F(2x2) on every family: the transform's co
 fp32=True, no accumulation error) is ~1.5e-6 on the same launches.  On the prediction heads the largest coefficient error is
 7.6e-5 absolute (exact-fp32 64x64 tile, F(4x4)), inside the 1e-4 absolute bar of tests/test_gpu_batch_parity.py.
 """
-import ast
 import json
 import os
 
@@ -41,6 +40,7 @@ import wino_ref as R
 pytestmark = pytest.mark.gpu
 
 from yolact_amd import _lib as L  # noqa: E402
+from yolact_amd import tune_table as TT  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # largest rel_err over this file on MI355X: F(2x2) 1.37e-6 / 9.4e-7 / 5.8e-7, F(4x4) 1.68e-5 / 1.70e-5 / 1.10e-5 (exact / x3 / h2)
@@ -97,11 +97,9 @@ def _shipped():
         entries = json.load(f)['entries']
     out = []
     for k, v in sorted(entries.items()):
-        if not k.startswith('wino(') or not v[0]:
-            continue
-        body, _, mode = k[len('wino'):].partition(')|')
-        key = ast.literal_eval(body + ')' if mode else body)
-        out.append((key, mode, int(v[0]), int(v[1]) & 255, 1 if int(v[1]) & L.WINO_PLANES else 0))
+        kind, key, mode = TT.parse(k)
+        if kind == 'wino' and v[0]:
+            out.append((key, mode, int(v[0])) + TT.wino_parts(v[1]))
     return out
 
 

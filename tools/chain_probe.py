@@ -77,7 +77,7 @@ def main():
         print('%-30s M=%d  %.4f ms  %6.1f MB  %.2f TB/s' % (name, M, best, nbytes / 1e6, nbytes / best / 1e9))
 
     # ---- the stage exit against the two launches it replaces
-    from yolact_amd.engine import load_tune_table
+    from yolact_amd import tune_table as TT
     B, H, W = args.batch, 138, 138
     wx = torch.randn(128, 256, 1, 1, generator=g) / 16
     px = Packed(wx, torch.randn(128, generator=g), None, 1, 0, None, dev)
@@ -94,8 +94,8 @@ def main():
         d.seg[0] = L.ConvSeg(0, 128, L.ACT_RELU, 128, H * W * 128, zs[k].data_ptr())
         d.x_amax, d.y_amax = amax.data_ptr() + 4096, amax.data_ptr() + 8192
         d.w_h2, d.scale_h2, d.winv_h2 = plx.data_ptr(), scx.data_ptr(), winvx.data_ptr()
-        val = load_tune_table(dev).get(str((B, H, W, 256, 128, 1, 1, 1, 0, 0, 1, 256)) + '|h2')
-        d.tile = (int(val) & 255) if val is not None else L.TILE_AUTO
+        val = TT.load_tune_table(dev).get(TT.conv_key((B, H, W, 256, 128, 1, 1, 1, 0, 0, 1, 256), 'h2'))
+        d.tile = TT.direct_parts(val)[0] if val is not None else L.TILE_AUTO
         return d
 
     def exit_desc(k, y_stride):
@@ -109,7 +109,7 @@ def main():
     c3 = [desc(k, False, True) for k in range(args.sets)]
     c1 = [conv1_desc(k) for k in range(args.sets)]
     arms = [('chain1 (conv3 + residual)', lambda k: lib.ymi_pointwise_chain_f32(C.byref(c3[k]), s), 4.0 * M * (64 + 256 + 256)),
-            ('layer1.0.conv1 (tile %d)' % (c1[0].tile & 255), lambda k: lib.ymi_conv2d_nhwc_f32(C.byref(c1[k]), s), 4.0 * M * (256 + 128)),
+            ('layer1.0.conv1 (tile %d)' % c1[0].tile, lambda k: lib.ymi_conv2d_nhwc_f32(C.byref(c1[k]), s), 4.0 * M * (256 + 128)),
             ('chain1, then conv1', lambda k: (lib.ymi_pointwise_chain_f32(C.byref(c3[k]), s), lib.ymi_conv2d_nhwc_f32(C.byref(c1[k]), s))[1],
              4.0 * M * (64 + 256 + 256 + 256 + 128))]
     for ys in (2, 1):

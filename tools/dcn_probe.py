@@ -29,7 +29,7 @@ def main():
     args = ap.parse_args()
     os.environ.setdefault('YOLACT_AMD_AUTOTUNE', 'table')
     import yolact_amd
-    from yolact_amd import _lib as L
+    from yolact_amd import _lib as L, tune_table as TT
     from yolact_amd.utils.synth import synth_images, synth_state_dict
     yolact_amd.set_cfg(args.config)
     from yolact_amd.yolact import Yolact
@@ -49,8 +49,7 @@ def main():
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     old = [t for t in L.BASIC_TILES if t != L.TILE_128x32]
     old = old + [t | L.TILE_H2 for t in old]
-    def tname(v):
-        return L.TILE_NAMES[v & 255] + ('/k%d' % (v >> 8) if v >> 8 else '')
+    tname = TT.choice_name
     if args.tiles:
         old = [L.TILE_64x64 | L.TILE_H2]
     abls = [int(a) for a in args.ablate.split(',')] if args.ablate else []
@@ -61,7 +60,7 @@ def main():
         dd = dptr.contents
         d = dd.conv
         fl = lib.ymi_conv_flops(C.byref(d))
-        tile0 = d.tile + 256 * max(d.split_k, 0) * (1 if d.split_k > 1 else 0)
+        tile0 = TT.direct_choice(d.tile, d.split_k)
         M = d.B * d.Ho * d.Wo
         y = torch.empty(M * d.Cout, device=dev)
         yptr0 = d.seg[0].ptr
@@ -76,7 +75,7 @@ def main():
             torch.cuda.synchronize()
             if t == (L.TILE_64x64 | L.TILE_H2):
                 ref = y.clone()
-            elif (t & 255) & L.TILE_DCNP and ref is not None:
+            elif TT.direct_parts(t)[0] & L.TILE_DCNP and ref is not None:
                 dev_max[t] = ((y - ref).abs().max() / ref.abs().max()).item()
             best = 1e30
             for _ in range(2):
@@ -87,7 +86,7 @@ def main():
                 e1.synchronize()
                 best = min(best, e0.elapsed_time(e1) / args.reps)
             times[t] = best
-            if (t & 255) & L.TILE_DCNP and abls:
+            if TT.direct_parts(t)[0] & L.TILE_DCNP and abls:
                 row = []
                 for a in abls:
                     os.environ['YMI_DCN_ABLATE'] = str(a)

@@ -34,7 +34,7 @@ def main():
     args = ap.parse_args()
     import torch
     import yolact_amd
-    from yolact_amd import engine
+    from yolact_amd import tune_table as TT
     from yolact_amd.utils.synth import synth_images, synth_state_dict
     yolact_amd.set_cfg(args.config)
     from yolact_amd.yolact import Yolact
@@ -76,7 +76,7 @@ def main():
                 net.forward_device(x)['count'].tolist()
             torch.cuda.synchronize()
             return (time.perf_counter() - t0) / n * 1e3
-        table = engine.load_tune_table(dev)
+        table = TT.load_tune_table(dev)
         out = {}
         base = statistics.median(step_ms(args.steps) for _ in range(3))
         print('plan: %s batch %d, %d tune misses, step %.3f ms' % (args.config, args.batch, plan.tune_misses, base), flush=True)
@@ -86,7 +86,7 @@ def main():
                 continue
             ratio = ent[3] / ent[2] if ent[2] else 0.0
             names = [e[1][2] for e in lst]
-            uses_wino = all(e[3] for e in lst) and table.get('instep|' + key) != 0
+            uses_wino = all(e[3] for e in lst) and table.get(TT.instep_key(key)) != 0
             if not uses_wino or ratio < args.max_margin:
                 print('skip %-60s isolated wino/direct %.2f  (%d layers: %s)' % (key[:60], ratio, len(lst), ','.join(names)[:80]))
                 continue
@@ -111,12 +111,12 @@ def main():
         print('step after the decisions: %.3f ms (was %.3f)' % (final, base))
     print(json.dumps({'config': args.config, 'batch': args.batch, 'overlap': args.overlap, 'base_ms': round(base, 4), 'final_ms': round(final, 4), 'keys': out}))
     if args.write and any(v['direct_wins_the_step'] for v in out.values()):
-        path = os.path.join(engine.TUNE_DIR, 'gfx950.json')
-        entries = engine._read_table_file(path)
+        path = os.path.join(TT.TUNE_DIR, 'gfx950.json')
+        entries = TT.read_table_file(path)
         for k, v in out.items():
             if v['direct_wins_the_step']:
-                entries['instep|' + k] = 0
-        engine._write_table_file(path, entries, dev)
+                entries[TT.instep_key(k)] = 0
+        TT.write_table_file(path, entries, dev)
         print('wrote %d instep decisions to %s' % (sum(v['direct_wins_the_step'] for v in out.values()), path))
 
 

@@ -9,7 +9,7 @@ is measured once and every plan that contains it runs the same tile (bit-identic
 layers).  The default plan of the product then reads the table and measures nothing: deterministic across processes and
 boxes (tests/test_gpu_batch_parity.py::test_plan_is_deterministic_across_processes).
 
-Re-run after any change to the conv kernels or tile ids (bump engine.TUNE_GEN so that old tables are ignored)."""
+Re-run after any change to the conv kernels or tile ids (bump tune_table.TUNE_GEN so that old tables are ignored)."""
 import argparse
 import json
 import os
@@ -56,14 +56,14 @@ def main():
     os.environ['YOLACT_AMD_AUTOTUNE'] = '1'
     import torch
     import yolact_amd
-    from yolact_amd import engine
+    from yolact_amd import tune_table
     from yolact_amd.utils.synth import synth_images, synth_state_dict
     dev = torch.device('cuda', 0)
     log = []
     for name, config, B, size in PLANS:
         if args.only and name not in args.only:
             continue
-        engine._table_cache.clear()                          # the shipped table may be the very file being extended
+        tune_table._table_cache.clear()                          # the shipped table may be the very file being extended
         yolact_amd.set_cfg(config)
         from yolact_amd.yolact import Yolact
         net = Yolact()
@@ -82,7 +82,7 @@ def main():
         print(log[-1], flush=True)
         del net, plan, x
         torch.cuda.empty_cache()
-    n = len(engine._read_table_file(args.out))
+    n = len(tune_table.read_table_file(args.out))
     print('table %s: %d entries' % (args.out, n))
     if args.copy_to:
         os.makedirs(os.path.dirname(args.copy_to), exist_ok=True)

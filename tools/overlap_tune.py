@@ -38,7 +38,7 @@ def main():
     args = ap.parse_args()
     import torch
     import yolact_amd
-    from yolact_amd import engine, _lib as L
+    from yolact_amd import _lib as L, tune_table as TT
     from yolact_amd.pipeline import BatchPipeline
     from yolact_amd.utils.synth import synth_images, synth_state_dict
     yolact_amd.set_cfg(args.config)
@@ -70,8 +70,7 @@ def main():
             pipe.synchronize()
             return (time.perf_counter() - t0) / n * 1e3
 
-        def cname(v):
-            return L.TILE_NAMES.get(v & 255, '?%d' % (v & 255)) + ('/k%d' % (v >> 8) if v >> 8 else '')
+        cname = TT.choice_name
 
         # the direct convolution launches of slot 0's plan, grouped by table key; the same op index in every slot
         groups = {}
@@ -81,14 +80,12 @@ def main():
             if (fn is not lib.ymi_conv2d_nhwc_f32 and not is_dcn) or opi in p0.wide_ops:
                 continue
             d = dptr.contents.conv if is_dcn else dptr.contents
-            key = (d.B, d.H, d.W, d.Cin, d.Cout, d.kh, d.kw, d.stride, d.pad, d.res_mode, d.nseg, d.Kpad) + (('dcn',) if is_dcn else ())
-            skey = str(key) + ('|x3' if p0.split else '|h2' if p0.h2 else '')
-            groups.setdefault(skey, []).append(opi)
+            groups.setdefault(p0.direct_key(fn, d), []).append(opi)
 
         def cur_val(opi):
             fn, dptr, _, _ = p0.ops[opi]
             d = dptr.contents.conv if fn is lib.ymi_dcn_v2_forward_f32 else dptr.contents
-            return int(d.tile) + 256 * (int(d.split_k) if d.split_k > 1 else 0)
+            return TT.direct_choice(d.tile, d.split_k)
 
         def install(opis, val):
             for p_ in plans:
@@ -160,11 +157,11 @@ def main():
                       'keys': {k: v[0] for k, v in out.items()}}))
     changed = {k: v[1] for k, v in out.items() if v[1] != v[2]}
     if args.write and changed:
-        path = os.path.join(engine.TUNE_DIR, 'gfx950.json')
-        entries = engine._read_table_file(path)
+        path = os.path.join(TT.TUNE_DIR, 'gfx950.json')
+        entries = TT.read_table_file(path)
         for k, v in changed.items():
             entries[k] = int(v)
-        engine._write_table_file(path, entries, dev)
+        TT.write_table_file(path, entries, dev)
         print('wrote %d entries to %s' % (len(changed), path))
 
 

@@ -30,7 +30,7 @@ def main():
     ap.add_argument('--plan-only', action='store_true', help='time the plan\'s own op of every eligible layer and nothing else (A/B of a rebuilt library)')
     args = ap.parse_args()
     import yolact_amd
-    from yolact_amd import _lib as L
+    from yolact_amd import _lib as L, tune_table as TT
     from yolact_amd.utils.synth import synth_images, synth_state_dict
     yolact_amd.set_cfg(args.config)
     from yolact_amd.yolact import Yolact
@@ -61,8 +61,7 @@ def main():
             best = min(best, e0.elapsed_time(e1) / args.reps)
         return best
 
-    def tname(v):
-        return L.TILE_NAMES[v & 255] + ('/k%d' % (v >> 8) if v >> 8 else '')
+    tname = TT.choice_name
     descs = dict(plan.conv_meta)
     tot_plan = tot_best = tot_fl = 0.0
     for fn, arg, name, where in plan.ops:
@@ -102,7 +101,7 @@ def main():
         for cand in plan.dcnp_candidates(d) + (plan.ws_candidates(d) if not args.no_ws else []) + plan.pc_candidates(d) + plan.patch2_candidates(d):
             if args.tiles and tname(cand) not in args.tiles.split(','):
                 continue
-            tile, S = cand & 255, cand >> 8
+            tile, S = TT.direct_parts(cand)
             d.tile = tile
             d.split_k = S if S > 1 else 0
             if S > 1:
@@ -122,7 +121,7 @@ def main():
             base, d.B, d.H, d.W, d.stride, d.kh, d.Cin, d.Cout, fl / 1e9, name[-34:], t_plan, fl / t_plan / 1e9, tname(best), times[best],
             fl / times[best] / 1e9, t_plan / times[best], devmax.get(best, float('nan'))), flush=True)
         if args.ablate:
-            tile, S = best & 255, best >> 8
+            tile, S = TT.direct_parts(best)
             d.tile, d.split_k = tile, (S if S > 1 else 0)
             if S > 1:
                 d.split_ws = plan._splitk_ws(where, S * M * d.Cout).data_ptr()

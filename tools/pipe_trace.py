@@ -61,7 +61,7 @@ def main():
         d = arg.contents
         tile = d.tile
         if not (tile & L.TILE_DCNP):
-            print('%s: tile %s is not a pipelined tile, skipped' % (name, L.TILE_NAMES.get(tile & 255, tile)))
+            print('%s: tile %s is not a pipelined tile, skipped' % (name, L.TILE_NAMES.get(tile, tile)))
             continue
         os.environ.pop('YMI_PIPE_TRACE', None)
         fn(arg, s)
@@ -84,7 +84,7 @@ def main():
         M = d.B * d.Ho * d.Wo
         fl = 2.0 * M * d.Cout * d.kh * d.kw * d.Cin
         print('\n%s  B%d %dx%d k%d %d>%d  tile %s  %d blocks  untraced launch %.1f us (%.0f TF/s algorithmic)' % (
-            name, d.B, d.H, d.W, d.kh, d.Cin, d.Cout, L.TILE_NAMES.get(tile & 255, tile),
+            name, d.B, d.H, d.W, d.kh, d.Cin, d.Cout, L.TILE_NAMES.get(tile, tile),
             nblk, best * 1e3, fl / best / 1e9))
         t = tr[-1, :nblk].double()                       # the last repetition (steady state: filters / activations cache-warm as in a step)
         cyc = (t[:, 9] - t[:, 0])

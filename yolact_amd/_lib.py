@@ -61,6 +61,7 @@ for _t, _n in list(DCNP_TILES.items()) + list(WS_TILES.items()) + list(PATCH_TIL
     TILE_NAMES[_t | TILE_H2 | TILE_DCNP] = _n
 WINO_PLANES = 1024                  # tune-table flag on a Winograd GEMM tile id: V written as fp16x2 planes (ymi_wino_desc.v_planes)
 KSPLIT_TILES = (6, 7, 8, 13, 14, 15, 6 | 32, 7 | 32, 8 | 32, 6 | 64, 7 | 64, 8 | 64, 13 | 64, 14 | 64, 15 | 64)   # different (still deterministic) fp32 summation order than the unsplit tiles
+AMAX_SLOT_FLOATS = 16 * 64          # one magnitude-bound slot: YMI_AMAX_SUB sub-slots, YMI_AMAX_STRIDE floats apart (include/yolact_amd.h)
 
 
 class ConvSeg(C.Structure):

@@ -85,7 +85,7 @@ def _fill_desc(d, xd, pk, y, Ho, Wo, amax, h2):
 
 def _input_bound(xd):
     """A magnitude-bound slot (ymi_conv_desc.x_amax) raised to max|x| by ymi_amax_f32."""
-    from .engine import AMAX_SLOT_FLOATS
+    from ._lib import AMAX_SLOT_FLOATS
     amax = torch.zeros(AMAX_SLOT_FLOATS, dtype=torch.float32, device=xd.device)
     L.check(L.lib().ymi_amax_f32(xd.data_ptr(), xd.numel(), amax.data_ptr(), L.stream_ptr()), 'ymi_amax_f32')
     return amax
