@@ -101,9 +101,10 @@ def chain_ref(x, P, blocks, batch_stats, keep=None, new_stats=None, **kw):
     return outs
 
 
-def run_ref(x, params, blocks, up, batch_stats, dtype, keep=None, **kw):
+def run_ref(x, params, blocks, up, batch_stats, dtype, keep=None, ups=None, **kw):
     """Forward of the chain and the gradients of <last output, up> -> dict('y' -> output, 'd_x', 'd_<name>' per parameter that takes a
-    gradient, 'new_<name>' per running statistic)."""
+    gradient, 'new_<name>' per running statistic).  ups (one upstream gradient per block output, `up` is then None): the gradients of
+    sum_i <output i, ups[i]>, every block output with two consumers but the last, and 'out<i>' per block in place of 'y'."""
     leaf = x.detach().to(dtype).requires_grad_(True)
     names = [n for n in params if is_leaf_name(n)]
     P = {n: params[n].detach().to(dtype) for n in params}
@@ -112,23 +113,28 @@ def run_ref(x, params, blocks, up, batch_stats, dtype, keep=None, **kw):
     new_stats = {}
     with helpers.oracle_threads():                       # torch's CPU summation order depends on the thread count
         outs = chain_ref(leaf, P, blocks, batch_stats, keep, new_stats, **kw)
-        total = (outs[-1] * up.to(dtype)).sum()
+        if ups is None:
+            total = (outs[-1] * up.to(dtype)).sum()
+        else:
+            assert up is None and len(ups) == len(outs)
+            total = sum((o * u.to(dtype)).sum() for o, u in zip(outs, ups))
         g = torch.autograd.grad(total, [leaf] + [P[n] for n in names], retain_graph=keep is not None)
-    res = {'y': outs[-1].detach(), 'd_x': g[0]}
+    res = {'y': outs[-1].detach()} if ups is None else {'out%d' % i: o.detach() for i, o in enumerate(outs)}
+    res['d_x'] = g[0]
     res.update({'d_' + n: t for n, t in zip(names, g[1:])})
     res.update({'new_' + n: t.detach() for n, t in new_stats.items()})
     res['_total'], res['_outs'] = total, outs
     return res
 
 
-def relu_margins(x, params, blocks, up, batch_stats):
+def relu_margins(x, params, blocks, up, batch_stats, ups=None):
     """Per ReLU: (name, the smallest |pre-activation| whose activation receives gradient, in fp64; the largest fp32-versus-fp64
     deviation of that tensor)."""
     res = {}
     with helpers.oracle_threads():
         for dtype in (torch.float64, torch.float32):
             keep = []
-            r = run_ref(x, params, blocks, up, batch_stats, dtype, keep)
+            r = run_ref(x, params, blocks, up, batch_stats, dtype, keep, ups=ups)
             ga = torch.autograd.grad(r['_total'], [a for _, _, a in keep], allow_unused=True)
             res[dtype] = [(n, z.detach(), torch.zeros_like(a) if g is None else g) for (n, z, a), g in zip(keep, ga)]
     out = []
@@ -178,11 +184,12 @@ def random_case(seed, xshape, specs):
     return x, params, blocks, up
 
 
-def find_seed(xshape, specs, modes=(False, True), first=1, last=200, factor=16):
-    """The first seed whose case keeps `factor` times the fp32 deviation at every ReLU in every mode -> (seed, tried)."""
+def find_seed(xshape, specs, modes=(False, True), first=1, last=200, factor=16, ups=None):
+    """The first seed whose case keeps `factor` times the fp32 deviation at every ReLU in every mode -> (seed, tried).  ups: as in
+    run_ref, the same for every seed (the case's own `up` is then not used)."""
     for seed in range(first, last + 1):
         x, params, blocks, up = random_case(seed, xshape, specs)
-        if all(all(lo >= factor * dev for _, lo, dev in relu_margins(x, params, blocks, up, m)) for m in modes):
+        if all(all(lo >= factor * dev for _, lo, dev in relu_margins(x, params, blocks, None if ups else up, m, ups)) for m in modes):
             return seed, seed - first + 1
     raise AssertionError('no seed in %d .. %d keeps the margin' % (first, last))
 

@@ -87,6 +87,26 @@ def test_margins_of_the_golden_case():
         assert max(rel_err(r32[k], r64[k]) for k in WANT[name]) <= 1e-6
 
 
+def test_an_upstream_gradient_per_block_output():
+    """run_ref's ups: with zeros everywhere but at the last output it is the single-up result; a gradient at the first block's output
+    as well adds exactly the gradient of that term (the total is linear in the ups), and changes d_x."""
+    first = R.out_shape(tuple(X.shape), [tuple(s) for s in META['specs']][:1])
+    up0 = torch.randint(-2, 3, first, generator=torch.Generator().manual_seed(1)).float() / 2
+    one = R.run_ref(X, PARAMS, BLOCKS, UP, False, torch.float64)
+    last = R.run_ref(X, PARAMS, BLOCKS, None, False, torch.float64, ups=[torch.zeros(first), UP])
+    assert sorted(last) == sorted([k for k in one if k != 'y'] + ['out0', 'out1']) and torch.equal(last['out1'], one['y'])
+    only0 = R.run_ref(X, PARAMS, BLOCKS, None, False, torch.float64, ups=[up0, torch.zeros_like(UP)])
+    both = R.run_ref(X, PARAMS, BLOCKS, None, False, torch.float64, ups=[up0, UP])
+    for k in one:
+        if k.startswith('d_'):
+            assert rel_err(last[k], one[k]) <= 1e-12, k
+            assert rel_err(both[k], one[k] + only0[k]) <= 1e-12, k
+    assert rel_err(both['d_x'], one['d_x']) > 1e-3
+    assert not bool(only0['d_1.conv1.weight'].ne(0).any()) and bool(only0['d_0.conv1.weight'].ne(0).any())
+    m = R.relu_margins(X, PARAMS, BLOCKS, None, False, ups=[up0, UP])
+    assert len(m) == 6 and all(lo < float('inf') for _, lo, _ in m)
+
+
 def bn_desc(**kw):
     d = L.BnDesc()
     d.npos, d.C, d.training, d.relu, d.eps, d.momentum = 70, 32, 1, 0, 1e-5, 0.1

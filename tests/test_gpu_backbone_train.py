@@ -9,6 +9,21 @@ a ReLU first asserts on the oracle that the smallest |pre-activation| that recei
 fp32-versus-fp64 deviation of that tensor; the seeds below were chosen on the CPU so that this holds (the golden's is in its meta).
 Every case runs twice on the same inputs and must give the same bits.  Where an entry is called directly its outputs go into NaN-filled
 buffers with a NaN guard band behind them.
+
+The real widths.  The whole real backbone's gradients cannot be compared with fp64: among its several hundred thousand ReLU elements
+some pre-activation sits inside the fp32 deviation for every seed.  So every distinct piece is pinned on its own, on the smallest map on
+which all of its paths still run:
+  DG_WIDE      ymi_conv_dgrad_s2_nhwc_f32 at 3x3 512 -> 512 and 1x1 1024 -> 2048 on 5 x 4 (8 and 16 blocks of 64 input channels,
+               Cout / 8 = 64 and 256 steps per tap, the masked last odd column), and at Cin = 160: the half block behind full ones
+  BN_SHAPES    C = 2048, 1024, 512 at npos = 18 (below one chunk), 40 (a chunk and a ragged one) and 2 (the smallest training takes)
+  conv2d_plain 3x3 512 -> 512 and 1x1 2048 -> 512: the stride-1 data gradient on the engine at K = 4608 and 2048
+  REAL_SPECS   the seven bottlenecks of ResNet-50 / 101 beside 'entry', planes 64 .. 512, on [2, inplanes, 5, 4]: behind a stride the
+               map is 3 x 2, 12 positions for the batch statistics; wgrad_k<4, 1> and wgrad_k<4, 2> with gz up to 4
+  the seam     train_net.backbone itself on four one-block stages whose outputs ALL take a gradient of their own: each map's gradient
+               is the sum of two consumers', added at the view_as alias; every other compared case has one consumer per map
+The stride-2 and stride-1 weight gradients alone at these widths are in tests/test_gpu_fpn_train.py and tests/test_gpu_heads_train.py.
+Each wide data-gradient and weight-gradient case also shows that it can fail: against an fp64 oracle that drops one block of 32 output
+channels of g the GPU result misses the bar.
 """
 import ctypes as C
 import functools
@@ -37,16 +52,42 @@ pytestmark = pytest.mark.gpu
 # (kernel, B, H, W, Cin, Cout): odd extents with every window at a border; even extents (the masked last row and column); 1x1 on odd
 # and on even extents; 2 * 37 * 41 pixels: many tiles with a ragged last one in every phase
 DG_SHAPES = [(3, 2, 5, 7, 32, 32), (3, 1, 8, 6, 64, 96), (1, 2, 7, 9, 64, 32), (1, 1, 8, 6, 32, 64), (3, 2, 37, 41, 96, 32)]
+# the widths of the real stages on a 5 x 4 map (odd H, even W: the last odd column has a masked tap, every pixel at a border; 2 or 6
+# pixels per phase, so three waves of every block leave at once): stage 3's conv2 (8 channel blocks of 64, Cout / 8 = 64 steps per tap),
+# stage 4's projection (16 channel blocks, 256 steps, three phases of exact zeros); Cin = 160 = 2.5 blocks: a half block (one row tile
+# live) BEHIND two full ones.  On the exact grids the largest |sum| is 2048 * 32 units of 1/32, below 2^24.
+DG_WIDE = [(3, 2, 5, 4, 512, 512), (1, 2, 5, 4, 1024, 2048), (3, 1, 4, 5, 160, 128)]
+DG_SHAPES += DG_WIDE
+DG_RANDOM = [DG_SHAPES[4]] + DG_WIDE                      # also run on N(0, 1) values against the fp64 oracle, under the bar
 BN_SHAPES = [(2, 32), (70, 32), (70, 256), (3034, 64)]
+# channel counts past 256 (bn_delta_k / bn_fin_k: 512 blocks of 4 waves; the chunk kernels: several blocks per chunk) at the position
+# counts of a 3 x 3 map (18: below one chunk of 32), of a 5 x 4 one (40: a full chunk and a ragged one of 8) and at the smallest npos
+# the training mode takes
+BN_SHAPES += [(18, 2048), (40, 1024), (2, 512)]
 # the ReLU cases' seeds, per (npos, C, training, residual): the first seed of 1 .. 40 with 64 times the deviation as margin, or the widest
 # of them (chosen on the CPU, bn_find_seed; the test asserts 16 times)
 BN_SEEDS = {(npos, Cc, training, residual): 1 for npos, Cc in BN_SHAPES for training in (True, False) for residual in (False, True)}
 BN_SEEDS.update({(70, 32, True, False): 2, (70, 256, True, False): 2, (70, 256, True, True): 2, (3034, 64, True, False): 4,
-                 (3034, 64, True, True): 39, (3034, 64, False, True): 3})
+                 (3034, 64, True, True): 39, (3034, 64, False, True): 3, (18, 2048, True, False): 5, (18, 2048, False, False): 2,
+                 (40, 1024, True, False): 5, (40, 1024, True, True): 2, (40, 1024, False, False): 6})
 # (inplanes, planes, stride, projection): identity; stride 1 with a projection; stride 2 with a projection; a layers[0]-style entry
 BLOCK_SPECS = {'identity': (128, 32, 1, False), 'proj_s1': (64, 32, 1, True), 'proj_s2': (64, 32, 2, True), 'entry': (64, 64, 1, True)}
 BLOCK_SEEDS = {(v, bs): 1 for v in BLOCK_SPECS for bs in (False, True)}      # chosen likewise (at least 77 times)
 BLOCK_SEEDS.update({('identity', True): 5, ('proj_s1', True): 2, ('proj_s2', True): 2, ('entry', True): 7})
+# every other distinct bottleneck of ResNet-50 / 101 at its real width ('entry' above is stage 1's first), on a 2 x 5 x 4 map
+REAL_SPECS = {'s1_id': (256, 64, 1, False), 's2_entry': (256, 128, 2, True), 's2_id': (512, 128, 1, False),
+              's3_entry': (512, 256, 2, True), 's3_id': (1024, 256, 1, False), 's4_entry': (1024, 512, 2, True),
+              's4_id': (2048, 512, 1, False)}
+REAL_X = (5, 4)
+# per (shape, batch statistics): R.find_seed(xshape, [spec], modes=(batch_stats,), last=40, factor=16) on the CPU
+# (the tightest: s4_id with batch statistics, 17 times; the fp32 oracle's largest rel_err over all quantities is 1.1e-6: the bar is
+# EXACT_BAR everywhere)
+REAL_SEEDS = {(v, bs): 1 for v in REAL_SPECS for bs in (False, True)}
+REAL_SEEDS.update({('s1_id', True): 2, ('s2_entry', True): 2, ('s3_id', False): 3, ('s4_id', False): 8, ('s4_id', True): 9})
+# the two-consumer seam: four stages of one block each; every stage output feeds the next stage AND takes a gradient of its own
+SEAM_SPECS = [(64, 32, 1, True), (128, 32, 2, True), (128, 32, 2, True), (128, 32, 2, True)]
+SEAM_X = (2, 64, 9, 7)
+SEAM_SEEDS = {False: 1, True: 3}                          # per batch statistics: R.find_seed(SEAM_X, SEAM_SPECS, (mode,), ups=seam_ups())
 _MAX = {}
 compare = functools.partial(train_helpers.compare, _MAX)
 
@@ -109,13 +150,20 @@ def test_stride_2_data_gradient_alone(shape):
         unread = torch.ones(Hh, W, dtype=torch.bool)
         unread[::2, ::2] = False
         assert (got[:, unread].view(torch.int32) == 0).all() and bool(got[:, ~unread].ne(0).any())
-    if shape == DG_SHAPES[-1]:
+    if shape in DG_RANDOM:
         g = torch.randn(B, down(Hh), down(W), Cout, generator=gen)
         w = torch.randn(Cout, Cin, k, k, generator=gen) * (2.0 / (Cout * k * k)) ** 0.5
         gd = nan_padded(g)
         got = twice(lambda: dict(dx=dgrad_gpu(gd, w, Hh, W)))
-        compare('dgrad_s2_random_%dx%d' % (Hh, W), got, dict(dx=dgrad_oracle(g, w, Hh, W, torch.float64)),
-                dict(dx=dgrad_oracle(g, w, Hh, W, torch.float32)))
+        name = 'dgrad_s2_random_%dx%d' % (Hh, W) + ('_%d_%d' % (Cin, Cout) if shape in DG_WIDE else '')
+        want = dict(dx=dgrad_oracle(g, w, Hh, W, torch.float64))
+        compare(name, got, want, dict(dx=dgrad_oracle(g, w, Hh, W, torch.float32)))
+        if shape in DG_WIDE:      # the comparison can fail: an oracle that drops one block of 32 output channels of g is not met
+            lost = g.clone()
+            lost[..., Cout - 64:Cout - 32] = 0
+            e, bar = rel_err(got['dx'], dgrad_oracle(lost, w, Hh, W, torch.float64)), _MAX[name]['dx'][1]
+            print('%s against an oracle without the channels %d .. %d of g: rel_err %.3e (bar %.3e)' % (name, Cout - 64, Cout - 33, e, bar))
+            assert e > bar
 
 
 # ---- 2. the BatchNorm kernels alone -------------------------------------------------------------------------------------------------------
@@ -236,7 +284,10 @@ def test_batchnorm_variance_comes_from_deviations():
 
 
 # ---- 3. conv2d_plain, batch_norm_act and bottleneck through autograd ----------------------------------------------------------------------
-@pytest.mark.parametrize('geo', [(3, 1, 32, 40), (1, 1, 64, 32), (3, 2, 32, 32), (1, 2, 64, 96), (3, 2, 64, 40)],
+# the last two: stage 4's conv2 and conv1 (in stage 4's identity blocks) at their real widths: the stride-1 data gradient on the inference
+# engine with K = 9 * 512 = 4608 and K = 2048, the weight gradient with gridDim.x = 144 and 64
+@pytest.mark.parametrize('geo', [(3, 1, 32, 40), (1, 1, 64, 32), (3, 2, 32, 32), (1, 2, 64, 96), (3, 2, 64, 40), (3, 1, 512, 512),
+                                 (1, 1, 2048, 512)],
                          ids=lambda g: '%dx%d_s%d_%dto%d' % (g[0], g[0], g[1], g[2], g[3]))
 def test_conv2d_plain_through_autograd(geo):
     k, stride, Cin, Cout = geo
@@ -341,6 +392,93 @@ def test_bottleneck_through_autograd(variant, batch_stats):
     xshape = (2, spec[0], 9, 7)
     x, params, blocks, up = R.random_case(BLOCK_SEEDS[(variant, batch_stats)], xshape, [spec])
     check_blocks('%s_%s' % (variant, 'stats' if batch_stats else 'frozen'), [spec], x, params, blocks, up, batch_stats)
+
+
+@pytest.mark.parametrize('batch_stats', [False, True], ids=['frozen', 'batch_stats'])
+@pytest.mark.parametrize('variant', list(REAL_SPECS))
+def test_bottleneck_at_the_real_widths(variant, batch_stats):
+    """Every distinct bottleneck of ResNet-50 / 101 the toy widths leave out, on x [2, inplanes, 5, 4]: odd H and even W (the stride-2
+    blocks meet the masked last column), every pixel at a border, and behind the stride a 3 x 2 map: 12 positions for the batch
+    statistics, below one BatchNorm chunk.  Output, d_x, every parameter gradient and the new running statistics."""
+    spec = REAL_SPECS[variant]
+    xshape = (2, spec[0]) + REAL_X
+    x, params, blocks, up = R.random_case(REAL_SEEDS[(variant, batch_stats)], xshape, [spec])
+    check_blocks('%s_%s' % (variant, 'stats' if batch_stats else 'frozen'), [spec], x, params, blocks, up, batch_stats)
+
+
+def seam_ups():
+    """One upstream gradient per stage output of the seam case, in {-1, -1/2, 0, 1/2, 1}: the same for every seed."""
+    gen = torch.Generator().manual_seed(6)
+    return [torch.randint(-2, 3, R.out_shape(SEAM_X, SEAM_SPECS[:i + 1]), generator=gen).float() / 2 for i in range(len(SEAM_SPECS))]
+
+
+class _Stages:
+    """What train_net.backbone reads of a Yolact: .backbone.layers, a ModuleList (the stages) of ModuleLists of Bottlenecks."""
+
+    def __init__(self, mods):
+        self.backbone = nn.Module()
+        self.backbone.layers = nn.ModuleList(nn.ModuleList([m]) for m in mods)
+
+
+def run_seam(mods, params, blocks, x, ups, batch_stats, through_backbone):
+    """sum_i <stage output i, ups[i]> through train_net.backbone (the view_as alias per stage and its node order) or through the
+    hand-composed chain of TO.bottleneck calls -> the stage outputs, d_x and the gradient of every parameter."""
+    from yolact_amd import train_net as TN
+    restore_stats(mods, params, blocks)
+    leaf = x.permute(0, 2, 3, 1).contiguous().to(DEV).requires_grad_(True)
+    if through_backbone:
+        outs = [o.permute(0, 3, 1, 2) for o in TN.backbone(_Stages(mods), leaf, batch_stats)]      # as Yolact.forward_backbone does
+    else:
+        # as manual() of test_forward_backbone_on_the_real_model: the view of a stage's output is made before the next stage runs, so
+        # that what arrives through it is added to the map's gradient last, behind the next stage's conv1 and shortcut (three addends:
+        # their order decides the bits)
+        h, outs = leaf, []
+        for blk in mods:
+            h = TO.bottleneck(h, blk, batch_stats)
+            outs.append(h.permute(0, 3, 1, 2))
+    assert len(outs) == len(mods)
+    names, plist = [], []
+    for blk, (prefix, _) in zip(mods, blocks):
+        for n, p in blk.named_parameters():
+            names.append(prefix + n)
+            plist.append(p)
+    total = sum((o * u.to(DEV)).sum() for o, u in zip(outs, ups))
+    gr = torch.autograd.grad(total, [leaf] + plist)
+    torch.cuda.synchronize()
+    got = {'out%d' % i: o.detach().cpu() for i, o in enumerate(outs)}
+    got['d_x'] = gr[0].permute(0, 3, 1, 2).cpu()
+    got.update({'d_' + n: t.cpu() for n, t in zip(names, gr[1:])})
+    return got
+
+
+@pytest.mark.parametrize('batch_stats', [False, True], ids=['frozen', 'batch_stats'])
+def test_every_stage_output_has_two_consumers(batch_stats):
+    """train_net.backbone on four stages of one block each (reduced planes, where the ReLU margins hold), with a gradient arriving at
+    EVERY stage output as well as through the next stage: autograd adds the two at the view_as alias.  A backward that wrote into its
+    incoming gradient, or reused it, would be wrong only here, where that buffer has a second reader.  Against the fp64 oracle (the four
+    outputs, d_x, every parameter gradient), the bits of the hand-composed chain, and each extra consumer shown to contribute."""
+    x, params, blocks, _ = R.random_case(SEAM_SEEDS[batch_stats], SEAM_X, SEAM_SPECS)
+    ups = seam_ups()
+    name = 'seam_%s' % ('stats' if batch_stats else 'frozen')
+    m = R.relu_margins(x, params, blocks, None, batch_stats, ups)
+    print(name, 'tightest ReLU margin: %s %.3e, fp32 deviation %.3e' % R.tightest(m))
+    assert len(m) == 12 and all(lo < float('inf') for _, lo, _ in m)
+    R.assert_margins(m)
+    r64, r32 = (R.run_ref(x, params, blocks, None, batch_stats, dt, ups=ups) for dt in (torch.float64, torch.float32))
+    keys = [k for k in r64 if not k.startswith('_') and not k.startswith('new_')]
+    assert len(keys) == 4 + 1 + 4 * 12
+    mods = make_blocks(SEAM_SPECS, params, blocks)
+    got = twice(lambda: run_seam(mods, params, blocks, x, ups, batch_stats, True))
+    assert [tuple(got['out%d' % i].shape) for i in range(4)] == [(2, 128, 9, 7), (2, 128, 5, 4), (2, 128, 3, 2), (2, 128, 2, 1)]
+    compare(name, got, {k: r64[k] for k in keys}, {k: r32[k] for k in keys})
+    same_bits(got, run_seam(mods, params, blocks, x, ups, batch_stats, False))
+    for i in range(3):      # without the gradient of its own at stage output i, d_x is another one: the extra consumer counts
+        less = [torch.zeros_like(u) if j == i else u for j, u in enumerate(ups)]
+        other = run_seam(mods, params, blocks, x, less, batch_stats, True)
+        same_bits(other['out%d' % i], got['out%d' % i])
+        assert not torch.equal(other['d_x'], got['d_x']), i
+        want = R.run_ref(x, params, blocks, None, batch_stats, torch.float64, ups=less)['d_x']
+        assert rel_err(got['d_x'], want) > _MAX[name]['d_x'][1], i
 
 
 def test_needs_input_grad_is_honoured_and_an_edited_parameter_is_refused():

@@ -9,6 +9,11 @@ a ReLU first asserts on the oracle that the smallest |pre-activation| that recei
 fp32-versus-fp64 deviation of that tensor; the seeds below were chosen on the CPU so that this holds (the golden's is in its meta).  The
 single-layer cases take their inputs from grids (maps in 1/256, weights in 1/2048), where the margin is the smallest non-zero
 |pre-activation|.  Every case runs twice on the same inputs and must give the same bits.
+
+WG2_WIDE holds the stride-2 weight gradients of the backbone's stage entries at their real widths, which select wgrad_k<4, 2> (nt = 4):
+3x3 512 -> 512 and 1x1 1024 -> 2048 (gz = 4), and the two Cout at which the waves of a block differ: 288 (nact = 3, 2, 2, 2) and 520 (a
+second z-block of 8 channels: nact = 1, 0, 0, 0).  Each also shows that it can fail: against an fp64 oracle that drops one block of 32
+output channels of g the GPU result misses the bar, in dw and in db.
 """
 import ctypes as C
 import functools
@@ -41,6 +46,14 @@ UP_SHAPES = [((4, 3), (7, 5)), ((7, 5), (13, 10)), ((1, 1), (2, 3)), ((5, 7), (1
 # (kernel, B, H, W, Cin, Cout) at stride 2: odd extents with every window at a border and Cout < 32; even extents; 1x1; 2 * 19 * 21 =
 # 798 positions: several chunks with a ragged last one
 WG2_SHAPES = [(3, 2, 5, 7, 32, 12), (3, 1, 8, 6, 64, 40), (1, 2, 7, 9, 64, 32), (3, 2, 37, 41, 32, 96)]
+# More than 8 column tiles of 32 output channels: wgrad_k<4, 2> (nt = 4: a wave holds the tiles wave, wave + 4, wave + 8, wave + 12 of its
+# block of 512 channels), which the shapes above (nt = 1) and the FPN at 256 features (nt = 2) never launch.  All on a 5 x 4 map (odd H,
+# even W; 6 or 12 positions: one ragged chunk).  Stage 3's conv2 (gz = 1, nact = 4 in every wave, gridDim.x = 9 * 16); stage 4's
+# projection (gz = 4 full z-blocks: the offset ob = 512 z, gridDim.x = 32); Cout = 288 = 9 tiles (wave 0 holds 3 live tiles, waves 1 .. 3
+# hold 2: nact differs per wave); Cout = 520 (gz = 2, the second z-block holds 8 channels: wave 0 has nact = 1 with 24 dead columns,
+# waves 1 .. 3 return at nact == 0).  Their g has 32 NaN padding channels behind Cout.
+WG2_WIDE = [(3, 2, 5, 4, 512, 512), (1, 2, 5, 4, 1024, 2048), (3, 1, 5, 4, 32, 288), (1, 2, 5, 4, 64, 520)]
+WG2_SHAPES += WG2_WIDE
 # conv2d_down: the first three, and mixed parity with a padded width: odd H, even W (the last odd column has a masked tap), ldg 64 with
 # 24 zero channels that must contribute nothing (SEEDS['conv'] keeps the ReLU margin here too: checked on the CPU)
 DOWN_SHAPES = WG2_SHAPES[:3] + [(3, 1, 5, 6, 32, 40)]
@@ -127,7 +140,8 @@ def wgrad_case(shape, stride):
     g = torch.Generator().manual_seed(SEEDS['wgrad'])
     x = torch.randn(B, Hh, W, Cin, generator=g)
     dy = torch.randn(B, Ho, Wo, Cout, generator=g)
-    gpad = torch.full((B, Ho, Wo, (Cout + 31) // 32 * 32), float('nan'))           # the padding channels are never read
+    ldg = (Cout + 31) // 32 * 32 + (32 if shape in WG2_WIDE else 0)
+    gpad = torch.full((B, Ho, Wo, ldg), float('nan'))           # the padding channels are never read
     gpad[..., :Cout] = dy
     return x, dy, gpad
 
@@ -136,22 +150,33 @@ def wgrad_case(shape, stride):
 def test_stride_2_weight_gradient_alone(shape):
     k, B, Hh, W, Cin, Cout = shape
     x, dy, gpad = wgrad_case(shape, 2)
-    want = {}
-    for dtype in (torch.float64, torch.float32):
+    def oracle(dy, dtype):
         w = torch.zeros(Cout, Cin, k, k, dtype=dtype, requires_grad=True)
         b = torch.zeros(Cout, dtype=dtype, requires_grad=True)
         y = F.conv2d(x.to(dtype).permute(0, 3, 1, 2), w, b, stride=2, padding=k // 2)
         assert y.shape[2:] == dy.shape[1:3]
         dw, db = torch.autograd.grad((y * dy.to(dtype).permute(0, 3, 1, 2)).sum(), [w, b])
-        want[dtype] = dict(dw=dw, db=db)
+        return dict(dw=dw, db=db)
+    want = {dtype: oracle(dy, dtype) for dtype in (torch.float64, torch.float32)}
     xd, gd = x.to(DEV), gpad.to(DEV)
+    assert shape not in WG2_WIDE or (gpad.shape[3] > Cout and bool(torch.isnan(gpad[..., Cout:]).all()))
     got = twice(lambda: wgrad_gpu(xd, gd, Cout, k, 2))
-    compare('wgrad_s2_%dx%d_%d_%d_%dx%d' % (k, k, Cin, Cout, Hh, W), got, want[torch.float64], want[torch.float32])
+    name = 'wgrad_s2_%dx%d_%d_%d_%dx%d' % (k, k, Cin, Cout, Hh, W)
+    compare(name, got, want[torch.float64], want[torch.float32])
+    if shape in WG2_WIDE:      # the comparison can fail: an oracle that drops the last full block of 32 output channels of g is not met
+        lost = dy.clone()
+        lo = (Cout - 32) // 32 * 32
+        lost[..., lo:lo + 32] = 0
+        off = oracle(lost, torch.float64)
+        for q in ('dw', 'db'):
+            e, bar = rel_err(got[q], off[q]), _MAX[name][q][1]
+            print('%s %s against an oracle without the channels %d .. %d of g: rel_err %.3e (bar %.3e)' % (name, q, lo, lo + 31, e, bar))
+            assert e > bar
 
 
 def test_stride_1_set_explicitly_gives_the_bits_of_the_field_left_zero():
     from test_gpu_heads_train import WG_SHAPES
-    assert len(WG_SHAPES) == 4
+    assert len(WG_SHAPES) == 7                            # the three real widths too: nt = 4 at stride 1, gz = 4
     for shape in WG_SHAPES:
         x, dy, gpad = wgrad_case(shape, 1)
         xd, gd = x.to(DEV), gpad.to(DEV)

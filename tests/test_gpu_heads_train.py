@@ -9,6 +9,10 @@ the measured fp32-versus-fp64 deviation of that tensor (the rule of tests/test_g
 the protonet is exempt (its input is a sum of non-negatives).  The seeds below were chosen on the CPU so that this holds.  The
 single-layer cases take their inputs from grids on which the pre-activations are exact in fp32 (maps in 1/256, weights in 1/2048):
 their deviation is 0 and the margin is the smallest non-zero |pre-activation|.  Nothing is left out of a comparison.
+
+WG_WIDE holds the stride-1 weight gradients of the backbone's last stage at their real widths, all wgrad_k<4, 1> (nt = 4): 1x1 2048 -> 512
+(gridDim.x = 64), 1x1 512 -> 2048 (gz = 4 full z-blocks) and 3x3 512 -> 512 (gridDim.x = 144), on 18 positions.  Each also shows that it
+can fail: against an fp64 oracle that drops one block of 32 output channels of g the GPU result misses the bar, in dw and in db.
 """
 import ctypes as C
 import functools
@@ -35,6 +39,12 @@ SMALL_PYRAMID = [(5, 5), (3, 3), (2, 2), (1, 1), (1, 1)]
 # (kernel, B, H, W, Cin, Cout): a map smaller than a tile with every pixel at a border and Cout < 32; an odd Cout over several column
 # tiles and two channel chunks; 1x1; 3 034 positions: several chunks with a ragged last one and the ordered second pass
 WG_SHAPES = [(3, 2, 5, 7, 32, 12), (3, 1, 9, 9, 64, 243), (1, 3, 6, 6, 256, 32), (3, 2, 37, 41, 32, 96)]
+# The backbone's stride-1 convolutions at the widths of stage 4, on its 3 x 3 map at batch 2 (18 positions: one ragged chunk, every pixel
+# at a border).  The heads reach Cout = 1053 only with Cin = 256 (gridDim.x = 72).  conv1: Cin = 2048, gridDim.x = 64 blocks of 32 input
+# channels, nt = 4, gz = 1; conv3: Cout = 2048 = 4 full z-blocks of 512 channels with nothing ragged, gridDim.x = 16; conv2: gridDim.x =
+# 9 * 16 = 144 (tap, channel block) pairs, the largest gradient of the backbone (9 x 512 x 512).
+WG_WIDE = [(1, 2, 3, 3, 2048, 512), (1, 2, 3, 3, 512, 2048), (3, 2, 3, 3, 512, 512)]
+WG_SHAPES += WG_WIDE
 _MAX = {}
 compare = functools.partial(train_helpers.compare, _MAX)
 
@@ -78,13 +88,13 @@ def test_weight_gradient_alone(shape):
     g = torch.Generator().manual_seed(SEEDS['wgrad'])
     x = torch.randn(B, Hh, W, Cin, generator=g)
     dy = torch.randn(B, Hh, W, Cout, generator=g)
-    want = {}
-    for dtype in (torch.float64, torch.float32):
+    def oracle(dy, dtype):
         w = torch.zeros(Cout, Cin, k, k, dtype=dtype, requires_grad=True)
         b = torch.zeros(Cout, dtype=dtype, requires_grad=True)
         y = F.conv2d(x.to(dtype).permute(0, 3, 1, 2), w, b, padding=k // 2)
         dw, db = torch.autograd.grad((y * dy.to(dtype).permute(0, 3, 1, 2)).sum(), [w, b])
-        want[dtype] = dict(dw=dw, db=db)
+        return dict(dw=dw, db=db)
+    want = {dtype: oracle(dy, dtype) for dtype in (torch.float64, torch.float32)}
     ldg = (Cout + 31) // 32 * 32
     gpad = torch.full((B, Hh, W, ldg), float('nan'))           # the padding channels are never read
     gpad[..., :Cout] = dy
@@ -94,6 +104,15 @@ def test_weight_gradient_alone(shape):
     dw2, db2 = wgrad_gpu(x.to(DEV), gpad.to(DEV), Cout, k)
     same_bits(dw, dw2, 'dw')
     same_bits(db, db2, 'db')
+    if shape in WG_WIDE:      # the comparison can fail: an oracle that drops one block of 32 output channels of g is not met
+        lost = dy.clone()
+        lost[..., Cout - 64:Cout - 32] = 0
+        off = oracle(lost, torch.float64)
+        for q, t in (('dw', dw), ('db', db)):
+            e, bar = rel_err(t, off[q]), _MAX[name][q][1]
+            print('%s %s against an oracle without the channels %d .. %d of g: rel_err %.3e (bar %.3e)'
+                  % (name, q, Cout - 64, Cout - 33, e, bar))
+            assert e > bar
 
 
 # ---- the activation backward alone ---------------------------------------------------------------------------------------------------------
