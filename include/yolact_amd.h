@@ -1133,6 +1133,45 @@ typedef struct { int32_t A, B; int64_t n; } ymi_mask_iou_shape;
 typedef struct { int32_t N, h, w, cap; } ymi_rle_shape;      /* cap <= 0: the safe capacity h*w + 1 */
 int64_t ymi_workspace_bytes(int what, const void *desc);
 
+/* -- the SGD update (csrc/sgd.hip; additive to ABI 9) ------------------------------------------------------------------------------
+ * train.py:215-216,316-318: torch.optim.SGD(lr, momentum, weight_decay).step() behind `if torch.isfinite(loss).item()`, and
+ * optimizer.zero_grad(), over EVERY tensor of a parameter group in ONE launch with no host read.  Per element, every operation rounded
+ * once to fp32 (no FMA contraction), so numpy fp32 restates it bit for bit:
+ *     d = g + wd * p              (wd == 0: d = g exactly)
+ *     m = mom * m + d             (the buffers start at zero, so the first step gives m = d, as torch does)
+ *     p = p - lr * m              (mom == 0: p = p - lr * d and m is neither read nor written)
+ * Dampening and Nesterov are not offered.  These are NOT torch's bits: torch's foreach / fused kernels contract to FMAs.
+ * Guard: with `loss` given and *loss not finite, no p and no m changes and one thread adds 1 to *skipped (a plain load and store).
+ * With zero_grad the gradients are zeroed in the same pass, applied or skipped.
+ * tensors [n_tensors] and chunks [n_chunks] are DEVICE tables; a chunk is up to YMI_SGD_CHUNK elements of one tensor starting at
+ * `first` (a multiple of YMI_SGD_CHUNK: ymi_sgd_plan writes the table).  One block walks a chunk; the grid is min(n_chunks,
+ * max_blocks) blocks, which stride over the chunks (max_blocks 0: 2048).  A chunk whose p, g and m are 16-byte aligned moves as
+ * 16-byte loads and stores with a scalar tail, any other one element at a time.  A chunk record that points outside its tensor, or
+ * outside the tensor table, is passed over.  No atomics, no LDS, bit-reproducible.
+ * YMI_ENULL: the descriptor NULL.  YMI_EARG: tensors or chunks NULL, n_tensors / n_chunks / max_blocks < 0, momentum < 0 or not
+ * finite; and, where the optional HOST copy of the tensor table `tensors_host` is given: p or g NULL, n < 0, m NULL with
+ * momentum > 0 (without the host copy the kernel leaves such a tensor untouched). */
+#define YMI_SGD_CHUNK 4096           /* elements; a multiple of 4 */
+typedef struct { float *p, *g, *m; int64_t n; } ymi_sgd_tensor;
+typedef struct { int32_t tensor; int32_t _pad0; int64_t first; } ymi_sgd_chunk;
+typedef struct {
+  const ymi_sgd_tensor *tensors;       /* device [n_tensors] */
+  const ymi_sgd_chunk *chunks;         /* device [n_chunks] */
+  const ymi_sgd_tensor *tensors_host;  /* host copy of `tensors` to validate, or NULL */
+  const float *loss;                   /* device scalar the guard reads, or NULL: always apply */
+  int32_t *skipped;                    /* device counter of skipped steps, or NULL */
+  int32_t n_tensors, n_chunks;
+  float lr, momentum, weight_decay;    /* rounded to fp32 once, by the caller */
+  int32_t zero_grad;                   /* != 0: g = 0 in the same pass */
+  int32_t max_blocks;                  /* 0: the default cap of 2048 blocks */
+  int32_t _pad0;
+} ymi_sgd_desc;
+int ymi_sgd_step_f32(const ymi_sgd_desc *d, void *stream);
+/* HOST.  The chunk table of tensors of numel[0 .. n) elements, tensor by tensor, a tensor of 0 elements getting none; returns its
+ * length, and writes its first min(length, cap) records to `out` unless `out` is NULL.  YMI_EARG: numel NULL with n > 0, n < 0, a
+ * negative numel, cap < 0. */
+int64_t ymi_sgd_plan(const int64_t *numel, int n, ymi_sgd_chunk *out, int64_t cap);
+
 /* -- box calibration (ABI 7; csrc/calib.hip) ------------------------------------------------------------------------------------
  * Two fixed micro-workloads the caller times (events on `stream`) right before a benchmark, so that a throughput number can be
  * attributed to the box or to the code (bench.py `box_calibration`).  Not on the product path.

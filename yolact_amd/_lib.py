@@ -226,6 +226,27 @@ class AugmentDesc(C.Structure):
                 ('masks_u8', C.c_int32), ('mean_bgr', C.c_float * 3), ('std_bgr', C.c_float * 3)]
 
 
+SGD_CHUNK = 4096                    # include/yolact_amd.h YMI_SGD_CHUNK: elements of one tensor a block updates at a time
+
+
+class SgdTensor(C.Structure):
+    """include/yolact_amd.h ymi_sgd_tensor."""
+    _fields_ = [('p', C.c_void_p), ('g', C.c_void_p), ('m', C.c_void_p), ('n', C.c_int64)]
+
+
+class SgdChunk(C.Structure):
+    """include/yolact_amd.h ymi_sgd_chunk."""
+    _fields_ = [('tensor', C.c_int32), ('_pad0', C.c_int32), ('first', C.c_int64)]
+
+
+class SgdDesc(C.Structure):
+    """include/yolact_amd.h ymi_sgd_desc."""
+    _fields_ = [('tensors', C.c_void_p), ('chunks', C.c_void_p), ('tensors_host', C.POINTER(SgdTensor)), ('loss', C.c_void_p),
+                ('skipped', C.c_void_p), ('n_tensors', C.c_int32), ('n_chunks', C.c_int32),
+                ('lr', C.c_float), ('momentum', C.c_float), ('weight_decay', C.c_float),
+                ('zero_grad', C.c_int32), ('max_blocks', C.c_int32), ('_pad0', C.c_int32)]
+
+
 class DetectDesc(C.Structure):
     _fields_ = [('conf', C.c_void_p), ('loc', C.c_void_p), ('coef', C.c_void_p), ('priors', C.c_void_p),
                 ('B', C.c_int32), ('P', C.c_int32), ('C', C.c_int32), ('D', C.c_int32),
@@ -391,6 +412,8 @@ SYMBOLS = [
     ('ymi_rle_to_string', C.c_int, [_P, _P, _I, _I, _P, _P, _I, _P]),
     ('ymi_fast_base_transform_f32', C.c_int, [_P, _P, _I, _I, _I, _I, _I, C.POINTER(C.c_float), C.POINTER(C.c_float), _I, _I, _P]),
     ('ymi_ssd_augment_f32', C.c_int, [C.POINTER(AugmentDesc), _P]),
+    ('ymi_sgd_step_f32', C.c_int, [C.POINTER(SgdDesc), _P]),
+    ('ymi_sgd_plan', C.c_int64, [C.POINTER(C.c_int64), _I, C.POINTER(SgdChunk), C.c_int64]),
     ('ymi_jpeg_parse', C.c_int, [_P, C.c_size_t, C.POINTER(JpegInfo)]),
     ('ymi_jpeg_decode_coefs', C.c_int, [_P, C.c_size_t, _P, C.c_int64, _P, C.POINTER(JpegInfo)]),
     ('ymi_jpeg_reconstruct_bgr_u8', C.c_int, [C.POINTER(JpegInfo), _P, _P, _P, _P, _P]),

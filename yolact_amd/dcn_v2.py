@@ -45,13 +45,16 @@ def _packed(weight, bias, stride, pad, cin_pad, device):
     """engine.Packed of (weight, bias) (packing splits the filters on the host: worth caching for modules called in a loop).  Keyed
     on the weight tensor OBJECT (identity) through a weak dictionary — an entry dies with its tensor, so a recycled address can never hit a
     stale pack and no dead module's parameters stay pinned on the GPU (round-4 advisor: the key used to be data_ptr + _version) —
-    plus its version counter (in-place edits), the bias object / version, the shapes, the geometry and the device."""
+    plus its version counter (in-place edits), the bias object / version, the shapes, the geometry and the device, plus how many
+    loss-guarded optimiser launches have written each of them (optim.guarded_writes: such a write bumps the version only once it is
+    settled, which a forward must not wait for)."""
     from .engine import Packed
+    from .optim import guarded_writes
     sub = _pack_cache.get(weight)
     if sub is None:
         sub = _pack_cache[weight] = {}
     key = (weight._version, tuple(weight.shape), None if bias is None else (id(bias), bias._version, tuple(bias.shape)),
-           stride, pad, cin_pad, str(device))
+           stride, pad, cin_pad, str(device), guarded_writes(weight), guarded_writes(bias))
     pk = sub.get(key)
     if pk is None:
         sub.clear()                            # one live pack per weight tensor: an older version's pack is garbage

@@ -20,6 +20,7 @@ import torch.nn as nn
 
 from . import _lib as L
 from . import modules as M
+from . import optim
 from . import train_net as TN
 from .config import act_name, active_cfg, backbone_kind, is_lincomb
 from .engine import Plan
@@ -140,7 +141,9 @@ class Yolact(nn.Module):
             self._ptensors = None
 
     def _param_stamp(self):
-        """Sum of the autograd version counters of every parameter / buffer: changes on any in-place edit."""
+        """Sum of the autograd version counters of every parameter / buffer: changes on any in-place edit.  (optim.SGD writes
+        through raw pointers and bumps the counters itself; the bump of a loss-guarded step waits for settle_all(), here.)"""
+        optim.settle_all()
         pt = self._ptensors
         if pt is None:
             pt = self._ptensors = [t for t in list(self.parameters()) + list(self.buffers())]
@@ -167,7 +170,31 @@ class Yolact(nn.Module):
         return r
 
     def init_weights(self, backbone_path):
-        raise NotImplementedError('training initialisation is out of scope (inference hot path only)')
+        """yolact.py:492-547: the backbone from the pretrained file at `backbone_path` as the reference's init_backbone loads it
+        (backbone.py:141-154: legacy `layer1..4` keys renamed to `layers.0..3`, non-strict), then xavier_uniform_ on the weight of every
+        Conv2d outside the backbone, in named_modules() order from torch's global generator, and zero biases.  (The focal-loss bias of
+        yolact.py:529-545 cannot be reached: __init__ refuses cfg.use_focal_loss.)  The plans are dropped afterwards."""
+        sd = torch.load(backbone_path, map_location='cpu')
+        for key in list(sd):
+            if key.startswith('layer') and not key.startswith('layers'):
+                sd['layers.' + str(int(key[5]) - 1) + key[6:]] = sd.pop(key)
+        self.backbone.load_state_dict(sd, strict=False)
+        backbone_convs = {id(m) for m in self.backbone.backbone_modules}
+        nn.Conv2d(1, 1, 1)      # yolact.py:497 builds one for its __constants__; its default initialisation draws from the generator first
+        for _, module in self.named_modules():
+            if isinstance(module, nn.Conv2d) and id(module) not in backbone_convs:
+                nn.init.xavier_uniform_(module.weight.data)
+                if module.bias is not None:
+                    module.bias.data.zero_()
+        self.invalidate_plans()
+
+    def freeze_bn(self, enable=False):
+        """yolact.py:555-562 without its module.train() / eval(): requires_grad of every BatchNorm's weight and bias.  The module mode
+        stays as it is (train() raises); whether a forward_train normalises with the batch statistics is its batch_stats argument."""
+        for module in self.modules():
+            if isinstance(module, nn.BatchNorm2d):
+                module.weight.requires_grad = enable
+                module.bias.requires_grad = enable
 
     def train(self, mode=True):
         if mode:
