@@ -23,9 +23,10 @@ def conv_plain_ref(x, w, stride=1):
     return F.conv2d(x, w, None, stride=stride, padding=w.shape[2] // 2)
 
 
-def bn_ref(x, gamma, beta, rmean, rvar, batch_stats, eps=EPS, momentum=MOMENTUM, unbiased_running=True):
+def bn_ref(x, gamma, beta, rmean, rvar, batch_stats, eps=EPS, momentum=MOMENTUM, unbiased_running=True, xhat_term=True):
     """-> (y, new running_mean, new running_var, mean, invstd).  batch_stats: the statistics of x over (N, H, W), biased variance
-    for the normalisation and the unbiased one in the running update; else the running statistics, which stay."""
+    for the normalisation and the unbiased one in the running update; else the running statistics, which stay.  xhat_term=False is a
+    deliberately WRONG variant: the same values, but the backward loses its mean(dy * xhat) * xhat term (the variance is a constant)."""
     dims = [d for d in range(x.dim()) if d != 1]
     shape = [1, -1] + [1] * (x.dim() - 2)
     if batch_stats:
@@ -37,7 +38,7 @@ def bn_ref(x, gamma, beta, rmean, rvar, batch_stats, eps=EPS, momentum=MOMENTUM,
             new_var = (1 - momentum) * rvar + momentum * var.detach() * ((n / (n - 1)) if unbiased_running else 1.0)
     else:
         mean, var, new_mean, new_var = rmean, rvar, rmean, rvar
-    invstd = 1 / torch.sqrt(var + eps)
+    invstd = 1 / torch.sqrt((var if xhat_term else var.detach()) + eps)
     y = gamma.view(shape) * ((x - mean.view(shape)) * invstd.view(shape)) + beta.view(shape)
     return y, new_mean, new_var, mean, invstd
 
@@ -68,11 +69,12 @@ def is_leaf_name(n):
     return 'running' not in n
 
 
-def bottleneck_ref(x, P, stride, batch_stats, prefix='', keep=None, new_stats=None, stride_on_conv1=False, unbiased_running=True):
-    """backbone.py:37-57.  keep receives (name, pre-activation, activation) of every ReLU; new_stats the updated running statistics."""
+def bottleneck_ref(x, P, stride, batch_stats, prefix='', keep=None, new_stats=None, stride_on_conv1=False, **bn_kw):
+    """backbone.py:37-57.  keep receives (name, pre-activation, activation) of every ReLU; new_stats the updated running statistics;
+    bn_kw goes to bn_ref (unbiased_running, momentum, xhat_term)."""
     def bn(z, name):
         y, nm, nv, _, _ = bn_ref(z, P[prefix + name + '.weight'], P[prefix + name + '.bias'], P[prefix + name + '.running_mean'],
-                                 P[prefix + name + '.running_var'], batch_stats, unbiased_running=unbiased_running)
+                                 P[prefix + name + '.running_var'], batch_stats, **bn_kw)
         if new_stats is not None:
             new_stats[prefix + name + '.running_mean'], new_stats[prefix + name + '.running_var'] = nm, nv
         return y

@@ -38,9 +38,10 @@ def param_shapes(in_channels, nf, n_down):
     return {n: shapes[n] for n in param_names(len(in_channels), n_down)}
 
 
-def fpn_ref(convouts, params, n_down, keep=None):
+def fpn_ref(convouts, params, n_down, keep=None, detach_down=False):
     """convouts: [B,C_j,h_j,w_j], finest first -> the len(convouts) + n_down maps [B,nf,h,w].  keep receives (name, pre-activation,
-    activation) of every pred layer."""
+    activation) of every pred layer.  detach_down=True is a deliberately WRONG variant: the same values, but nothing comes back from the
+    downsample layers into the deepest pred layer's map."""
     n = len(convouts)
     sums, x = [None] * n, None
     for i in range(n):                                                       # layer i works on level n - 1 - i
@@ -57,7 +58,7 @@ def fpn_ref(convouts, params, n_down, keep=None):
         if keep is not None:
             keep.append(('fpn.pred_layers.%d' % i, z, out[j]))
     for i in range(n_down):
-        out.append(F.conv2d(out[-1], params['fpn.downsample_layers.%d.weight' % i], params['fpn.downsample_layers.%d.bias' % i],
+        out.append(F.conv2d(out[-1].detach() if (detach_down and i == 0) else out[-1], params['fpn.downsample_layers.%d.weight' % i], params['fpn.downsample_layers.%d.bias' % i],
                             stride=2, padding=1))
     return out
 

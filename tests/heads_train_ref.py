@@ -81,14 +81,18 @@ def priors_ref(sizes, spec):
     return torch.tensor(data, dtype=torch.float32).view(-1, 4)
 
 
-def heads_ref(outs, params, spec, keep=None, priors=None):
+def heads_ref(outs, params, spec, keep=None, priors=None, head_grad_levels=None):
     """outs: the FPN maps [B,nf,h_i,w_i] (NCHW, any float dtype, leaves or not); params: name -> tensor of the same dtype ->
-    {'loc' [B,P,4], 'conf' [B,P,C], 'mask' [B,P,D], 'priors' [P,4] fp32, 'proto' [B,2h_0,2w_0,D], 'segm' [B,C-1,h_0,w_0]}."""
+    {'loc' [B,P,4], 'conf' [B,P,C], 'mask' [B,P,D], 'priors' [P,4] fp32, 'proto' [B,2h_0,2w_0,D], 'segm' [B,C-1,h_0,w_0]}.
+    head_grad_levels=n is a deliberately WRONG variant: the same values, but the shared prediction head's parameters take their
+    gradient from the first n levels only."""
     B = outs[0].shape[0]
     proto = net_ref(outs[spec['proto_src']], spec['mask_proto_net'], params, 'proto_net.', spec['proto_act'], keep)
     pred = {'loc': [], 'conf': [], 'mask': []}
     hp = {k: v for k, v in spec['head_layer_params'].items() if k != 'kernel_size'}
-    for x in outs:
+    shared = params
+    for lvl, x in enumerate(outs):
+        params = shared if (head_grad_levels is None or lvl < head_grad_levels) else {k: v.detach() for k, v in shared.items()}
         if spec['extra_head_net'] is not None:
             x = net_ref(x, spec['extra_head_net'], params, 'prediction_layers.0.upfeature.', 'relu', keep)
         for name, width, act in (('loc', 4, 'none'), ('conf', spec['num_classes'], 'none'), ('mask', None, spec['coef_act'])):
@@ -101,7 +105,7 @@ def heads_ref(outs, params, spec, keep=None, priors=None):
     out['priors'] = priors_ref([tuple(o.shape[2:]) for o in outs], spec) if priors is None else priors
     out['proto'] = proto.permute(0, 2, 3, 1).contiguous()
     if spec['segm']:
-        out['segm'] = F.conv2d(outs[0], params['semantic_seg_conv.weight'], params['semantic_seg_conv.bias'])
+        out['segm'] = F.conv2d(outs[0], shared['semantic_seg_conv.weight'], shared['semantic_seg_conv.bias'])
     return out
 
 

@@ -36,11 +36,11 @@ def stem_conv_ref(x, w):
     return F.conv2d(x, w, None, stride=2, padding=3)
 
 
-def stem_ref(x, P, batch_stats, keep=None, new_stats=None, unbiased_running=True):
+def stem_ref(x, P, batch_stats, keep=None, new_stats=None, **bn_kw):
     """backbone.py:129-132 -> the pooled map.  keep receives 'relu': (pre-activation, activation) and 'pool': (input, output);
-    new_stats the updated running statistics."""
+    new_stats the updated running statistics; bn_kw goes to bn_ref (unbiased_running, momentum, xhat_term)."""
     z, nm, nv, _, _ = bn_ref(stem_conv_ref(x, P['conv1.weight']), P['bn1.weight'], P['bn1.bias'], P['bn1.running_mean'],
-                             P['bn1.running_var'], batch_stats, unbiased_running=unbiased_running)
+                             P['bn1.running_var'], batch_stats, **bn_kw)
     if new_stats is not None:
         new_stats['bn1.running_mean'], new_stats['bn1.running_var'] = nm, nv
     a = F.relu(z)

@@ -101,7 +101,9 @@ def test_a_step_is_its_parts(case):
     reset(net, state)
     same_bits(a, run_trainer(net, inputs, 3))                      # and again: the same bits
     moved = [n for n, p in net.named_parameters() if not torch.equal(a['p ' + n], state[n].cpu())]
-    assert len(moved) == len(list(net.parameters()))               # one backward reaches every parameter, one step moves each
+    # one step moves every parameter: weight decay alone does that, so this does NOT show that the backward reaches each (here the
+    # gradients of fpn.downsample_layers.* are exactly zero); tests/test_gpu_train_grads.py shows it, on cases where every one is not
+    assert len(moved) == len(list(net.parameters()))
     assert any(not torch.equal(a['b ' + n], state[n].cpu()) for n, _ in net.named_buffers() if 'running_mean' in n)
     for k in [k for k in a if k.startswith('loss')]:
         assert bool(torch.isfinite(a[k]).all()), k
