@@ -623,6 +623,47 @@ typedef struct ymi_dcn_bwd_desc {
 } ymi_dcn_bwd_desc;
 int ymi_dcn_v2_backward_f32(const ymi_dcn_bwd_desc *d, void *stream);
 
+/* -- the train path's deformable convolution: the column tensor and its backward (csrc/dcn_train.hip; additive at ABI 9) -----------
+ * The im2col half of DCNv2 (dcn_v2_im2col_cuda.cu:143-327) for the same geometry — 3x3, pad 1, dilation 1, one deformable group,
+ * square stride 1 or 2, Cin % 32 == 0 — on dense NHWC fp32, with om [B,Ho,Wo,27] the RAW output of conv_offset_mask: channel 2k =
+ * dh_k, 2k + 1 = dw_k, 18 + k = the mask LOGIT of tap k = 3i + j (the sigmoid and its derivative are applied here).  The GEMM half is
+ * ymi_conv2d_nhwc_f32 / ymi_conv_wgrad_nhwc_f32 on col as a 1x1 convolution of 9 Cin channels.  item = m * 9 + k, m = (b, oy, ox).
+ *   ymi_dcn_cols_fwd_f32      col[item, c] = sigmoid(logit_k) * bilinear(x, point_k)[c], zero-padded, 0 for a point outside
+ *                             -1 < h < H, -1 < w < W (the point formed in fp32 as ymi_dcn_v2_forward_f32 forms it).  Reads x, om.
+ *   ymi_dcn_cols_entries_f32  the inverted index's raw material: entry e = item * 4 + corner (top-left, top-right, bottom-left,
+ *                             bottom-right) gets keys[e] = the corner's pixel (b*H + y)*W + x, or B*H*W when the corner is outside the
+ *                             image or the point is gated out, and coef[e] = corner weight * mu (0 there).  Reads om.
+ *   ymi_dcn_cols_bwd_f32      from dcol [B,Ho,Wo,9*Cin]: g_om [B,Ho,Wo,27] (d/d dh_k, d/d dw_k, d/d logit_k; exactly 0 for a gated-out
+ *                             point; at an integer coordinate the derivative of the cell [h, h + 1]) and gx [B,H,W,Cin].  Either may
+ *                             be NULL (both: no launch).  gx needs sorted_keys / order — keys sorted ascending by a STABLE sort and
+ *                             the permutation that did it (order[i] = the entry at sorted position i) — coef as written above, and
+ *                             seg, B*H*W + 1 ints of scratch.  g_om needs x and om.
+ * SUMMATION ORDER (part of the contract, a function of the shape and of om only): a dot product over channels — lane l of eight
+ * adds the channels 4 l + 32 j + e, j ascending, e = 0 .. 3, from +0.0, then the lanes combine by the butterfly 4, 2, 1; gx[t, c] —
+ * from +0.0, (coef[e] * dcol[e / 4, c]) over the entries of pixel t in ascending e.  No floating-point atomics: the same inputs
+ * give the same bits.  Every element of every output is written.  An order[] value outside [0, 36 B Ho Wo) is skipped, a run
+ * outside the list is clipped: a wrong permutation gives wrong sums, never an access outside the tensors.
+ * YMI_EARG: a size < 1, stride not 1 / 2; YMI_ESHAPE: Cin % 32, Ho / Wo not the convolution's output size, x, col, dcol, om or the
+ * entry list (36 B Ho Wo) of 2^31 elements or more, x / col / dcol / gx / keys / coef not 16-byte aligned; YMI_ENULL: a pointer the
+ * call needs is NULL.  No error path launches anything. */
+typedef struct ymi_dcn_cols_desc {
+  const float *x;               /* [B,H,W,Cin] */
+  const float *om;              /* [B,Ho,Wo,27] */
+  float *col;                   /* [B,Ho,Wo,9*Cin] (fwd: written) */
+  const float *dcol;            /* [B,Ho,Wo,9*Cin] (bwd: read) */
+  float *g_om;                  /* [B,Ho,Wo,27] or NULL */
+  float *gx;                    /* [B,H,W,Cin] or NULL */
+  int32_t *keys;                /* [36 B Ho Wo] (entries: written) */
+  float *coef;                  /* [36 B Ho Wo] (entries: written; bwd: read) */
+  const int32_t *sorted_keys;   /* [36 B Ho Wo] (bwd, gx) */
+  const int64_t *order;         /* [36 B Ho Wo] (bwd, gx) */
+  int32_t *seg;                 /* [B*H*W + 1] scratch (bwd, gx) */
+  int32_t B, H, W, Cin, Ho, Wo, stride, _pad0;
+} ymi_dcn_cols_desc;
+int ymi_dcn_cols_fwd_f32(const ymi_dcn_cols_desc *d, void *stream);
+int ymi_dcn_cols_entries_f32(const ymi_dcn_cols_desc *d, void *stream);
+int ymi_dcn_cols_bwd_f32(const ymi_dcn_cols_desc *d, void *stream);
+
 /* -- lincomb mask loss 'M' with gradients (layers/modules/multibox_loss.py:499-627,650; csrc/mask_loss.hip; additive at ABI 9) --
  * The mask term of MultiBoxLoss for the switches both shipped base configs train with (mask_proto_crop,
  * mask_proto_normalize_emulate_roi_pooling, binarised downsampled GT, sigmoid), for a whole batch in one call:

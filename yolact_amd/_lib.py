@@ -113,6 +113,15 @@ class DcnBwdDesc(C.Structure):
                 ('ldo', C.c_int32), ('mask_is_prob', C.c_int32), ('om_layout', C.c_int32), ('_pad0', C.c_int32)]
 
 
+class DcnColsDesc(C.Structure):
+    """include/yolact_amd.h ymi_dcn_cols_desc."""
+    _fields_ = [('x', C.c_void_p), ('om', C.c_void_p), ('col', C.c_void_p), ('dcol', C.c_void_p), ('g_om', C.c_void_p),
+                ('gx', C.c_void_p), ('keys', C.c_void_p), ('coef', C.c_void_p), ('sorted_keys', C.c_void_p), ('order', C.c_void_p),
+                ('seg', C.c_void_p),
+                ('B', C.c_int32), ('H', C.c_int32), ('W', C.c_int32), ('Cin', C.c_int32), ('Ho', C.c_int32), ('Wo', C.c_int32),
+                ('stride', C.c_int32), ('_pad0', C.c_int32)]
+
+
 class MaskLossDesc(C.Structure):
     """include/yolact_amd.h ymi_mask_loss_desc."""
     _fields_ = [('proto', C.c_void_p), ('coef', C.c_void_p), ('box', C.c_void_p), ('gt', C.c_void_p), ('gt_idx', C.c_void_p),
@@ -376,6 +385,9 @@ SYMBOLS = [
     ('ymi_boxes_to_pixels', C.c_int, [_P, _P, _I, _I, _I, _P]),
     ('ymi_dcn_v2_forward_f32', C.c_int, [C.POINTER(DcnDesc), _P]),
     ('ymi_dcn_v2_backward_f32', C.c_int, [C.POINTER(DcnBwdDesc), _P]),
+    ('ymi_dcn_cols_fwd_f32', C.c_int, [C.POINTER(DcnColsDesc), _P]),
+    ('ymi_dcn_cols_entries_f32', C.c_int, [C.POINTER(DcnColsDesc), _P]),
+    ('ymi_dcn_cols_bwd_f32', C.c_int, [C.POINTER(DcnColsDesc), _P]),
     ('ymi_mask_loss_f32', C.c_int, [C.POINTER(MaskLossDesc), _P]),
     ('ymi_match_f32', C.c_int, [C.POINTER(MatchDesc), _P]),
     ('ymi_box_loss_f32', C.c_int, [_P, _P, _P, _I, _I, _F, _P, _P, _P, _P]),

@@ -13,6 +13,9 @@
                                                             FPN's top-down sum, yolact.py:332-334), any size of lat >= that of top
     batch_norm_act(x, bn, batch_stats, residual, relu)   -> relu(bn(x) + residual) for an nn.BatchNorm2d, batch statistics or frozen
     bottleneck(x, block, batch_stats)                    -> a modules.Bottleneck (backbone.py:37-57); bn3 + shortcut + ReLU are one launch
+    deform_conv(x, om, weight, bias, stride)             -> [B,Ho,Wo,Cout]: a DCN's modulated deformable 3x3 (dcn_v2.py:16-52) from the raw
+                                                            conv_offset_mask output om [B,Ho,Wo,27] (offsets, then mask logits)
+    dcn_bottleneck(x, block, batch_stats)                -> a modules.Bottleneck whose conv2 is a DCN (use_dcn = True)
     stem_conv(x4, weight)                                -> [B,Ho,Wo,Cout]: the stem's 7x7 / stride 2 / padding 3 convolution of 3 channels
                                                             (backbone.py:77) on the image padded to 4 channels, x4 [B,H,W,4]
     max_pool_3x3_s2(x)                                   -> [B,Hp,Wp,C]: F.max_pool2d(x, 3, 2, 1) (backbone.py:80)
@@ -38,6 +41,11 @@ raises NotImplementedError naming it.  Forward: one ymi_conv2d_nhwc_f32 launch o
        being 62 us (profiles/train_net_ab.txt).
 upsample_add: d_lat = dy, d_top = ymi_bilinear_size_bwd_nhwc_f32 (a gather in a fixed order).  batch_norm_act: ymi_bn_fwd_nhwc_f32 /
 ymi_bn_bwd_nhwc_f32 (csrc/bn_train.hip).
+deform_conv: the reference's im2col + GEMM split.  DeformCols (csrc/dcn_train.hip) materialises col [B,Ho,Wo,9*Cin] (ymi_dcn_cols_fwd_f32);
+the GEMM is Conv as a 1 x 1 convolution of col, so y, dw, db and dcol come from the kernels above.  DeformCols' backward:
+ymi_dcn_cols_entries_f32 writes one (target pixel, coefficient) entry per (output pixel, tap, corner), torch.sort(stable=True) orders
+the int32 keys, and ymi_dcn_cols_bwd_f32 gathers gx per input pixel over its entries in that order and forms g_om by fixed-tree dot
+products: no floating-point atomics, equal bits on every run.  col is saved for the weight gradient: 9x the input map.
 stem_conv: one ymi_conv2d_nhwc_f32 launch through the engine's Cin-4 loader with the filter's fourth input channel zero; the backward
 is ymi_stem_wgrad_nhwc_f32 on the SAME x4 (its fourth channel reaches nothing), then _unpack_dw.  It is differentiable in the weight
 only: an x4 that requires grad raises, since nothing upstream of the image needs a gradient and returning None would silently give a
@@ -586,6 +594,171 @@ def bottleneck(x, block, batch_stats=None):
     check_bottleneck(block)
     out = batch_norm_act(conv2d_plain(x, block.conv1.weight), block.bn1, batch_stats, relu=True)
     out = batch_norm_act(conv2d_plain(out, block.conv2.weight, block.stride), block.bn2, batch_stats, relu=True)
+    out = conv2d_plain(out, block.conv3.weight)
+    res = x
+    if block.downsample is not None:
+        res = batch_norm_act(conv2d_plain(x, block.downsample[0].weight, block.stride), block.downsample[1], batch_stats)
+    return batch_norm_act(out, block.bn3, batch_stats, residual=res, relu=True)
+
+
+def check_deform(weight, stride=1, padding=1, dilation=1, deformable_groups=1, who='deform_conv'):
+    """NotImplementedError naming what of a deformable convolution the kernels do not take: anything but the 3 x 3 / padding 1 /
+    dilation 1 / one deformable group / square stride 1 or 2 DCN that YOLACT++ constructs (backbone.py:22-26) on a multiple of 32
+    input channels -> stride."""
+    if weight.dim() != 4:
+        raise NotImplementedError('yolact_amd %s: a weight of shape %s is not supported ([Cout,Cin,3,3] is)' % (who, tuple(weight.shape)))
+    Cout, Cin, kh, kw = weight.shape
+    if (kh, kw) != (3, 3):
+        raise NotImplementedError('yolact_amd %s: a %d x %d kernel is not supported (3 x 3 is)' % (who, kh, kw))
+    if isinstance(stride, str) or _pair(stride) not in ((1, 1), (2, 2)):
+        raise NotImplementedError('yolact_amd %s: stride = %r is not supported (stride 1 and stride 2 are)' % (who, stride))
+    if isinstance(padding, str) or _pair(padding) != (1, 1):
+        raise NotImplementedError('yolact_amd %s: padding = %r is not supported (padding 1 is)' % (who, padding))
+    if _pair(dilation) != (1, 1):
+        raise NotImplementedError('yolact_amd %s: dilation = %r is not supported (dilation 1 is)' % (who, dilation))
+    if deformable_groups != 1:
+        raise NotImplementedError('yolact_amd %s: deformable_groups = %r is not supported (one deformable group is)'
+                                  % (who, deformable_groups))
+    if Cin % 32 != 0:
+        raise NotImplementedError('yolact_amd %s: Cin = %d is not supported (a multiple of 32 input channels is)' % (who, Cin))
+    return _pair(stride)[0]
+
+
+def _cols_desc(xd, omd, stride):
+    B, H, W, Cin = xd.shape
+    Ho, Wo = _out_size(H, W, 3, 1, stride)
+    d = L.DcnColsDesc()
+    d.x, d.om = xd.data_ptr(), omd.data_ptr()
+    d.B, d.H, d.W, d.Cin, d.Ho, d.Wo, d.stride = B, H, W, Cin, Ho, Wo, stride
+    return d, Ho, Wo
+
+
+class DeformCols(torch.autograd.Function):
+    """apply(stride, x [B,H,W,Cin], om [B,Ho,Wo,27]) -> col [B,Ho,Wo,9*Cin], col[m, k*Cin + c] = sigmoid(logit_k) * bilinear(x, point_k)[c]
+    (csrc/dcn_train.hip).  The backward writes the inverted index's entries, sorts their int32 keys stably with torch.sort, and
+    gathers gx in that order; g_om is one launch of fixed-tree dot products."""
+
+    @staticmethod
+    def forward(ctx, stride, x, om):
+        dev = x.device
+        with torch.cuda.device(dev), torch.no_grad():
+            xd, omd = LC.f32(x, dev), LC.f32(om, dev)
+            d, Ho, Wo = _cols_desc(xd, omd, stride)
+            col = torch.empty(xd.shape[0], Ho, Wo, 9 * xd.shape[3], dtype=torch.float32, device=dev)
+            d.col = col.data_ptr()
+            L.check(L.lib().ymi_dcn_cols_fwd_f32(C.byref(d), L.stream_ptr()), 'ymi_dcn_cols_fwd_f32')
+        ctx.save_for_backward(x, om)                        # (the version check)
+        ctx.stride, ctx.dtypes = stride, (x.dtype, om.dtype)
+        return col
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dcol):
+        x, om = ctx.saved_tensors
+        want_x, want_om = ctx.needs_input_grad[1:3]
+        if not (want_x or want_om):
+            return None, None, None
+        dev = x.device
+        with torch.cuda.device(dev), torch.no_grad():
+            xd, omd, dcold = LC.f32(x, dev), LC.f32(om, dev), LC.f32(dcol, dev)
+            d, Ho, Wo = _cols_desc(xd, omd, ctx.stride)
+            B, H, W, _ = xd.shape
+            d.dcol = dcold.data_ptr()
+            gx = g_om = None
+            if want_x:
+                n = 36 * B * Ho * Wo
+                keys = torch.empty(n, dtype=torch.int32, device=dev)
+                coef = torch.empty(n, dtype=torch.float32, device=dev)
+                d.keys, d.coef = keys.data_ptr(), coef.data_ptr()
+                L.check(L.lib().ymi_dcn_cols_entries_f32(C.byref(d), L.stream_ptr()), 'ymi_dcn_cols_entries_f32')
+                # ascending target pixel, ties in entry order: the permutation of a stable sort is unique, whatever its internals
+                skeys, order = torch.sort(keys, stable=True)
+                seg = torch.empty(B * H * W + 1, dtype=torch.int32, device=dev)
+                gx = torch.empty_like(xd)
+                d.sorted_keys, d.order, d.seg, d.gx = skeys.data_ptr(), order.data_ptr(), seg.data_ptr(), gx.data_ptr()
+            if want_om:
+                g_om = torch.empty_like(omd)
+                d.g_om = g_om.data_ptr()
+            L.check(L.lib().ymi_dcn_cols_bwd_f32(C.byref(d), L.stream_ptr()), 'ymi_dcn_cols_bwd_f32')
+        return None, (None if gx is None else gx.to(ctx.dtypes[0])), (None if g_om is None else g_om.to(ctx.dtypes[1]))
+
+
+def deform_conv(x, om, weight, bias, stride=1):
+    """The modulated deformable convolution of a DCN (dcn_v2.py:16-52, 118-128) on NHWC x [B,H,W,Cin]: om [B,Ho,Wo,27] is the RAW
+    output of the DCN's conv_offset_mask (channel 2k = dh_k, 2k + 1 = dw_k, 18 + k = the mask logit of tap k = 3i + j; the sigmoid is
+    applied here), weight [Cout,Cin,3,3] and bias [Cout] (or None) in torch layout -> [B,Ho,Wo,Cout].  Two steps: the modulated
+    column tensor (DeformCols), then Conv as a 1 x 1 convolution of its 9 Cin channels with the weight viewed as [Cout, 9 Cin, 1, 1]
+    (autograd carries the gradient back to [Cout,Cin,3,3]).  Once differentiable in x, om, weight and bias; no floating-point
+    atomics, the same inputs give the same bits."""
+    L.require_cuda(x, 'deform_conv x')
+    L.require_cuda(om, 'deform_conv om')
+    L.require_cuda(weight, 'deform_conv weight')
+    st = check_deform(weight, stride)
+    _check_x('deform_conv', x, weight)
+    Cout, Cin = int(weight.shape[0]), int(weight.shape[1])
+    B, H, W, _ = x.shape
+    Ho, Wo = _out_size(H, W, 3, 1, st)
+    if tuple(om.shape) != (B, Ho, Wo, 27):
+        raise ValueError('deform_conv: om %s for x %s at stride %d ([B,Ho,Wo,27] = %s is expected)'
+                         % (tuple(om.shape), tuple(x.shape), st, (B, Ho, Wo, 27)))
+    if bias is not None:
+        L.require_cuda(bias, 'deform_conv bias')
+        if bias.numel() != Cout:
+            raise ValueError('deform_conv: weight %s / bias %s' % (tuple(weight.shape), tuple(bias.shape)))
+    if min(B, H, W, Ho, Wo) < 1:
+        raise ValueError('deform_conv: x %s has no output pixel at stride %d' % (tuple(x.shape), st))
+    # the column tensor is the 1 x 1 convolution's input: the conv engine and the weight gradient address it with 31-bit byte offsets
+    if B * Ho * Wo * 9 * Cin >= 1 << 29 or B * H * W * Cin >= 1 << 29:
+        raise NotImplementedError('yolact_amd deform_conv: x %s gives a column tensor of %d elements, which is not supported (fewer '
+                                  'than 2^29, 2 GiB, are)' % (tuple(x.shape), B * Ho * Wo * 9 * Cin))
+    w1 = weight.permute(0, 2, 3, 1).reshape(Cout, 9 * Cin, 1, 1)
+    k, pad = check_conv(w1, 0, who='deform_conv')
+    col = DeformCols.apply(st, x, om)
+    return Conv.apply(k, pad, 1, (L.ACT_NONE,), False, col, w1, bias)[0]
+
+
+def check_dcn_bottleneck(block, name='block'):
+    """NotImplementedError naming what of a DCN backbone block (a modules.Bottleneck with use_dcn = True) the kernels do not take."""
+    from .. import modules as M
+    if not isinstance(block, M.Bottleneck):
+        raise NotImplementedError('yolact_amd dcn_bottleneck: %s is a %s, which is not supported (a Bottleneck is)'
+                                  % (name, type(block).__name__))
+    if not block.use_dcn or not isinstance(block.conv2, M.DCN):
+        raise NotImplementedError('yolact_amd dcn_bottleneck: %s is not a DCN block (use_dcn = False), which is not supported '
+                                  '(bottleneck takes it)' % name)
+    convs = [('conv1', block.conv1, 1, 1), ('conv3', block.conv3, 1, 1)]
+    if block.downsample is not None:
+        convs.append(('downsample.0', block.downsample[0], 1, block.stride))
+    for n, m, k, st in convs:
+        if (tuple(m.kernel_size), tuple(m.stride), tuple(m.padding), tuple(m.dilation), m.groups, m.bias is None) != \
+                ((k, k), (st, st), (k // 2, k // 2), (1, 1), 1, True):
+            raise NotImplementedError('yolact_amd dcn_bottleneck: %s.%s = %r is not supported (a bias-free %d x %d / stride %d / '
+                                      'padding %d is)' % (name, n, m, k, k, st, k // 2))
+        check_plain(m.weight, st, 'dcn_bottleneck %s.%s' % (name, n))
+    dcn, st = block.conv2, block.stride
+    if tuple(dcn.stride) != (st, st):
+        raise NotImplementedError('yolact_amd dcn_bottleneck: %s.conv2 has stride %r in a block of stride %r, which is not supported'
+                                  % (name, tuple(dcn.stride), st))
+    check_deform(dcn.weight, dcn.stride, dcn.padding, dcn.dilation, dcn.deformable_groups, 'dcn_bottleneck %s.conv2' % name)
+    com = dcn.conv_offset_mask
+    if (tuple(com.kernel_size), tuple(com.stride), tuple(com.padding), tuple(com.dilation), com.groups, com.bias is None,
+            com.out_channels) != ((3, 3), (st, st), (1, 1), (1, 1), 1, False, 27):
+        raise NotImplementedError('yolact_amd dcn_bottleneck: %s.conv2.conv_offset_mask = %r is not supported (a biased 3 x 3 / '
+                                  'stride %d / padding 1 convolution to 27 channels is)' % (name, com, st))
+    check_plain(com.weight, st, 'dcn_bottleneck %s.conv2.conv_offset_mask' % name)
+
+
+def dcn_bottleneck(x, block, batch_stats=None):
+    """backbone.py:37-57 on NHWC x for a block whose conv2 is a DCN (dcn_v2.py:97-128): relu(bn1(conv1 x)); om = conv_offset_mask of
+    that map; relu(bn2(deform_conv(., om))); relu(bn3(conv3 .) + (downsample(x) or x))."""
+    L.require_cuda(x, 'dcn_bottleneck x')
+    check_dcn_bottleneck(block)
+    dcn = block.conv2
+    com = dcn.conv_offset_mask
+    out = batch_norm_act(conv2d_plain(x, block.conv1.weight), block.bn1, batch_stats, relu=True)
+    om = conv2d_act(out, com.weight, com.bias, 1) if block.stride == 1 else conv2d_down(out, com.weight, com.bias)
+    out = deform_conv(out, om, dcn.weight, dcn.bias, block.stride)
+    out = batch_norm_act(out, block.bn2, batch_stats, relu=True)
     out = conv2d_plain(out, block.conv3.weight)
     res = x
     if block.downsample is not None:

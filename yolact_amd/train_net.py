@@ -71,12 +71,14 @@ def stem(net, x_nchw, batch_stats=None):
 
 
 def backbone(net, x, batch_stats=None):
-    """The ResNet stages behind the stem (backbone.py:135-142) -> one output per stage."""
+    """The ResNet stages behind the stem (backbone.py:135-142) -> one output per stage.  A DCN block (use_dcn = True, the YOLACT++
+    configs) runs through TO.dcn_bottleneck: the Yolact methods still refuse such a model in _check_backbone, so only a caller of
+    this module reaches it."""
     outs = []
     with torch.cuda.device(x.device):
         for layer in net.backbone.layers:
             for block in layer:
-                x = TO.bottleneck(x, block, batch_stats)
+                x = (TO.dcn_bottleneck if getattr(block, 'use_dcn', False) else TO.bottleneck)(x, block, batch_stats)
             # an alias made HERE, before the next stage exists: autograd runs its node after the next stage's, so what comes back
             # through a stage's output (the FPN's lateral) is added to that map's gradient last, with or without a layout change
             # between the stages.  forward() and the chain of Yolact's four methods then give the same gradient bits.
@@ -145,6 +147,9 @@ def heads(net, feats):
 
 
 def forward(net, x_nchw, batch_stats=None):
-    """The image batch [B,3,H,W] -> pred_outs, without a layout change between the stages."""
+    """The image batch [B,3,H,W] -> pred_outs, without a layout change between the stages.  Writes cfg._tmp_img_h / _w (the image
+    size the criterion reads, yolact.py:566-567) as Yolact.forward_train does, so a caller that comes here directly needs no method
+    of Yolact."""
+    net.cfg._tmp_img_h, net.cfg._tmp_img_w = int(x_nchw.shape[2]), int(x_nchw.shape[3])
     outs = backbone(net, stem(net, x_nchw, batch_stats), batch_stats)
     return heads(net, fpn(net, [outs[i] for i in net.cfg.backbone.selected_layers]))

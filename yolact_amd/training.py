@@ -48,9 +48,11 @@ class Trainer:
     """One training iteration per step().  Defaults: MultiBoxLoss, or MultiBoxLossPlus under cfg.use_maskiou, with the config's
     thresholds (train.py:217-220); optim.SGD over net.parameters() with cfg.lr, cfg.momentum and cfg.decay (train.py:215-216);
     batch_stats = not cfg.freeze_bn, and under cfg.freeze_bn the BatchNorm affine parameters stop requiring grad (yolact.py:552-553).
-    The config is read when the Trainer is made and at every step."""
+    The config is read when the Trainer is made and at every step.  forward: a callable (images, batch_stats) -> pred_outs, default
+    net.forward_train; Trainer(net, forward=lambda x, bs: train_net.forward(net, x, bs)) trains a YOLACT++ config, whose DCN blocks
+    Yolact.forward_train still refuses."""
 
-    def __init__(self, net, criterion=None, optimizer=None, batch_stats=None):
+    def __init__(self, net, criterion=None, optimizer=None, batch_stats=None, forward=None):
         cfg = active_cfg()
         self.net = net
         if cfg.freeze_bn:
@@ -62,6 +64,7 @@ class Trainer:
                 from .layers.modules.multibox_loss import MultiBoxLoss as Loss
             criterion = Loss(cfg.num_classes, cfg.positive_iou_threshold, cfg.negative_iou_threshold, cfg.ohem_negpos_ratio)
         self.criterion = criterion
+        self.forward = forward                               # None: net.forward_train, looked up at every step
         if optimizer is None:
             optimizer = SGD(net.parameters(), lr=cfg.lr, momentum=cfg.momentum, weight_decay=cfg.decay)
             optimizer.name_parameters(net.named_parameters())
@@ -76,7 +79,7 @@ class Trainer:
         synchronised.  In train.py's order: the learning rate of this iteration, forward, criterion, the sum, backward, the guarded
         update (which zeroes the gradients for the next iteration), iteration += 1."""
         set_lr(self.optimizer, lr_at(self.iteration, active_cfg(), self.lr, self.gamma))
-        preds = self.net.forward_train(images, self.batch_stats)
+        preds = (self.net.forward_train if self.forward is None else self.forward)(images, self.batch_stats)
         losses = self.criterion(self.net, preds, targets, masks, num_crowds)
         loss = sum(losses.values())
         loss.backward()
