@@ -1167,8 +1167,9 @@ enum {
   YMI_WS_BN = 25,               /* desc: ymi_bn_desc, npos / C read -> its ws: 2 * chunks * C + 2 * C floats, chunks = ceil(npos / max(32,
                                  * ceil(npos / 1024))), each part padded to 16 */
   YMI_WS_STEM_WGRAD = 26,       /* desc: ymi_stem_wgrad_desc, the shape read -> its ws: chunks * 147 * Cout floats, padded to 16 */
-  YMI_WS_AUGMENT = 27           /* desc: ymi_augment_desc, B / n_masks read -> its ws: B records, n_masks (image, instance) pairs and B
+  YMI_WS_AUGMENT = 27,          /* desc: ymi_augment_desc, B / n_masks read -> its ws: B records, n_masks (image, instance) pairs and B
                                  * pairs of resize scales, B * sizeof(ymi_augment_rec) + 8 n_masks + 16 B bytes, each part padded to 16 */
+  YMI_WS_PRECONV_WGRAD = 28     /* desc: ymi_preconv_wgrad_desc, the shape read -> its ws: chunks * 27 * Cout floats, padded to 16 */
 };
 typedef struct { int32_t A, B; int64_t n; } ymi_mask_iou_shape;
 typedef struct { int32_t N, h, w, cap; } ymi_rle_shape;      /* cap <= 0: the safe capacity h*w + 1 */
@@ -1227,6 +1228,50 @@ int ymi_calib_l2_read(const float *src, long n_floats, int blocks, int iters, fl
 /* one lane follows i = chain[i] from `start` for `hops` dependent loads and stores where it ended in out[0]; the caller lays the
  * permutation (one entry per 128-byte line over the footprint to probe) and divides its event time by hops: load-to-use latency. */
 int ymi_calib_latency(const int32_t *chain, long n, int start, int hops, int32_t *out, void *stream);
+
+/* -- the train-mode DarkNet53 backbone (csrc/bn_train.hip, csrc/darknet_train.hip; additive, the ABI number stays) ----------------------
+ * backbone.py:222-294: every layer is a bias-free convolution, BatchNorm2d, LeakyReLU(0.1); a DarkNetBlock is conv2(conv1(x)) + x.  The
+ * convolutions of 32 .. 1024 input channels run on ymi_conv2d_nhwc_f32 / ymi_conv_wgrad_nhwc_f32 / ymi_conv_dgrad_s2_nhwc_f32; the
+ * pre-convolution's forward is ymi_conv2d_nhwc_f32 with Cin = 4.  No atomics; every element of every output is written exactly once;
+ * the same inputs give the same bits.
+ *
+ * ymi_bn_leaky_fwd_nhwc_f32 / ymi_bn_leaky_bwd_nhwc_f32: ymi_bn_fwd_nhwc_f32 / ymi_bn_bwd_nhwc_f32 (same descriptor, same workspace, same
+ * statistics, mean / invstd, running update, two-pass variance and COLUMN SUMS) with LeakyReLU(0.1) and the residual BEHIND it:
+ *     z = gamma (x - mean) invstd + beta;  a = z > 0 ? z : 0.1f * z (one fp32 multiply);  y = a + res, or a when res is NULL
+ *     gh = z > 0 ? dy : 0.1f * dy;  dbeta, dgamma and dx from gh by ymi_bn_bwd_nhwc_f32's formulas, chunks and order of additions.
+ * d_res is dy itself: no kernel writes it, and d->d_res must be NULL.  d->relu must be 0.
+ * THE SLOPE DECISION z > 0 is made once, by the forward.  Without a residual y > 0 is exactly z > 0 and the backward reads it from
+ * d->y (pass mask = NULL to both).  With a residual the forward writes it to `mask`, ceil(npos C / 32) uint32 words, 16-byte aligned: bit
+ * (i & 31) of word i >> 5 belongs to element i of the [npos, C] map, the bits past the last element are 0, every word is written exactly
+ * once.  The backward given that mask reads the bit (and not d->y); z is never computed a second time.  The forward writes a mask
+ * whenever one is given.  With gamma = beta = 0 every z is 0 and gh is 0.1f * dy, as in PyTorch.
+ * Errors as for the plain pair, and: YMI_EARG: relu != 0, d_res != NULL (backward); YMI_ENULL: res without a mask (forward), neither a
+ * mask nor y (backward); YMI_ESHAPE: a mask not 16-byte aligned.  No error path launches anything. */
+int ymi_bn_leaky_fwd_nhwc_f32(const ymi_bn_desc *d, uint32_t *mask, void *stream);
+int ymi_bn_leaky_bwd_nhwc_f32(const ymi_bn_desc *d, const uint32_t *mask, void *stream);
+
+/* ymi_preconv_wgrad_nhwc_f32: dw[k,co] = sum_pos x[n, oy + ky - 1, ox + kx - 1, ci] g[pos,co], k = (ky*3 + kx)*3 + ci (27 rows),
+ * pos = [n, oy, ox] over the B H W positions of g (3x3 / stride 1 / pad 1), any H, W >= 1, reads outside the image are 0.  x is the
+ * NHWC-4 image the forward's Cin-4 loader reads; its channel 3 is padding, is never addressed and reaches no row of dw WHATEVER IT
+ * HOLDS; taps outside the image and positions past a chunk are masked by a select, never by a product.  On v_mfma_f32_32x32x2_f32
+ * (fp32 in, fp32 accumulate) with the positions as its k index and the 27 rows as rows 0 .. 26 of one 32-row tile.  No data gradient:
+ * nothing upstream of the image needs one.
+ * SUMMATION ORDER (part of the contract, a function of the shape only): the positions n-major, then oy, then ox, are cut into chunks of
+ * per = 32 ceil(ceil(P / 32) / min(ceil(P / 32), ceil(2048 / (Cout / 32)))) positions, P = B H W.  A chunk's partial sum starts from
+ * +0.0 and takes its positions in ascending order two at a time: one instruction adds the two products of positions p and p + 1
+ * (p - chunk start even; a tap outside the image or a position past the chunk contributes an exact 0 product).  The partials go to ws
+ * and a second launch adds them in chunk order from +0.0.
+ * YMI_ENULL: the descriptor, x, g, dw or ws NULL; YMI_EARG: B, H, W or Cout < 1; YMI_ESHAPE: Cout % 32, ldg < Cout, ldg % 4, x or g of
+ * 2^29 elements or more, ws not 16-byte aligned, ws_bytes too small.  No error path launches anything. */
+typedef struct ymi_preconv_wgrad_desc {
+  const float *x;               /* [B,H,W,4] */
+  const float *g;               /* [B,H,W,ldg], channels [0, Cout) are read */
+  float *dw;                    /* [27, Cout] */
+  void *ws;                     /* ymi_workspace_bytes(YMI_WS_PRECONV_WGRAD, desc) bytes, 16-byte aligned */
+  int64_t ws_bytes;
+  int32_t B, H, W, Cout, ldg, _pad0;
+} ymi_preconv_wgrad_desc;
+int ymi_preconv_wgrad_nhwc_f32(const ymi_preconv_wgrad_desc *d, void *stream);
 
 /* -- profiling hooks -------------------------------------------------------------------- */
 /* When enabled, every conv launch is bracketed by hipEvents on its stream; ymi_prof_read returns

@@ -212,6 +212,12 @@ class StemWgradDesc(C.Structure):
                 ('B', C.c_int32), ('H', C.c_int32), ('W', C.c_int32), ('Cout', C.c_int32), ('ldg', C.c_int32), ('_pad0', C.c_int32)]
 
 
+class PreconvWgradDesc(C.Structure):
+    """include/yolact_amd.h ymi_preconv_wgrad_desc."""
+    _fields_ = [('x', C.c_void_p), ('g', C.c_void_p), ('dw', C.c_void_p), ('ws', C.c_void_p), ('ws_bytes', C.c_int64),
+                ('B', C.c_int32), ('H', C.c_int32), ('W', C.c_int32), ('Cout', C.c_int32), ('ldg', C.c_int32), ('_pad0', C.c_int32)]
+
+
 # ymi_augment_rec.flags (include/yolact_amd.h YMI_AUG_*)
 AUG_PHOTOMETRIC, AUG_BRIGHTNESS, AUG_CONTRAST, AUG_CONTRAST_LAST, AUG_SATURATION, AUG_HUE, AUG_MIRROR, AUG_SRC_F32 = (
     1, 2, 4, 8, 16, 32, 64, 128)
@@ -351,7 +357,7 @@ class RleShape(C.Structure):
 (WS_WINO_V, WS_WINO_M, WS_SPLITK, WS_MASK_IOU, WS_JPEG_COEFS, WS_JPEG_PLANES, WS_DETECT_SCORES_T, WS_DETECT_PER_PRIOR,
  WS_DETECT_CAND, WS_DETECT_REC, WS_AMAX_SLOT, WS_RLE_COUNTS, WS_DETECT_GREEDY, WS_JPEG_ENC, WS_JPEG_ENC_OUT,
  WS_MASK_LOSS, WS_MATCH, WS_BOX_LOSS, WS_CLASS_LOSS, WS_SEGM_LOSS, WS_MASKIOU_INPUT, WS_CONV_BWD, WS_MASKIOU_HEAD,
- WS_CONV_WGRAD, WS_BN, WS_STEM_WGRAD, WS_AUGMENT) = range(1, 28)
+ WS_CONV_WGRAD, WS_BN, WS_STEM_WGRAD, WS_AUGMENT, WS_PRECONV_WGRAD) = range(1, 29)
 
 EFORMAT, EUNSUPPORTED = -4, -5
 UP_FLAT, UP_BAND, UP_ROWS16, UP_ROWS32 = 1, 2, 3, 4       # ymi_mask_upsample_kernel (include/yolact_amd.h YMI_UP_*)
@@ -404,6 +410,9 @@ SYMBOLS = [
     ('ymi_bn_fwd_nhwc_f32', C.c_int, [C.POINTER(BnDesc), _P]),
     ('ymi_bn_bwd_nhwc_f32', C.c_int, [C.POINTER(BnDesc), _P]),
     ('ymi_stem_wgrad_nhwc_f32', C.c_int, [C.POINTER(StemWgradDesc), _P]),
+    ('ymi_bn_leaky_fwd_nhwc_f32', C.c_int, [C.POINTER(BnDesc), _P, _P]),
+    ('ymi_bn_leaky_bwd_nhwc_f32', C.c_int, [C.POINTER(BnDesc), _P, _P]),
+    ('ymi_preconv_wgrad_nhwc_f32', C.c_int, [C.POINTER(PreconvWgradDesc), _P]),
     ('ymi_maxpool_fwd_nhwc_f32', C.c_int, [_P, _P, _I, _I, _I, _I, _P]),
     ('ymi_maxpool_bwd_nhwc_f32', C.c_int, [_P, _P, _P, _I, _I, _I, _I, _P]),
     ('ymi_bilinear_bwd_nhwc_f32', C.c_int, [_P, _P, _P] + [_I] * 7 + [_P]),

@@ -1,5 +1,6 @@
 // Shared by the train-mode gradient kernels on the exact-fp32 matrix instruction v_mfma_f32_32x32x2_f32 (fp32 in, fp32 accumulate):
-// conv_train.hip (wgrad_k), stem_train.hip (stem_wgrad_k), dcn_bwd.hip, and by reference conv_dgrad.hip.
+// conv_train.hip (wgrad_k), stem_train.hip (stem_wgrad_k), darknet_train.hip (preconv_wgrad_k), dcn_bwd.hip, and by reference
+// conv_dgrad.hip.
 //
 // STRUCTURE of a weight gradient dw[k,co] = sum_pos a[pos,k] g[pos,co].  The POSITIONS are the instruction's k index, so both operands
 // are read in their natural NHWC layout: lane & 31 = the row (of a) or column (of g), the two halves of a wave = two consecutive

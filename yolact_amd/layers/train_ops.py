@@ -1,5 +1,5 @@
-"""Differentiable building blocks of the train-mode heads, protonet, FPN, ResNet stages and ResNet stem on the HIP kernels
-(csrc/conv_train.hip, csrc/conv_dgrad.hip, csrc/bn_train.hip, csrc/stem_train.hip and the conv engine).
+"""Differentiable building blocks of the train-mode heads, protonet, FPN, ResNet stages, ResNet stem and DarkNet backbone on the HIP
+kernels (csrc/conv_train.hip, csrc/conv_dgrad.hip, csrc/bn_train.hip, csrc/stem_train.hip, csrc/darknet_train.hip and the conv engine).
 
     conv2d_act(x, weight, bias, padding, act)            -> y [B,H,W,Cout]: act(conv(x, weight) + bias), act in {None, 'relu', 'tanh'}
     conv2d_multi(x, [(weight, bias, act), ..], padding)  -> one y per entry: up to three convolutions of the SAME input as one launch
@@ -19,6 +19,12 @@
     stem_conv(x4, weight)                                -> [B,Ho,Wo,Cout]: the stem's 7x7 / stride 2 / padding 3 convolution of 3 channels
                                                             (backbone.py:77) on the image padded to 4 channels, x4 [B,H,W,4]
     max_pool_3x3_s2(x)                                   -> [B,Hp,Wp,C]: F.max_pool2d(x, 3, 2, 1) (backbone.py:80)
+    batch_norm_leaky(x, bn, batch_stats, residual)       -> leaky_relu(bn(x), 0.1) + residual: the residual BEHIND the activation
+    preconv(x4, weight)                                  -> [B,H,W,Cout]: DarkNet's 3x3 / stride 1 / padding 1 convolution of 3 channels
+                                                            (backbone.py:268) on the image padded to 4 channels, x4 [B,H,W,4]
+    dark_unit(x, seq, batch_stats, residual)             -> a DarkNet unit, Sequential(conv, BatchNorm2d, LeakyReLU(0.1)): conv2d_plain,
+                                                            then batch_norm_leaky
+    dark_block(x, block, batch_stats)                    -> a modules.DarkNetBlock (backbone.py:235-247): conv2(conv1(x)) + x
 
 x and the results are NHWC fp32 GPU tensors; weight and bias are nn.Conv2d parameters in torch layout.  Everything is once
 differentiable in x, every weight and every bias.  Each call packs its filters from the CURRENT parameter values (a permute; no
@@ -51,6 +57,10 @@ is ymi_stem_wgrad_nhwc_f32 on the SAME x4 (its fourth channel reaches nothing), 
 only: an x4 that requires grad raises, since nothing upstream of the image needs a gradient and returning None would silently give a
 zero one.  max_pool_3x3_s2: ymi_maxpool_fwd_nhwc_f32 / ymi_maxpool_bwd_nhwc_f32 (csrc/stem_train.hip); the backward recomputes each
 window's argmax from the saved input, the first of equal maxima in row-major window order taking the gradient as in PyTorch.
+batch_norm_leaky: ymi_bn_leaky_fwd_nhwc_f32 / ymi_bn_leaky_bwd_nhwc_f32 (csrc/bn_train.hip).  The slope decision z > 0 is the forward's:
+without a residual the backward reads it from y, with one from the bit mask the forward wrote (1/32 of the map, saved beside y); the
+residual's gradient is the incoming one.  preconv: stem_conv's scheme at 3x3 / stride 1; the backward is ymi_preconv_wgrad_nhwc_f32
+(csrc/darknet_train.hip).  check_darknet names what of a DarkNetBackbone these do not take.
 """
 from __future__ import annotations
 
@@ -531,42 +541,130 @@ class BnAct(torch.autograd.Function):
         return (None,) * 6 + tuple(None if (t is None or dt is None) else t.to(dt) for t, dt in zip(out, ctx.dtypes))
 
 
-def batch_norm_act(x, bn, batch_stats=None, residual=None, relu=False):
-    """relu(bn(x) + residual) on NHWC x for an nn.BatchNorm2d `bn`.  batch_stats None follows bn.training; True: the batch statistics
-    (running_mean / running_var updated in place, num_batches_tracked incremented); False: the running statistics (frozen)."""
-    L.require_cuda(x, 'batch_norm_act x')
+def _check_bn(who, x, bn, batch_stats, residual):
+    """What batch_norm_act and batch_norm_leaky refuse, named -> whether the batch statistics are used."""
+    L.require_cuda(x, who + ' x')
     if not isinstance(bn, torch.nn.BatchNorm2d):
-        raise NotImplementedError('yolact_amd batch_norm_act: a %s is not supported (an nn.BatchNorm2d is)' % type(bn).__name__)
+        raise NotImplementedError('yolact_amd %s: a %s is not supported (an nn.BatchNorm2d is)' % (who, type(bn).__name__))
     if not bn.affine:
-        raise NotImplementedError('yolact_amd batch_norm_act: affine = False is not supported')
+        raise NotImplementedError('yolact_amd %s: affine = False is not supported' % who)
     if not bn.track_running_stats:
-        raise NotImplementedError('yolact_amd batch_norm_act: track_running_stats = False is not supported')
+        raise NotImplementedError('yolact_amd %s: track_running_stats = False is not supported' % who)
     if bn.momentum is None:
-        raise NotImplementedError('yolact_amd batch_norm_act: momentum = None (a cumulative average) is not supported')
+        raise NotImplementedError('yolact_amd %s: momentum = None (a cumulative average) is not supported' % who)
     stats = bool(bn.training if batch_stats is None else batch_stats)
     Cc = int(bn.num_features)
     if x.dim() < 2 or x.shape[-1] != Cc or Cc % 4 != 0:
-        raise NotImplementedError('yolact_amd batch_norm_act: x %s for %d features is not supported ([..,C] with C %% 4 == 0 is)'
-                                  % (tuple(x.shape), Cc))
+        raise NotImplementedError('yolact_amd %s: x %s for %d features is not supported ([..,C] with C %% 4 == 0 is)'
+                                  % (who, tuple(x.shape), Cc))
     if residual is not None:
-        L.require_cuda(residual, 'batch_norm_act residual')
+        L.require_cuda(residual, who + ' residual')
         if residual.shape != x.shape:
-            raise ValueError('batch_norm_act: residual %s for x %s' % (tuple(residual.shape), tuple(x.shape)))
+            raise ValueError('%s: residual %s for x %s' % (who, tuple(residual.shape), tuple(x.shape)))
     if stats and x.numel() // Cc < 2:
-        raise NotImplementedError('yolact_amd batch_norm_act: batch statistics over npos = %d values per channel are not supported '
-                                  '(more than one is; PyTorch refuses it too)' % (x.numel() // Cc))
-    L.require_cuda(bn.weight, 'batch_norm_act bn.weight')
+        raise NotImplementedError('yolact_amd %s: batch statistics over npos = %d values per channel are not supported '
+                                  '(more than one is; PyTorch refuses it too)' % (who, x.numel() // Cc))
+    L.require_cuda(bn.weight, who + ' bn.weight')
     for t in (bn.running_mean, bn.running_var):
         if t.dtype != torch.float32 or not t.is_contiguous() or t.device != x.device:
-            raise NotImplementedError('yolact_amd batch_norm_act: running statistics that are not contiguous fp32 on the device of x '
-                                      'are not supported')
+            raise NotImplementedError('yolact_amd %s: running statistics that are not contiguous fp32 on the device of x '
+                                      'are not supported' % who)
+    return stats
+
+
+def _bn_stats_written(bn):
+    """After a launch with batch statistics: what nn.BatchNorm2d itself does to its buffers besides the values."""
+    with torch.no_grad():
+        bn.num_batches_tracked += 1
+    for t in (bn.running_mean, bn.running_var):            # written by the kernel: tell autograd's version check, as an in-place op does
+        torch.autograd.graph.increment_version(t)
+
+
+def batch_norm_act(x, bn, batch_stats=None, residual=None, relu=False):
+    """relu(bn(x) + residual) on NHWC x for an nn.BatchNorm2d `bn`.  batch_stats None follows bn.training; True: the batch statistics
+    (running_mean / running_var updated in place, num_batches_tracked incremented); False: the running statistics (frozen)."""
+    stats = _check_bn('batch_norm_act', x, bn, batch_stats, residual)
     y = BnAct.apply(stats, bool(relu), float(bn.eps), float(bn.momentum), bn.running_mean, bn.running_var, x, residual, bn.weight,
                     bn.bias)
     if stats:
-        with torch.no_grad():
-            bn.num_batches_tracked += 1
-        for t in (bn.running_mean, bn.running_var):        # written by the kernel: tell autograd's version check, as an in-place op does
-            torch.autograd.graph.increment_version(t)
+        _bn_stats_written(bn)
+    return y
+
+
+LEAKY_SLOPE = 0.1
+
+
+class BnLeaky(torch.autograd.Function):
+    """apply(stats, eps, momentum, running_mean, running_var, x [..,C], residual or None, gamma, beta) -> leaky_relu(bn(x), 0.1) +
+    residual (ymi_bn_leaky_fwd_nhwc_f32 / ymi_bn_leaky_bwd_nhwc_f32).  With a residual the forward's decisions z > 0 are kept as a bit
+    mask (1/32 of the map) and the backward reads them; without one it reads them from y."""
+
+    @staticmethod
+    def forward(ctx, stats, eps, momentum, rmean, rvar, x, residual, gamma, beta):
+        dev = x.device
+        with torch.cuda.device(dev), torch.no_grad():
+            xd = LC.f32(x, dev)
+            Cc = xd.shape[-1]
+            npos = xd.numel() // Cc
+            y = torch.empty_like(xd)
+            mean = torch.empty(Cc, dtype=torch.float32, device=dev)
+            invstd = torch.empty(Cc, dtype=torch.float32, device=dev)
+            rd = None if residual is None else LC.f32(residual, dev)
+            mask = None if residual is None else torch.empty((xd.numel() + 31) // 32, dtype=torch.int32, device=dev)
+            gd, bd = LC.f32(gamma, dev), LC.f32(beta, dev)
+            d = L.BnDesc()
+            d.x, d.res, d.gamma, d.beta = xd.data_ptr(), (None if rd is None else rd.data_ptr()), gd.data_ptr(), bd.data_ptr()
+            d.running_mean, d.running_var = rmean.data_ptr(), rvar.data_ptr()
+            d.y, d.mean, d.invstd = y.data_ptr(), mean.data_ptr(), invstd.data_ptr()
+            d.npos, d.C, d.training, d.relu, d.eps, d.momentum = npos, Cc, int(stats), 0, eps, momentum
+            ws = LC.workspace('BN', d, dev)
+            d.ws_bytes = ws.numel()
+            L.check(L.lib().ymi_bn_leaky_fwd_nhwc_f32(C.byref(d), None if mask is None else mask.data_ptr(), L.stream_ptr()),
+                    'ymi_bn_leaky_fwd_nhwc_f32')
+        # the inputs are saved too: autograd's version check refuses a backward after x or a parameter was edited in place
+        ctx.save_for_backward(x, gamma, beta, y, mean, invstd, *(() if residual is None else (residual, mask)))
+        ctx.stats, ctx.eps = int(stats), eps
+        ctx.dtypes = [x.dtype, None if residual is None else residual.dtype, gamma.dtype, beta.dtype]
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        want_x, want_r, want_g, want_b = ctx.needs_input_grad[5:]
+        x, gamma, beta, y, mean, invstd = ctx.saved_tensors[:6]      # (the version check)
+        mask = ctx.saved_tensors[7] if len(ctx.saved_tensors) > 6 else None
+        if not (want_x or want_r or want_g or want_b):
+            return (None,) * 9
+        dev = x.device
+        with torch.cuda.device(dev), torch.no_grad():
+            xd, dyd, gd = LC.f32(x, dev), LC.f32(dy, dev), LC.f32(gamma, dev)
+            Cc = xd.shape[-1]
+            dx = torch.empty_like(xd) if want_x else None
+            dg = torch.empty(Cc, dtype=torch.float32, device=dev) if want_g else None
+            db = torch.empty(Cc, dtype=torch.float32, device=dev) if want_b else None
+            if dx is not None or dg is not None or db is not None:
+                d = L.BnDesc()
+                d.x, d.gamma, d.y, d.mean, d.invstd, d.dy = (xd.data_ptr(), gd.data_ptr(), y.data_ptr(), mean.data_ptr(),
+                                                             invstd.data_ptr(), dyd.data_ptr())
+                d.dx, d.dgamma, d.dbeta = (None if t is None else t.data_ptr() for t in (dx, dg, db))
+                d.npos, d.C, d.training, d.relu, d.eps = xd.numel() // Cc, Cc, ctx.stats, 0, ctx.eps
+                ws = LC.workspace('BN', d, dev)
+                d.ws_bytes = ws.numel()
+                L.check(L.lib().ymi_bn_leaky_bwd_nhwc_f32(C.byref(d), None if mask is None else mask.data_ptr(), L.stream_ptr()),
+                        'ymi_bn_leaky_bwd_nhwc_f32')
+            # the residual is added behind the activation: its gradient is dy itself
+            dres = dyd if want_r else None
+        out = [dx, dres, dg, db]
+        return (None,) * 5 + tuple(None if (t is None or dt is None) else t.to(dt) for t, dt in zip(out, ctx.dtypes))
+
+
+def batch_norm_leaky(x, bn, batch_stats=None, residual=None):
+    """leaky_relu(bn(x), 0.1) + residual on NHWC x for an nn.BatchNorm2d `bn`: the residual is added AFTER the activation (a
+    DarkNetBlock's `conv2(conv1(x)) + x`).  batch_stats as in batch_norm_act."""
+    stats = _check_bn('batch_norm_leaky', x, bn, batch_stats, residual)
+    y = BnLeaky.apply(stats, float(bn.eps), float(bn.momentum), bn.running_mean, bn.running_var, x, residual, bn.weight, bn.bias)
+    if stats:
+        _bn_stats_written(bn)
     return y
 
 
@@ -892,3 +990,164 @@ def max_pool_3x3_s2(x):
     if x.dim() != 4 or x.shape[3] % 4 != 0 or min(x.shape) < 1:
         raise NotImplementedError('yolact_amd max_pool_3x3_s2: x %s is not supported ([B,H,W,C] with C %% 4 == 0 is)' % (tuple(x.shape),))
     return MaxPool3x3S2.apply(x)
+
+
+PRE_K, PRE_PAD, PRE_STRIDE = 3, 1, 1
+
+
+def check_preconv(weight, stride=1, padding=1, dilation=1, groups=1, bias=None, who='preconv'):
+    """NotImplementedError naming what of DarkNet's pre-convolution the kernels do not take: anything but a bias-free 3 x 3 / stride 1 /
+    padding 1 / dilation 1 / groups 1 convolution of 3 input channels to a multiple of 32 output channels."""
+    if weight.dim() != 4:
+        raise NotImplementedError('yolact_amd %s: a weight of shape %s is not supported ([Cout,3,3,3] is)' % (who, tuple(weight.shape)))
+    Cout, Cin, kh, kw = weight.shape
+    if (kh, kw) != (PRE_K, PRE_K):
+        raise NotImplementedError('yolact_amd %s: a %d x %d kernel is not supported (3 x 3 is)' % (who, kh, kw))
+    if isinstance(stride, str) or _pair(stride) != (PRE_STRIDE, PRE_STRIDE):
+        raise NotImplementedError('yolact_amd %s: stride = %r is not supported (stride 1 is)' % (who, stride))
+    if isinstance(padding, str) or _pair(padding) != (PRE_PAD, PRE_PAD):
+        raise NotImplementedError('yolact_amd %s: padding = %r is not supported (padding 1 is)' % (who, padding))
+    if _pair(dilation) != (1, 1):
+        raise NotImplementedError('yolact_amd %s: dilation = %r is not supported (dilation 1 is)' % (who, dilation))
+    if groups != 1:
+        raise NotImplementedError('yolact_amd %s: groups = %r is not supported (groups 1 is)' % (who, groups))
+    if Cin != 3:
+        raise NotImplementedError('yolact_amd %s: Cin = %d is not supported (3 input channels are, on an input padded to 4)' % (who, Cin))
+    if bias is not None:
+        raise NotImplementedError('yolact_amd %s: a bias is not supported (a bias-free convolution is)' % who)
+    if Cout % 32 != 0:
+        raise NotImplementedError('yolact_amd %s: Cout = %d is not supported (a multiple of 32 output channels is)' % (who, Cout))
+
+
+def _pack_preconv(w):
+    """[Cout,3,3,3] -> [ceil128(Cout)][64], k = (ky*3 + kx)*4 + c with c = 3 and k >= 36 zero (a permute of the CURRENT values)."""
+    Cout = int(w.shape[0])
+    out = torch.zeros(_ceil(Cout, 128), _ceil(PRE_K * PRE_K * 4, 32), dtype=torch.float32, device=w.device)
+    out[:Cout, :PRE_K * PRE_K * 4] = F.pad(w.permute(0, 2, 3, 1), (0, 1)).reshape(Cout, PRE_K * PRE_K * 4)
+    return out
+
+
+class PreConv(torch.autograd.Function):
+    """apply(x4 [B,H,W,4], weight [Cout,3,3,3]) -> [B,H,W,Cout]; differentiable in the weight."""
+
+    @staticmethod
+    def forward(ctx, x4, weight):
+        dev = x4.device
+        Cout = int(weight.shape[0])
+        with torch.cuda.device(dev), torch.no_grad():
+            xd = LC.f32(x4, dev)
+            B, H, W, _ = xd.shape
+            y = torch.empty(B, H, W, Cout, dtype=torch.float32, device=dev)
+            _engine_conv(xd, 4, _pack_preconv(weight.detach().float()), None, 4, Cout, PRE_K, PRE_PAD, [(0, Cout, L.ACT_NONE, y)],
+                         stride=PRE_STRIDE)
+        ctx.save_for_backward(x4, weight)                   # (the version check)
+        ctx.dtype = weight.dtype
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        x4, weight = ctx.saved_tensors                      # (the version check)
+        if not ctx.needs_input_grad[1]:
+            return None, None
+        dev = x4.device
+        Cout = int(weight.shape[0])
+        with torch.cuda.device(dev), torch.no_grad():
+            xd, g = LC.f32(x4, dev), LC.f32(dy, dev)
+            B, H, W, _ = xd.shape
+            dw = torch.empty(PRE_K * PRE_K * 3, Cout, dtype=torch.float32, device=dev)
+            d = L.PreconvWgradDesc()
+            d.x, d.g, d.dw = xd.data_ptr(), g.data_ptr(), dw.data_ptr()
+            d.B, d.H, d.W, d.Cout, d.ldg = B, H, W, Cout, Cout
+            ws = LC.workspace('PRECONV_WGRAD', d, dev)
+            d.ws_bytes = ws.numel()
+            L.check(L.lib().ymi_preconv_wgrad_nhwc_f32(C.byref(d), L.stream_ptr()), 'ymi_preconv_wgrad_nhwc_f32')
+            out = _unpack_dw(dw, PRE_K, 3)
+        return None, out.to(ctx.dtype)
+
+
+def preconv(x4, weight, bias=None, stride=1, padding=1, dilation=1, groups=1):
+    """conv2d(x, weight, None, stride 1, padding 1) for a [Cout,3,3,3] weight (DarkNet's _preconv, backbone.py:268) on x4 [B,H,W,4], the
+    NHWC image with a fourth channel of zeros -> NHWC.  Differentiable in the weight only, like stem_conv."""
+    L.require_cuda(x4, 'preconv x4')
+    L.require_cuda(weight, 'preconv weight')
+    check_preconv(weight, stride, padding, dilation, groups, bias)
+    if x4.dim() != 4 or x4.shape[3] != 4:
+        raise ValueError('preconv: x4 %s ([B,H,W,4], the image padded to 4 channels, is expected)' % (tuple(x4.shape),))
+    if x4.requires_grad:
+        raise NotImplementedError('yolact_amd preconv: an x4 that requires grad is not supported (the gradient with respect to the '
+                                  'image is not computed; detach it)')
+    return PreConv.apply(x4, weight)
+
+
+def _check_unit(seq, who, name):
+    """A DarkNet unit: Sequential(bias-free Conv2d, BatchNorm2d, LeakyReLU(0.1)) -> (conv, bn); anything else is refused by name."""
+    mods = list(seq) if isinstance(seq, torch.nn.Sequential) else None
+    if mods is None or len(mods) != 3 or not isinstance(mods[0], torch.nn.Conv2d) or not isinstance(mods[1], torch.nn.BatchNorm2d) \
+            or not isinstance(mods[2], torch.nn.LeakyReLU):
+        raise NotImplementedError('yolact_amd %s: %s = %r is not supported (a Sequential of Conv2d, BatchNorm2d, LeakyReLU(0.1) is)'
+                                  % (who, name, seq))
+    if mods[2].negative_slope != LEAKY_SLOPE:
+        raise NotImplementedError('yolact_amd %s: %s has negative_slope = %r, which is not supported (0.1 is)'
+                                  % (who, name, mods[2].negative_slope))
+    conv = mods[0]
+    if conv.bias is not None:
+        raise NotImplementedError('yolact_amd %s: %s.0 has a bias, which is not supported (a bias-free convolution is)' % (who, name))
+    if isinstance(conv.padding, str) or tuple(conv.padding) != (conv.kernel_size[0] // 2,) * 2:
+        raise NotImplementedError('yolact_amd %s: %s.0 has padding = %r, which is not supported (padding k // 2 is)'
+                                  % (who, name, conv.padding))
+    if tuple(conv.dilation) != (1, 1) or conv.groups != 1:
+        raise NotImplementedError('yolact_amd %s: %s.0 has dilation = %r / groups = %r, which is not supported (dilation 1 / groups 1 '
+                                  'is)' % (who, name, tuple(conv.dilation), conv.groups))
+    return conv, mods[1]
+
+
+def dark_unit(x, seq, batch_stats=None, residual=None):
+    """A DarkNet unit (backbone.py:222-233's conv, BatchNorm2d, LeakyReLU(0.1)) on NHWC x, + residual behind the activation."""
+    L.require_cuda(x, 'dark_unit x')
+    conv, bn = _check_unit(seq, 'dark_unit', 'seq')
+    check_plain(conv.weight, conv.stride, 'dark_unit seq.0')
+    return batch_norm_leaky(conv2d_plain(x, conv.weight, conv.stride), bn, batch_stats, residual)
+
+
+def _check_dark_block(block, who, name):
+    from .. import modules as M
+    if not isinstance(block, M.DarkNetBlock):
+        raise NotImplementedError('yolact_amd %s: %s is a %s, which is not supported (a DarkNetBlock is)' % (who, name, type(block).__name__))
+    for n, k in (('conv1', 1), ('conv2', 3)):
+        conv, _ = _check_unit(getattr(block, n), who, '%s.%s' % (name, n))
+        if tuple(conv.kernel_size) != (k, k) or tuple(conv.stride) != (1, 1):
+            raise NotImplementedError('yolact_amd %s: %s.%s.0 = %r is not supported (a %d x %d / stride 1 convolution is)'
+                                      % (who, name, n, conv, k, k))
+        check_plain(conv.weight, 1, '%s %s.%s.0' % (who, name, n))
+    if block.conv2[0].out_channels != block.conv1[0].in_channels:
+        raise NotImplementedError('yolact_amd %s: %s maps %d to %d channels, which is not supported (the residual needs equal widths)'
+                                  % (who, name, block.conv1[0].in_channels, block.conv2[0].out_channels))
+
+
+def dark_block(x, block, batch_stats=None):
+    """A DarkNetBlock (backbone.py:235-247) on NHWC x: conv2(conv1(x)) + x, the sum behind conv2's LeakyReLU."""
+    L.require_cuda(x, 'dark_block x')
+    _check_dark_block(block, 'dark_block', 'block')
+    return dark_unit(dark_unit(x, block.conv1, batch_stats), block.conv2, batch_stats, residual=x)
+
+
+def check_darknet(bb, name='backbone'):
+    """NotImplementedError naming what of a DarkNet backbone the kernels do not take."""
+    from .. import modules as M
+    who = 'darknet'
+    if not isinstance(bb, M.DarkNetBackbone):
+        raise NotImplementedError('yolact_amd %s: %s is a %s, which is not supported (a DarkNetBackbone is)' % (who, name, type(bb).__name__))
+    conv, _ = _check_unit(bb._preconv, who, name + '._preconv')
+    check_preconv(conv.weight, conv.stride, conv.padding, conv.dilation, conv.groups, conv.bias, '%s %s._preconv.0' % (who, name))
+    for i, layer in enumerate(bb.layers):
+        mods = list(layer)
+        if not mods:
+            raise NotImplementedError('yolact_amd %s: %s.layers.%d is empty, which is not supported' % (who, name, i))
+        conv, _ = _check_unit(mods[0], who, '%s.layers.%d.0' % (name, i))
+        if tuple(conv.kernel_size) != (3, 3) or tuple(conv.stride) != (2, 2):
+            raise NotImplementedError('yolact_amd %s: %s.layers.%d.0.0 = %r is not supported (a 3 x 3 / stride 2 convolution is)'
+                                      % (who, name, i, conv))
+        check_plain(conv.weight, 2, '%s %s.layers.%d.0.0' % (who, name, i))
+        for j, block in enumerate(mods[1:], 1):
+            _check_dark_block(block, who, '%s.layers.%d.%d' % (name, i, j))

@@ -1,8 +1,8 @@
 """The train-mode network: the reference's TRAIN-mode Yolact.forward (yolact.py:564-647) as plain functions on NHWC fp32 GPU tensors,
 each a sequence of layers/train_ops.py calls (the HIP kernels) and once differentiable like them.  `net` is a Yolact; its plans are not
 touched.  stem (which takes the NCHW image: it builds x4 itself) -> backbone -> fpn (of the selected stages) -> heads; forward is their
-composition.  Nothing here validates: Yolact.forward_stem / .. / forward_train check the model, cfg and the tensors and change the
-layout.  What shows only layer by layer (a make_net or downsample layer the kernels do not take) raises here, named after the Yolact
+composition.  A DarkNetBackbone (yolact_darknet53) goes through darknet in place of stem -> backbone.  Nothing here validates:
+Yolact.forward_stem / .. / forward_train check the model, cfg and the tensors and change the layout.  What shows only layer by layer (a make_net or downsample layer the kernels do not take) raises here, named after the Yolact
 method.  The ORDER of the train_ops calls is part of the contract: autograd adds the gradients of a map's consumers in node order.
 """
 from __future__ import annotations
@@ -86,6 +86,27 @@ def backbone(net, x, batch_stats=None):
     return outs
 
 
+def darknet(net, x_nchw, batch_stats=None):
+    """A DarkNetBackbone (backbone.py:252-294) on the NCHW image -> one output per stage: the image padded to NHWC-4 as in stem, the
+    _preconv unit, then five stages, each a stride-2 unit followed by its DarkNetBlocks.  Yolact's methods refuse a DarkNet, so only
+    a caller of this module (forward, below) reaches it; check_darknet names what the kernels do not take."""
+    bb = net.backbone
+    TO.check_darknet(bb)
+    outs = []
+    with torch.cuda.device(x_nchw.device):
+        x4 = nn.functional.pad(x_nchw.detach().to(torch.float32).permute(0, 2, 3, 1), (0, 1)).contiguous()
+        conv, bn = bb._preconv[0], bb._preconv[1]
+        x = TO.batch_norm_leaky(TO.preconv(x4, conv.weight), bn, batch_stats)
+        for layer in bb.layers:
+            mods = list(layer)
+            x = TO.dark_unit(x, mods[0], batch_stats)
+            for block in mods[1:]:
+                x = TO.dark_block(x, block, batch_stats)
+            # the alias backbone() makes, for its reason: a stage output has two consumers (the next stage and the FPN's lateral)
+            outs.append(x.view_as(x))
+    return outs
+
+
 def fpn(net, feats):
     """FPN.forward (yolact.py:311-360) on the selected stage outputs, finest first, for the variant Yolact.__init__ insists on."""
     f = net.fpn
@@ -151,5 +172,8 @@ def forward(net, x_nchw, batch_stats=None):
     size the criterion reads, yolact.py:566-567) as Yolact.forward_train does, so a caller that comes here directly needs no method
     of Yolact."""
     net.cfg._tmp_img_h, net.cfg._tmp_img_w = int(x_nchw.shape[2]), int(x_nchw.shape[3])
-    outs = backbone(net, stem(net, x_nchw, batch_stats), batch_stats)
+    if isinstance(net.backbone, M.DarkNetBackbone):
+        outs = darknet(net, x_nchw, batch_stats)
+    else:
+        outs = backbone(net, stem(net, x_nchw, batch_stats), batch_stats)
     return heads(net, fpn(net, [outs[i] for i in net.cfg.backbone.selected_layers]))

@@ -50,7 +50,7 @@ class Trainer:
     batch_stats = not cfg.freeze_bn, and under cfg.freeze_bn the BatchNorm affine parameters stop requiring grad (yolact.py:552-553).
     The config is read when the Trainer is made and at every step.  forward: a callable (images, batch_stats) -> pred_outs, default
     net.forward_train; Trainer(net, forward=lambda x, bs: train_net.forward(net, x, bs)) trains a YOLACT++ config, whose DCN blocks
-    Yolact.forward_train still refuses."""
+    Yolact.forward_train still refuses, and yolact_darknet53, whose DarkNetBackbone it refuses too (train_net.darknet runs it)."""
 
     def __init__(self, net, criterion=None, optimizer=None, batch_stats=None, forward=None):
         cfg = active_cfg()
