@@ -912,6 +912,29 @@ typedef struct ymi_conv_wgrad_desc {
 } ymi_conv_wgrad_desc;
 int ymi_conv_wgrad_nhwc_f32(const ymi_conv_wgrad_desc *d, void *stream);
 
+/* The same weight gradient on the fp16 matrix pipe, opt-in (csrc/conv_wgrad_h2.hip; additive, the ABI number stays).  The descriptor,
+ * dw, db, ldg, stride, the accepted shapes and every error code are those of ymi_conv_wgrad_nhwc_f32; ws is
+ * ymi_workspace_bytes(YMI_WS_CONV_WGRAD_H2, desc) bytes.  No error path launches anything.  The bits differ from the fp32 entry's
+ * and are equal on every run: no floating-point atomics, the order of additions is a function of the shape only.
+ *   Operands  "fp16x2" (csrc/gemm_h2.h): per element t = v * s, h = fp16(t), l = fp16(t - h), both by round to nearest; s is one
+ *             power of two per tensor, the one that puts the tensor's magnitude bound into [2^13, 2^14) (a bound of 0, Inf or NaN:
+ *             s = 1).  The bounds, max |x| over all of x and max |g| over the channels [0, Cout) only (channels [Cout, ldg) may hold
+ *             anything, NaN included: they are never part of a sum), are computed on the device inside the call, into ws; there is
+ *             no host read and no synchronisation.
+ *   dw        A block owns one (tap, 32 input channels), one chunk of positions and 128 (Cout <= 128) or 256 output channels.  The
+ *             positions are cut into chunks by the fp32 entry's rule (csrc/grad_common.h: about 1024 blocks in all when
+ *             kh kw (Cin / 32) G blocks work on every chunk) with G = ceil(Cout / 128) for Cout <= 128 and ceil(Cout / 256)
+ *             above: the fp32 entry's very chunks up to Cout = 256, more and shorter ones above it.  Within a chunk the positions
+ *             go in K-steps of 16, ascending; per K-step and element the fp32 accumulator takes, in this order,
+ *             sum16(xh gh), sum16(xh gl), sum16(xl gh) (v_mfma_f32_32x32x16_f16: exact products, fp32 accumulation; xl gl is
+ *             dropped, <= 2^-22 |x g|).  The chunk partials are added in chunk order from +0.0, and the sum is multiplied by
+ *             2^(e >> 1), then by 2^(e - (e >> 1)), 2^e = 1 / (s_x s_g): the product of the scales is never formed, so operands of
+ *             2^-60 or 2^50 keep an fp32-class result.  A bound of 0 gives dw = +0.0 in every element; an Inf or NaN in column co of
+ *             g makes dw[:,co] non-finite.
+ *   db        Plain fp32, no split, from the same call: per chunk, the positions 16 q + 0 .. 7 (all q ascending) and
+ *             16 q + 8 .. 15 as two running sums, the first plus the second; the chunk partials in chunk order from +0.0. */
+int ymi_conv_wgrad_nhwc_h2(const ymi_conv_wgrad_desc *d, void *stream);
+
 /* The backward of ymi_bilinear_nhwc_f32 (align_corners=False, optional ReLU: dy is masked by y > 0, y = its output) for Ho = 2 Hi,
  * Wo = 2 Wi, odd sizes included, as a gather: dx[b,iy,ix,c] sums the output pixels that read (iy, ix), rows then columns in order,
  * with the coordinates of the forward.  YMI_ESHAPE: another ratio, C % 4, a pointer not 16-byte aligned; YMI_EARG: a size < 1, relu
@@ -1169,7 +1192,10 @@ enum {
   YMI_WS_STEM_WGRAD = 26,       /* desc: ymi_stem_wgrad_desc, the shape read -> its ws: chunks * 147 * Cout floats, padded to 16 */
   YMI_WS_AUGMENT = 27,          /* desc: ymi_augment_desc, B / n_masks read -> its ws: B records, n_masks (image, instance) pairs and B
                                  * pairs of resize scales, B * sizeof(ymi_augment_rec) + 8 n_masks + 16 B bytes, each part padded to 16 */
-  YMI_WS_PRECONV_WGRAD = 28     /* desc: ymi_preconv_wgrad_desc, the shape read -> its ws: chunks * 27 * Cout floats, padded to 16 */
+  YMI_WS_PRECONV_WGRAD = 28,    /* desc: ymi_preconv_wgrad_desc, the shape read -> its ws: chunks * 27 * Cout floats, padded to 16 */
+  YMI_WS_CONV_WGRAD_H2 = 29     /* desc: ymi_conv_wgrad_desc, the shape read -> ymi_conv_wgrad_nhwc_h2's ws: the two parts of
+                                 * YMI_WS_CONV_WGRAD, then kh*kw * chunks * per + 64 and chunks * per + 64 table entries (per = the
+                                 * positions of a chunk) and 2048 partial bounds, 4 bytes each, each part padded to 16 */
 };
 typedef struct { int32_t A, B; int64_t n; } ymi_mask_iou_shape;
 typedef struct { int32_t N, h, w, cap; } ymi_rle_shape;      /* cap <= 0: the safe capacity h*w + 1 */

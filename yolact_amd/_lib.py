@@ -357,7 +357,7 @@ class RleShape(C.Structure):
 (WS_WINO_V, WS_WINO_M, WS_SPLITK, WS_MASK_IOU, WS_JPEG_COEFS, WS_JPEG_PLANES, WS_DETECT_SCORES_T, WS_DETECT_PER_PRIOR,
  WS_DETECT_CAND, WS_DETECT_REC, WS_AMAX_SLOT, WS_RLE_COUNTS, WS_DETECT_GREEDY, WS_JPEG_ENC, WS_JPEG_ENC_OUT,
  WS_MASK_LOSS, WS_MATCH, WS_BOX_LOSS, WS_CLASS_LOSS, WS_SEGM_LOSS, WS_MASKIOU_INPUT, WS_CONV_BWD, WS_MASKIOU_HEAD,
- WS_CONV_WGRAD, WS_BN, WS_STEM_WGRAD, WS_AUGMENT, WS_PRECONV_WGRAD) = range(1, 29)
+ WS_CONV_WGRAD, WS_BN, WS_STEM_WGRAD, WS_AUGMENT, WS_PRECONV_WGRAD, WS_CONV_WGRAD_H2) = range(1, 30)
 
 EFORMAT, EUNSUPPORTED = -4, -5
 UP_FLAT, UP_BAND, UP_ROWS16, UP_ROWS32 = 1, 2, 3, 4       # ymi_mask_upsample_kernel (include/yolact_amd.h YMI_UP_*)
@@ -406,6 +406,7 @@ SYMBOLS = [
     ('ymi_maskiou_head_f32', C.c_int, [C.POINTER(MaskIouHeadDesc), _P]),
     ('ymi_act_bwd_f32', C.c_int, [_P, _P, _P, C.c_long] + [_I] * 6 + [_P]),
     ('ymi_conv_wgrad_nhwc_f32', C.c_int, [C.POINTER(ConvWgradDesc), _P]),
+    ('ymi_conv_wgrad_nhwc_h2', C.c_int, [C.POINTER(ConvWgradDesc), _P]),
     ('ymi_conv_dgrad_s2_nhwc_f32', C.c_int, [C.POINTER(ConvDgradDesc), _P]),
     ('ymi_bn_fwd_nhwc_f32', C.c_int, [C.POINTER(BnDesc), _P]),
     ('ymi_bn_bwd_nhwc_f32', C.c_int, [C.POINTER(BnDesc), _P]),

@@ -1,5 +1,5 @@
 """Differentiable building blocks of the train-mode heads, protonet, FPN, ResNet stages, ResNet stem and DarkNet backbone on the HIP
-kernels (csrc/conv_train.hip, csrc/conv_dgrad.hip, csrc/bn_train.hip, csrc/stem_train.hip, csrc/darknet_train.hip and the conv engine).
+kernels (csrc/conv_train.hip, csrc/conv_wgrad_h2.hip, csrc/conv_dgrad.hip, csrc/bn_train.hip, csrc/stem_train.hip, csrc/darknet_train.hip and the conv engine).
 
     conv2d_act(x, weight, bias, padding, act)            -> y [B,H,W,Cout]: act(conv(x, weight) + bias), act in {None, 'relu', 'tanh'}
     conv2d_multi(x, [(weight, bias, act), ..], padding)  -> one y per entry: up to three convolutions of the SAME input as one launch
@@ -25,6 +25,8 @@ kernels (csrc/conv_train.hip, csrc/conv_dgrad.hip, csrc/bn_train.hip, csrc/stem_
     dark_unit(x, seq, batch_stats, residual)             -> a DarkNet unit, Sequential(conv, BatchNorm2d, LeakyReLU(0.1)): conv2d_plain,
                                                             then batch_norm_leaky
     dark_block(x, block, batch_stats)                    -> a modules.DarkNetBlock (backbone.py:235-247): conv2(conv1(x)) + x
+    wgrad_mode(mode) / set_wgrad_mode(mode)              the weight-gradient kernel of the four convolutions and deform_conv's GEMM: 'fp32'
+                                                            (default) or 'fp16x2' (csrc/conv_wgrad_h2.hip); a context manager and a setter
 
 x and the results are NHWC fp32 GPU tensors; weight and bias are nn.Conv2d parameters in torch layout.  Everything is once
 differentiable in x, every weight and every bias.  Each call packs its filters from the CURRENT parameter values (a permute; no
@@ -38,6 +40,7 @@ raises NotImplementedError naming it.  Forward: one ymi_conv2d_nhwc_f32 launch o
        is ceil32 of the summed widths, padding zeroed by the last output's launch.  Without one (conv2d_plain): dy itself, F.pad-ed
        to ldg only when Cout % 32 != 0, and no activation launch.
   dw   _weight_grad: ymi_conv_wgrad_nhwc_f32 once over all outputs (dw, and db when there is a bias), then _unpack_dw per output.
+       Under wgrad_mode('fp16x2') / set_wgrad_mode (read by the forward, kept on ctx): ymi_conv_wgrad_nhwc_h2 in its place.
   dx   _data_grad.  Stride 1: ymi_conv2d_nhwc_f32 on g with the filters flipped in both taps and transposed in (Cin, Cout).
        Stride 2 has two routes.  conv2d_plain: ymi_conv_dgrad_s2_nhwc_f32 (csrc/conv_dgrad.hip: only the taps that exist).
        conv2d_down (zero_insert = True): g spread over a zeroed [B,H,W,ldg] buffer (gz[:, ::2, ::2] = g), then the stride-1 launch,
@@ -64,7 +67,9 @@ residual's gradient is the incoming one.  preconv: stem_conv's scheme at 3x3 / s
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
+import threading
 
 import torch
 import torch.nn.functional as F
@@ -179,9 +184,44 @@ def _cat_f32(ts):
     return ts[0] if len(ts) == 1 else torch.cat(ts, 0)
 
 
-def _weight_grad(xd, g, ldg, Cin, ctot, k, pad, stride, want_w, want_b):
-    """One ymi_conv_wgrad_nhwc_f32 launch on xd [B,H,W,Cin] and g [B,Ho,Wo,ldg] -> (dw_flat [k*k*Cin, ctot], db [ctot]), None
-    where not wanted."""
+WGRAD_MODES = {'fp32': ('ymi_conv_wgrad_nhwc_f32', 'CONV_WGRAD'), 'fp16x2': ('ymi_conv_wgrad_nhwc_h2', 'CONV_WGRAD_H2')}
+_wgrad = threading.local()                               # .mode: this thread's weight-gradient mode, 'fp32' where never set
+
+
+def check_wgrad_mode(mode):
+    if mode not in WGRAD_MODES:
+        raise ValueError("wgrad mode %r: 'fp32' and 'fp16x2' are the modes" % (mode,))
+    return mode
+
+
+def get_wgrad_mode():
+    """The calling thread's weight-gradient mode."""
+    return getattr(_wgrad, 'mode', 'fp32')
+
+
+def set_wgrad_mode(mode):
+    """The weight-gradient kernel of every Conv whose FORWARD runs on this thread from now on -> the mode it replaces.  'fp32':
+    ymi_conv_wgrad_nhwc_f32, the default, whose bits the goldens pin.  'fp16x2': ymi_conv_wgrad_nhwc_h2 (csrc/conv_wgrad_h2.hip), the
+    same sums on the fp16 matrix pipe with both operands split in two fp16 planes: other bits, equal on every run, within the fp32
+    bar of fp64.  The forward, dx, the stem, the pre-convolution and the mask-IoU net do not read the mode."""
+    old = get_wgrad_mode()
+    _wgrad.mode = check_wgrad_mode(mode)
+    return old
+
+
+@contextlib.contextmanager
+def wgrad_mode(mode):
+    """with wgrad_mode('fp16x2'): the forwards inside record the mode; their backward uses it wherever and whenever it runs."""
+    old = set_wgrad_mode(mode)
+    try:
+        yield
+    finally:
+        _wgrad.mode = old
+
+
+def _weight_grad(xd, g, ldg, Cin, ctot, k, pad, stride, want_w, want_b, mode='fp32'):
+    """One launch of the mode's weight-gradient entry on xd [B,H,W,Cin] and g [B,Ho,Wo,ldg] -> (dw_flat [k*k*Cin, ctot], db [ctot]),
+    None where not wanted."""
     dev = xd.device
     B, H, W = xd.shape[:3]
     dw = torch.empty(k * k * Cin, ctot, dtype=torch.float32, device=dev) if want_w else None
@@ -190,9 +230,10 @@ def _weight_grad(xd, g, ldg, Cin, ctot, k, pad, stride, want_w, want_b):
     d.x, d.g = xd.data_ptr(), g.data_ptr()
     d.dw, d.db = (None if t is None else t.data_ptr() for t in (dw, db))
     d.B, d.H, d.W, d.Cin, d.Cout, d.ldg, d.kh, d.kw, d.pad, d.stride = B, H, W, Cin, ctot, ldg, k, k, pad, stride
-    ws = LC.workspace('CONV_WGRAD', d, dev)
+    entry, kind = WGRAD_MODES[mode]
+    ws = LC.workspace(kind, d, dev)
     d.ws_bytes = ws.numel()
-    L.check(L.lib().ymi_conv_wgrad_nhwc_f32(C.byref(d), L.stream_ptr()), 'ymi_conv_wgrad_nhwc_f32')
+    L.check(getattr(L.lib(), entry)(C.byref(d), L.stream_ptr()), entry)
     return dw, db
 
 
@@ -250,6 +291,8 @@ class Conv(torch.autograd.Function):
         ctx.save_for_backward(x, *((*params, *ys) if biased else ws))
         ctx.geo, ctx.acts, ctx.couts, ctx.biased, ctx.zero_insert = (k, pad, stride), acts, couts, biased, zero_insert
         ctx.dtypes = [x.dtype] + [None if p is None else p.dtype for p in params]
+        # autograd runs a CUDA backward on a thread of its own, where the thread-local mode is the default: the forward's is kept
+        ctx.wgrad = get_wgrad_mode()
         return tuple(ys)
 
     @staticmethod
@@ -286,7 +329,7 @@ class Conv(torch.autograd.Function):
             grads = [None] * len(want_p)
             want_w, want_b = any(want_p[0::2]), any(want_p[1::2])
             if want_w or want_b:
-                dw, db = _weight_grad(xd, g, ldg, Cin, ctot, k, pad, stride, want_w, want_b)
+                dw, db = _weight_grad(xd, g, ldg, Cin, ctot, k, pad, stride, want_w, want_b, ctx.wgrad)
                 n0 = 0
                 for i, co in enumerate(couts):
                     if want_p[2 * i]:

@@ -10,9 +10,12 @@ the update kernel (optim.SGD.step(loss)), and the losses come back as device ten
 """
 from __future__ import annotations
 
+import contextlib
+
 import torch
 
 from .config import active_cfg
+from .layers import train_ops
 from .optim import SGD
 
 
@@ -50,10 +53,13 @@ class Trainer:
     batch_stats = not cfg.freeze_bn, and under cfg.freeze_bn the BatchNorm affine parameters stop requiring grad (yolact.py:552-553).
     The config is read when the Trainer is made and at every step.  forward: a callable (images, batch_stats) -> pred_outs, default
     net.forward_train; Trainer(net, forward=lambda x, bs: train_net.forward(net, x, bs)) trains a YOLACT++ config, whose DCN blocks
-    Yolact.forward_train still refuses, and yolact_darknet53, whose DarkNetBackbone it refuses too (train_net.darknet runs it)."""
+    Yolact.forward_train still refuses, and yolact_darknet53, whose DarkNetBackbone it refuses too (train_net.darknet runs it).
+    wgrad: None leaves train_ops' weight-gradient mode as the caller set it; 'fp32' or 'fp16x2' runs the forward of every step under
+    train_ops.wgrad_mode(wgrad), so the step's convolutions take their weight gradient from that kernel."""
 
-    def __init__(self, net, criterion=None, optimizer=None, batch_stats=None, forward=None):
+    def __init__(self, net, criterion=None, optimizer=None, batch_stats=None, wgrad=None, forward=None):
         cfg = active_cfg()
+        self.wgrad = None if wgrad is None else train_ops.check_wgrad_mode(wgrad)
         self.net = net
         if cfg.freeze_bn:
             net.freeze_bn()
@@ -79,7 +85,8 @@ class Trainer:
         synchronised.  In train.py's order: the learning rate of this iteration, forward, criterion, the sum, backward, the guarded
         update (which zeroes the gradients for the next iteration), iteration += 1."""
         set_lr(self.optimizer, lr_at(self.iteration, active_cfg(), self.lr, self.gamma))
-        preds = (self.net.forward_train if self.forward is None else self.forward)(images, self.batch_stats)
+        with contextlib.nullcontext() if self.wgrad is None else train_ops.wgrad_mode(self.wgrad):
+            preds = (self.net.forward_train if self.forward is None else self.forward)(images, self.batch_stats)
         losses = self.criterion(self.net, preds, targets, masks, num_crowds)
         loss = sum(losses.values())
         loss.backward()
