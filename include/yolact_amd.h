@@ -935,6 +935,40 @@ int ymi_conv_wgrad_nhwc_f32(const ymi_conv_wgrad_desc *d, void *stream);
  *             16 q + 8 .. 15 as two running sums, the first plus the second; the chunk partials in chunk order from +0.0. */
 int ymi_conv_wgrad_nhwc_h2(const ymi_conv_wgrad_desc *d, void *stream);
 
+/* The filters of a training step as the fp16x2 tiles of ymi_conv2d_nhwc_f32 read them (ymi_conv_desc.w_h2 / scale_h2 / winv_h2), packed
+ * ON THE DEVICE from the parameters' current storage (csrc/conv_pack_h2.hip; additive, the ABI number stays).  w[i], i < n <= 3, are
+ * fp32 [cout[i], Cin, k, k] in torch layout, contiguous, any 4-byte alignment, read in place; their output channels are concatenated,
+ * Rows below is the row count, RowsPad = ceil128(Rows).
+ *   mode 0    the forward's filters: row = output channel, Rows = sum cout, Kp = k k Cin, column (ky k + kx) Cin + c.
+ *   mode 1    the data gradient's: row = input channel, Rows = Cin, Kp = k k ld, column (ky' k + kx') ld + co holds
+ *             w[co, row, k - 1 - ky', k - 1 - kx'] (both taps flipped), co over the concatenated outputs, columns co in [sum cout, ld)
+ *             zero (ld: the channel stride of the backward's g).
+ *   planes    int16 [2][RowsPad][Kp]: plane 0 = fp16(w s_row), plane 1 = fp16(w s_row - plane 0), both by round to nearest even (the
+ *             difference is exact in fp32; csrc/gemm_h2.h split8h does the same to the activations).
+ *   winv      fp32 [RowsPad] = 1 / s_row.  s_row is the scale that ymi_h2_scale of csrc/common.h gives the row's max |w|: the power of two that puts it
+ *             into [2^13, 2^14), clamped to [2^-125, 2^125]; a row maximum of 0, Inf or NaN (a NaN anywhere in the row counts) gives
+ *             s_row = 1, the helper's rule, so an Inf or NaN stays one in plane 0.  For every row whose maximum is a normal number in
+ *             [2^-100, 2^100] the result equals engine.split2_planes_f16 of the torch packing bit for bit.
+ *   w32       optional (NULL: not written) fp32 [RowsPad][Kp]: the same packing unsplit, ymi_conv_desc.w of the fp32 tiles.  The fp16x2
+ *             tiles never read ymi_conv_desc.w; the entry's validation only wants it non-NULL and 16-byte aligned.
+ * Rows [Rows, RowsPad) are written too: planes (and w32) zero, winv 1.  Every element of every output is written, once.  One launch,
+ * no atomics, no workspace: a block owns whole rows (mode 0: one; mode 1: 8 input channels), finds their maxima in a first pass
+ * over the source and splits in a second; both passes read the source in contiguous runs and transpose through LDS.
+ * YMI_ENULL: d, planes, winv or one of w[0 .. n) NULL; YMI_EARG: n outside 1 .. 3, k not 1 or 3, mode not 0 or 1, Cin or a cout < 1;
+ * YMI_ESHAPE: Cin % 32, in mode 1 ld % 32 or ld < sum cout, planes / winv / w32 not 16-byte aligned, RowsPad Kp >= 2^29.  Validation
+ * runs on the host before any HIP call; no error path launches anything. */
+typedef struct ymi_conv_pack_desc {
+  const float *w[3];            /* [cout[i], Cin, k, k] */
+  void *planes;                 /* int16 [2][RowsPad][Kp] */
+  float *winv;                  /* [RowsPad] */
+  float *w32;                   /* NULL, or [RowsPad][Kp] */
+  int32_t cout[3];
+  int32_t n, Cin, k;
+  int32_t mode;                 /* 0: forward, 1: data gradient */
+  int32_t ld;                   /* mode 1: the padded output-channel count; mode 0: unused */
+} ymi_conv_pack_desc;
+int ymi_conv_pack_h2_f32(const ymi_conv_pack_desc *d, void *stream);
+
 /* The backward of ymi_bilinear_nhwc_f32 (align_corners=False, optional ReLU: dy is masked by y > 0, y = its output) for Ho = 2 Hi,
  * Wo = 2 Wi, odd sizes included, as a gather: dx[b,iy,ix,c] sums the output pixels that read (iy, ix), rows then columns in order,
  * with the coordinates of the forward.  YMI_ESHAPE: another ratio, C % 4, a pointer not 16-byte aligned; YMI_EARG: a size < 1, relu

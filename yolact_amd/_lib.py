@@ -196,6 +196,12 @@ class ConvDgradDesc(C.Structure):
                 ('kh', C.c_int32), ('kw', C.c_int32), ('pad', C.c_int32), ('stride', C.c_int32)]
 
 
+class ConvPackDesc(C.Structure):
+    """include/yolact_amd.h ymi_conv_pack_desc."""
+    _fields_ = [('w', C.c_void_p * 3), ('planes', C.c_void_p), ('winv', C.c_void_p), ('w32', C.c_void_p),
+                ('cout', C.c_int32 * 3), ('n', C.c_int32), ('Cin', C.c_int32), ('k', C.c_int32), ('mode', C.c_int32), ('ld', C.c_int32)]
+
+
 class BnDesc(C.Structure):
     """include/yolact_amd.h ymi_bn_desc."""
     _fields_ = [('x', C.c_void_p), ('res', C.c_void_p), ('gamma', C.c_void_p), ('beta', C.c_void_p),
@@ -407,6 +413,7 @@ SYMBOLS = [
     ('ymi_act_bwd_f32', C.c_int, [_P, _P, _P, C.c_long] + [_I] * 6 + [_P]),
     ('ymi_conv_wgrad_nhwc_f32', C.c_int, [C.POINTER(ConvWgradDesc), _P]),
     ('ymi_conv_wgrad_nhwc_h2', C.c_int, [C.POINTER(ConvWgradDesc), _P]),
+    ('ymi_conv_pack_h2_f32', C.c_int, [C.POINTER(ConvPackDesc), _P]),
     ('ymi_conv_dgrad_s2_nhwc_f32', C.c_int, [C.POINTER(ConvDgradDesc), _P]),
     ('ymi_bn_fwd_nhwc_f32', C.c_int, [C.POINTER(BnDesc), _P]),
     ('ymi_bn_bwd_nhwc_f32', C.c_int, [C.POINTER(BnDesc), _P]),

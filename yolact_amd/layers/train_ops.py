@@ -27,6 +27,10 @@ kernels (csrc/conv_train.hip, csrc/conv_wgrad_h2.hip, csrc/conv_dgrad.hip, csrc/
     dark_block(x, block, batch_stats)                    -> a modules.DarkNetBlock (backbone.py:235-247): conv2(conv1(x)) + x
     wgrad_mode(mode) / set_wgrad_mode(mode)              the weight-gradient kernel of the four convolutions and deform_conv's GEMM: 'fp32'
                                                             (default) or 'fp16x2' (csrc/conv_wgrad_h2.hip); a context manager and a setter
+    conv_mode(mode) / set_conv_mode(mode)                the tiles of the same convolutions' forward and data gradient: 'fp32' (default)
+                                                            or 'fp16x2' (filters packed on the device by csrc/conv_pack_h2.hip, the
+                                                            engine's fp16x2 tiles); a switch of its own, with get_conv_mode,
+                                                            check_conv_mode and CONV_MODES beside it
 
 x and the results are NHWC fp32 GPU tensors; weight and bias are nn.Conv2d parameters in torch layout.  Everything is once
 differentiable in x, every weight and every bias.  Each call packs its filters from the CURRENT parameter values (a permute; no
@@ -41,6 +45,11 @@ raises NotImplementedError naming it.  Forward: one ymi_conv2d_nhwc_f32 launch o
        to ldg only when Cout % 32 != 0, and no activation launch.
   dw   _weight_grad: ymi_conv_wgrad_nhwc_f32 once over all outputs (dw, and db when there is a bias), then _unpack_dw per output.
        Under wgrad_mode('fp16x2') / set_wgrad_mode (read by the forward, kept on ctx): ymi_conv_wgrad_nhwc_h2 in its place.
+  Under conv_mode('fp16x2') / set_conv_mode (read by the forward, kept on ctx) the 3 x 3 convolutions (_h2_pays) run their forward, their
+  stride-1 dx and conv2d_down's zero-insert dx on the engine's fp16x2 tiles: _pack_h2 (one ymi_conv_pack_h2_f32 launch over the
+  parameters in place, both layouts), ymi_amax_f32 on x or g into a zeroed slot, then the same ymi_conv2d_nhwc_f32 with w_h2,
+  scale_h2 = winv_h2 (no BatchNorm is folded in training) and the tile of _h2_tile.  ymi_conv_dgrad_s2_nhwc_f32, dw, db, the 1 x 1
+  convolutions, the stem, the pre-convolution, the BatchNorm kernels and the mask-IoU net never read the mode.
   dx   _data_grad.  Stride 1: ymi_conv2d_nhwc_f32 on g with the filters flipped in both taps and transposed in (Cin, Cout).
        Stride 2 has two routes.  conv2d_plain: ymi_conv_dgrad_s2_nhwc_f32 (csrc/conv_dgrad.hip: only the taps that exist).
        conv2d_down (zero_insert = True): g spread over a zeroed [B,H,W,ldg] buffer (gz[:, ::2, ::2] = g), then the stride-1 launch,
@@ -138,19 +147,91 @@ def check_plain(weight, stride, who='conv2d_plain'):
     return _check_geometry(who, weight, stride)
 
 
-def _engine_conv(x, ldx, wpk, bias, Cin, Cout, k, pad, segs, stride=1):
+def _engine_conv(x, ldx, wpk, bias, Cin, Cout, k, pad, segs, stride=1, h2=None):
     """One ymi_conv2d_nhwc_f32 launch on the exact-fp32 tiles: x [B,H,W,ldx], wpk [CoutPad][Kpad], Kpad = k*k*Cin or, for the Cin-4
-    loader, its ceil32; segs = (n0, n1, act, tensor)."""
+    loader, its ceil32; segs = (n0, n1, act, tensor).  h2 = (planes [2][CoutPad][Kpad], winv [CoutPad]) of _pack_h2: the same launch on
+    the fp16x2 tile _h2_tile picks, with the magnitude bound of x from one ymi_amax_f32 launch; wpk is then never read and may be
+    the planes themselves (the fp16x2 kernels take their filters from w_h2; the entry's validation wants w non-null and aligned)."""
     B, H, W = x.shape[:3]
     Ho, Wo = _out_size(H, W, k, pad, stride)
     d = L.ConvDesc()
     d.x, d.w, d.bias = x.data_ptr(), wpk.data_ptr(), (None if bias is None else bias.data_ptr())
     d.B, d.H, d.W, d.Cin, d.ldx, d.Ho, d.Wo, d.Cout = B, H, W, Cin, ldx, Ho, Wo, Cout
-    d.kh, d.kw, d.stride, d.pad, d.Kpad, d.tile = k, k, stride, pad, int(wpk.shape[1]), L.TILE_AUTO
+    d.kh, d.kw, d.stride, d.pad, d.Kpad, d.tile = k, k, stride, pad, int(wpk.shape[-1]), L.TILE_AUTO
     d.nseg = len(segs)
     for i, (n0, n1, act, y) in enumerate(segs):
         d.seg[i] = L.ConvSeg(n0, n1, act, n1 - n0, Ho * Wo * (n1 - n0), y.data_ptr())
+    if h2 is not None:
+        planes, winv = h2
+        # no BatchNorm is folded into a training convolution: the epilogue's scale is the inverse filter scale itself
+        d.w_h2, d.scale_h2, d.winv_h2 = planes.data_ptr(), winv.data_ptr(), winv.data_ptr()
+        amax = _amax_slot(x.device)
+        L.check(L.lib().ymi_amax_f32(x.data_ptr(), x.numel(), amax.data_ptr(), L.stream_ptr()), 'ymi_amax_f32')
+        d.x_amax = amax.data_ptr()
+        d.tile = _h2_tile(d)
     L.check(L.lib().ymi_conv2d_nhwc_f32(C.byref(d), L.stream_ptr()), 'ymi_conv2d_nhwc_f32')
+
+
+_slots = threading.local()                               # .pool: (device, stream, chunk, slots handed out) of this thread
+_SLOTS_PER_CHUNK = 256
+
+
+def _amax_slot(dev):
+    """A zeroed magnitude-bound slot (ymi_conv_desc.x_amax).  Slots are cut from a chunk of 256 that one memset zeroes, and no slot
+    is handed out twice, so a launch costs no fill of its own; a chunk belongs to one thread, device and stream, and its memory goes
+    back to the allocator, in stream order, when its last slot's launch has been enqueued."""
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    pool = getattr(_slots, 'pool', None)
+    if pool is None or pool[0] != (dev, stream) or pool[2] == _SLOTS_PER_CHUNK:
+        pool = _slots.pool = [(dev, stream), torch.zeros(_SLOTS_PER_CHUNK, L.AMAX_SLOT_FLOATS, dtype=torch.float32, device=dev), 0]
+    pool[2] += 1
+    return pool[1][pool[2] - 1]
+
+
+def _h2_pays(k):
+    """Whether a convolution runs on the fp16x2 tiles under conv_mode('fp16x2'): the 3 x 3 ones do, the 1 x 1 ones stay on the
+    exact-fp32 tiles.  A static class rule from profiles/conv_h2_train_probe_b8.txt: every 3 x 3 class of a step gains or stays within
+    the spread of the class, while the pointwise ones are bound by the traffic of x and y, to which the mode adds the pass for the bound
+    of x: of eighteen measured calls five are slower by more than the spread, the ten faster ones gain through the cheaper packing
+    rather than the tile, and the class's sum, 1647 against 1680 us, lies inside its summed spread of 43 us."""
+    return k == 3
+
+
+def _h2_tile(d):
+    """The fp16x2 tile of a described convolution: a static rule, no tune table, nothing measured at run time.  Where the pipelined
+    kernel of csrc/dcn.hip takes the descriptor (run_pipe: one dense output, Cout % 4 == 0, no activation or ReLU; its fourth
+    condition, two chunks of 32 along K, holds for every 3 x 3) and the output fills its 128 columns (Cout >= 128: at 64 the
+    engine's 64x64 measured 100 us against 125) its tile, 64x128 on eight waves from M = 16384 rows and 32x128 below, as
+    dcn_v2._dcn_launch chooses; otherwise the engine's own choice (ymi_conv_pick_tile) as its fp16x2 variant, 128x32, which has
+    none, becoming 64x32 split in K."""
+    M = d.B * d.Ho * d.Wo
+    g0 = d.seg[0]
+    if (d.nseg == 1 and g0.n0 == 0 and g0.n1 == d.Cout and d.Cout % 4 == 0 and d.Cout >= 128 and g0.act in (L.ACT_NONE, L.ACT_RELU)
+            and d.Kpad // 32 >= 2 and M * d.Cout < 1 << 31):
+        return L.TILE_H2 | L.TILE_DCNP | (L.DCNP_64x128_W8 if M >= 16384 else L.DCNP_32x128)
+    tile = L.lib().ymi_conv_pick_tile(C.byref(d))
+    if tile < 0:
+        L.check(tile, 'ymi_conv_pick_tile')
+    return (L.TILE_64x32_K2 if tile == L.TILE_128x32 else tile) | L.TILE_H2
+
+
+def _pack_h2(ws, Cin, k, mode, ld=0):
+    """One ymi_conv_pack_h2_f32 launch over the parameters ws (their CURRENT values, read in place: no permute, no concatenation)
+    -> (planes int16 [2][RowsPad][Kp], winv fp32 [RowsPad]).  mode 0: the layout of _pack_forward; mode 1: that of _pack_dgrad(., ld)."""
+    dev = ws[0].device
+    ws = [LC.f32(w, dev) for w in ws]                       # (fp32 contiguous parameters: themselves, no copy)
+    couts = [int(w.shape[0]) for w in ws]
+    rows_pad = _ceil(sum(couts) if mode == 0 else Cin, 128)
+    Kp = k * k * (Cin if mode == 0 else ld)
+    planes = torch.empty(2, rows_pad, Kp, dtype=torch.int16, device=dev)
+    winv = torch.empty(rows_pad, dtype=torch.float32, device=dev)
+    d = L.ConvPackDesc()
+    for i, w in enumerate(ws):
+        d.w[i], d.cout[i] = w.data_ptr(), couts[i]
+    d.planes, d.winv, d.w32 = planes.data_ptr(), winv.data_ptr(), None
+    d.n, d.Cin, d.k, d.mode, d.ld = len(ws), Cin, k, mode, ld
+    L.check(L.lib().ymi_conv_pack_h2_f32(C.byref(d), L.stream_ptr()), 'ymi_conv_pack_h2_f32')
+    return planes, winv
 
 
 def _pack_forward(wcat):
@@ -219,6 +300,46 @@ def wgrad_mode(mode):
         _wgrad.mode = old
 
 
+CONV_MODES = ('fp32', 'fp16x2')
+_conv = threading.local()                                # .mode: this thread's forward / data-gradient mode, 'fp32' where never set
+
+
+def check_conv_mode(mode):
+    if mode not in CONV_MODES:
+        raise ValueError("conv mode %r: 'fp32' and 'fp16x2' are the modes" % (mode,))
+    return mode
+
+
+def get_conv_mode():
+    """The calling thread's forward / data-gradient mode."""
+    return getattr(_conv, 'mode', 'fp32')
+
+
+def set_conv_mode(mode):
+    """The tiles of the forward and of the data gradient of every Conv whose FORWARD runs on this thread from now on -> the mode it
+    replaces; a switch of its own beside set_wgrad_mode.  'fp32': the exact-fp32 tiles, the default, whose bits the goldens pin.
+    'fp16x2': where _h2_pays says so (the 3 x 3 convolutions) the filters are packed on the device as two fp16 planes under one
+    power-of-two scale per row (ymi_conv_pack_h2_f32), the input's magnitude bound comes from a ymi_amax_f32 launch, and the same
+    ymi_conv2d_nhwc_f32 runs on the fp16x2 tile _h2_tile picks: other bits, equal on every run, within the fp32 bar of fp64.  The
+    1 x 1 convolutions, deform_conv's GEMM among them, keep the fp32 tiles and their bits.  The forward, the stride-1 dx and
+    conv2d_down's zero-insert dx follow the mode; ymi_conv_dgrad_s2_nhwc_f32 (conv2d_plain's stride-2 dx), dw, db, the stem, the
+    pre-convolution, the BatchNorm kernels and the mask-IoU net do not read it."""
+    old = get_conv_mode()
+    _conv.mode = check_conv_mode(mode)
+    return old
+
+
+@contextlib.contextmanager
+def conv_mode(mode):
+    """with conv_mode('fp16x2'): the forwards inside run on the fp16x2 tiles and record the mode; their dx uses it wherever and
+    whenever the backward runs."""
+    old = set_conv_mode(mode)
+    try:
+        yield
+    finally:
+        _conv.mode = old
+
+
 def _weight_grad(xd, g, ldg, Cin, ctot, k, pad, stride, want_w, want_b, mode='fp32'):
     """One launch of the mode's weight-gradient entry on xd [B,H,W,Cin] and g [B,Ho,Wo,ldg] -> (dw_flat [k*k*Cin, ctot], db [ctot]),
     None where not wanted."""
@@ -242,9 +363,10 @@ def _unpack_dw(dw_flat, k, Cin):
     return dw_flat.reshape(k, k, Cin, dw_flat.shape[1]).permute(3, 2, 0, 1).contiguous()
 
 
-def _data_grad(g, ldg, wcat, B, H, W, k, pad, stride, zero_insert):
-    """dx [B,H,W,Cin] from g [B,Ho,Wo,ldg] and the filters wcat [ctot,Cin,k,k] (the module docstring has the routes)."""
-    dev, Cin = g.device, int(wcat.shape[1])
+def _data_grad(g, ldg, ws, B, H, W, k, pad, stride, zero_insert, mode='fp32'):
+    """dx [B,H,W,Cin] from g [B,Ho,Wo,ldg] and the parameters ws, each [co,Cin,k,k] (the module docstring has the routes).  mode
+    'fp16x2': the stride-1 launch (the zero-insert route's too) on the fp16x2 tiles, its filters from _pack_h2."""
+    dev, Cin = g.device, int(ws[0].shape[1])
     if stride == 2 and zero_insert:
         # g with zeros between its pixels, exactly H x W (even and odd sizes), then the stride-1 data gradient: the added zeros
         # change no bit of a sum, and a pixel no window reads (1x1) gets an exact +0.0
@@ -252,10 +374,13 @@ def _data_grad(g, ldg, wcat, B, H, W, k, pad, stride, zero_insert):
         gz[:, ::2, ::2] = g
         g, stride = gz, 1
     dx = torch.empty(B, H, W, Cin, dtype=torch.float32, device=dev)
-    if stride == 1:
-        _engine_conv(g, ldg, _pack_dgrad(wcat, ldg), None, ldg, Cin, k, k - 1 - pad, [(0, Cin, L.ACT_NONE, dx)])
+    if stride == 1 and mode == 'fp16x2' and _h2_pays(k):
+        planes, winv = _pack_h2(ws, Cin, k, 1, ldg)
+        _engine_conv(g, ldg, planes, None, ldg, Cin, k, k - 1 - pad, [(0, Cin, L.ACT_NONE, dx)], h2=(planes, winv))
+    elif stride == 1:
+        _engine_conv(g, ldg, _pack_dgrad(_cat_f32(ws), ldg), None, ldg, Cin, k, k - 1 - pad, [(0, Cin, L.ACT_NONE, dx)])
     else:
-        wpk = _pack_dgrad_s2(wcat, ldg)
+        wpk = _pack_dgrad_s2(_cat_f32(ws), ldg)
         d = L.ConvDgradDesc()
         d.g, d.w, d.dx = g.data_ptr(), wpk.data_ptr(), dx.data_ptr()
         d.B, d.H, d.W, d.Cin, d.Cout, d.ldg, d.kh, d.kw, d.pad, d.stride = B, H, W, Cin, ldg, ldg, k, k, pad, 2
@@ -284,15 +409,20 @@ class Conv(torch.autograd.Function):
                 ys.append(y)
                 segs.append((n0, n0 + co, a, y))
                 n0 += co
-            _engine_conv(xd, Cin, _pack_forward(_cat_f32(ws)), _cat_f32(bs).contiguous() if biased else None, Cin, n0, k, pad, segs,
-                         stride=stride)
+            mode = get_conv_mode()
+            bias = _cat_f32(bs).contiguous() if biased else None
+            if mode == 'fp16x2' and _h2_pays(k):
+                planes, winv = _pack_h2(ws, Cin, k, 0)
+                _engine_conv(xd, Cin, planes, bias, Cin, n0, k, pad, segs, stride=stride, h2=(planes, winv))
+            else:
+                _engine_conv(xd, Cin, _pack_forward(_cat_f32(ws)), bias, Cin, n0, k, pad, segs, stride=stride)
         # the inputs are saved so that autograd's version check refuses a backward after x or a parameter was edited in place; the
         # outputs (this call's own tensors) are what an activation's backward reads
         ctx.save_for_backward(x, *((*params, *ys) if biased else ws))
         ctx.geo, ctx.acts, ctx.couts, ctx.biased, ctx.zero_insert = (k, pad, stride), acts, couts, biased, zero_insert
         ctx.dtypes = [x.dtype] + [None if p is None else p.dtype for p in params]
         # autograd runs a CUDA backward on a thread of its own, where the thread-local mode is the default: the forward's is kept
-        ctx.wgrad = get_wgrad_mode()
+        ctx.wgrad, ctx.conv = get_wgrad_mode(), mode
         return tuple(ys)
 
     @staticmethod
@@ -337,7 +467,7 @@ class Conv(torch.autograd.Function):
                     if want_p[2 * i + 1]:
                         grads[2 * i + 1] = db if n == 1 else db[n0:n0 + co].clone()
                     n0 += co
-            dx = _data_grad(g, ldg, _cat_f32(ws), B, H, W, k, pad, stride, ctx.zero_insert) if want_x else None
+            dx = _data_grad(g, ldg, ws, B, H, W, k, pad, stride, ctx.zero_insert, ctx.conv) if want_x else None
         out = [dx] + grads
         return (None,) * 5 + tuple(None if t is None else t.to(dt) for t, dt in zip(out, ctx.dtypes))
 

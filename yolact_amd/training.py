@@ -55,11 +55,13 @@ class Trainer:
     net.forward_train; Trainer(net, forward=lambda x, bs: train_net.forward(net, x, bs)) trains a YOLACT++ config, whose DCN blocks
     Yolact.forward_train still refuses, and yolact_darknet53, whose DarkNetBackbone it refuses too (train_net.darknet runs it).
     wgrad: None leaves train_ops' weight-gradient mode as the caller set it; 'fp32' or 'fp16x2' runs the forward of every step under
-    train_ops.wgrad_mode(wgrad), so the step's convolutions take their weight gradient from that kernel."""
+    train_ops.wgrad_mode(wgrad), so the step's convolutions take their weight gradient from that kernel.  conv: the same for
+    train_ops.conv_mode, the tiles of the convolutions' forward and data gradient; the two switches are independent."""
 
-    def __init__(self, net, criterion=None, optimizer=None, batch_stats=None, wgrad=None, forward=None):
+    def __init__(self, net, criterion=None, optimizer=None, batch_stats=None, wgrad=None, conv=None, forward=None):
         cfg = active_cfg()
         self.wgrad = None if wgrad is None else train_ops.check_wgrad_mode(wgrad)
+        self.conv = None if conv is None else train_ops.check_conv_mode(conv)
         self.net = net
         if cfg.freeze_bn:
             net.freeze_bn()
@@ -85,7 +87,8 @@ class Trainer:
         synchronised.  In train.py's order: the learning rate of this iteration, forward, criterion, the sum, backward, the guarded
         update (which zeroes the gradients for the next iteration), iteration += 1."""
         set_lr(self.optimizer, lr_at(self.iteration, active_cfg(), self.lr, self.gamma))
-        with contextlib.nullcontext() if self.wgrad is None else train_ops.wgrad_mode(self.wgrad):
+        with contextlib.nullcontext() if self.wgrad is None else train_ops.wgrad_mode(self.wgrad), \
+                contextlib.nullcontext() if self.conv is None else train_ops.conv_mode(self.conv):
             preds = (self.net.forward_train if self.forward is None else self.forward)(images, self.batch_stats)
         losses = self.criterion(self.net, preds, targets, masks, num_crowds)
         loss = sum(losses.values())
