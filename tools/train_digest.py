@@ -9,11 +9,17 @@ run on the model of tests/test_gpu_stem_train.py::test_multibox_loss_from_the_im
 images) with random inputs: every output and every parameter gradient, with frozen and with batch statistics.  The weight-gradient
 entries ymi_conv_wgrad_nhwc_f32 and ymi_stem_wgrad_nhwc_f32 are also called on their own (WGRAD_SHAPES, STEM_WGRAD_SHAPES) at the edges
 of their position walk and chunk plan; the C ABI they are called through is that of every tree with these entries.
+fold_cases() reaches what the older cases leave out, through public functions too: batch_norm_leaky and batch_norm_act where only the
+residual asks for a gradient, preconv, dark_unit, dark_block, deform_conv, dcn_bottleneck, the convolutions under conv_mode / wgrad_mode
+with the backward inside and behind the `with`, and train_net.forward on a DarkNet of one block per stage.
 
     python tools/train_digest.py > digests.txt
+    python tools/train_digest.py --per-case > digests.txt      one line per case: its number of tensor lines and the SHA-256 of them
 """
+import contextlib
 import ctypes as C
 import hashlib
+import math
 import os
 import sys
 
@@ -28,6 +34,7 @@ import heads_train_ref as H  # noqa: E402
 import yolact_amd  # noqa: E402, F401
 from yolact_amd import _lib as L  # noqa: E402
 from yolact_amd import modules as M  # noqa: E402
+from yolact_amd import train_net as TN  # noqa: E402
 from yolact_amd.layers import train_ops as TO  # noqa: E402
 
 DEV = 'cuda:0'
@@ -43,9 +50,16 @@ WGRAD_SHAPES = [(3, 1, 3, 5, 1, 32, 32), (3, 2, 3, 5, 1, 32, 32), (3, 1, 2, 23, 
 STEM_WGRAD_SHAPES = [(1, 9, 9, 32)]                                                            # (B, H, W, Cout)
 
 
+PER_CASE = None            # --per-case: case -> its tensor lines, kept back and hashed at the end
+
+
 def emit(case, name, t):
     t = t.detach().cpu().contiguous()
-    print('%-30s %-26s %-7s %-18s %s' % (case, name, str(t.dtype)[6:], list(t.shape), hashlib.sha256(t.numpy().tobytes()).hexdigest()))
+    line = '%-30s %-26s %-7s %-18s %s' % (case, name, str(t.dtype)[6:], list(t.shape), hashlib.sha256(t.numpy().tobytes()).hexdigest())
+    if PER_CASE is None:
+        print(line)
+    else:
+        PER_CASE.setdefault(case, []).append(line)
 
 
 def leaf(t, grad=True, dtype=None):
@@ -78,7 +92,31 @@ def act_case(case, shape, act, grads=(True, True, True), dtype=None):
     backward_and_emit(case, [y], [up], leaves)
 
 
-def multi_case(case, n_in_loss):
+@contextlib.contextmanager
+def under(modes):
+    """modes None: nothing; (conv, wgrad): the two switches of train_ops around the block."""
+    if modes is None:
+        yield
+    else:
+        with TO.conv_mode(modes[0]), TO.wgrad_mode(modes[1]):
+            yield
+
+
+def forward_then_backward(case, modes, inside, forward, ups, leaves):
+    """forward() -> outputs, under the modes; every output, then the gradients, from a backward inside the block or behind it."""
+    def finish():
+        for i, y in enumerate(ys):
+            emit(case, 'y' if len(ys) == 1 else 'y%d' % i, y)
+        backward_and_emit(case, ys[:len(ups)], ups, leaves)
+    with under(modes):
+        ys = forward()
+        if inside:
+            finish()
+    if not inside:
+        finish()
+
+
+def multi_case(case, n_in_loss, modes=None, inside=True):
     g = torch.Generator().manual_seed(6)
     x = torch.randn(2, 5, 7, 32, generator=g)
     leaves, layers, ups = dict(x=leaf(x)), [], []
@@ -87,34 +125,27 @@ def multi_case(case, n_in_loss):
         leaves['w%d' % i], leaves['b%d' % i] = leaf(w), leaf(b)
         layers.append((leaves['w%d' % i], leaves['b%d' % i], act))
         ups.append(up)
-    ys = TO.conv2d_multi(leaves['x'], layers, 1)
-    for i, y in enumerate(ys):
-        emit(case, 'y%d' % i, y)
-    backward_and_emit(case, ys[:n_in_loss], ups[:n_in_loss], leaves)
+    forward_then_backward(case, modes, inside, lambda: TO.conv2d_multi(leaves['x'], layers, 1), ups[:n_in_loss], leaves)
 
 
 def down(n):
     return (n - 1) // 2 + 1
 
 
-def down_case(case, shape, act):
+def down_case(case, shape, act, modes=None, inside=True):
     k, B, H, W, Cin, Cout = shape
     x, w, b, up = conv_inputs(torch.Generator().manual_seed(7), *shape, Ho=down(H), Wo=down(W))
     leaves = dict(x=leaf(x), w=leaf(w), b=leaf(b))
-    y = TO.conv2d_down(leaves['x'], leaves['w'], leaves['b'], act)
-    emit(case, 'y', y)
-    backward_and_emit(case, [y], [up], leaves)
+    forward_then_backward(case, modes, inside, lambda: [TO.conv2d_down(leaves['x'], leaves['w'], leaves['b'], act)], [up], leaves)
 
 
-def plain_case(case, geo):
+def plain_case(case, geo, modes=None, inside=True):
     k, stride, Cin, Cout = geo
     B, H, W = 2, 9, 7
     Ho, Wo = (down(H), down(W)) if stride == 2 else (H, W)
     x, w, _, up = conv_inputs(torch.Generator().manual_seed(8), k, B, H, W, Cin, Cout, Ho=Ho, Wo=Wo)
     leaves = dict(x=leaf(x), w=leaf(w))
-    y = TO.conv2d_plain(leaves['x'], leaves['w'], stride)
-    emit(case, 'y', y)
-    backward_and_emit(case, [y], [up], leaves)
+    forward_then_backward(case, modes, inside, lambda: [TO.conv2d_plain(leaves['x'], leaves['w'], stride)], [up], leaves)
 
 
 def block_case(case, spec, batch_stats):
@@ -285,7 +316,137 @@ def net_cases():
     net_case('forward_heads', net, lambda *m: net.forward_heads(list(m)), maps)
 
 
+def seed_module(mod, g):
+    """Every parameter and running statistic of mod from the generator g: He-scaled filters, gamma and the running variance in
+    [0.5, 1.5), small biases and means; a DCN's offset convolution small in its filters and of order one in its bias, so that the
+    sampling points lie between the pixels."""
+    with torch.no_grad():
+        for n, t in mod.state_dict().items():
+            if 'num_batches' in n:
+                continue
+            if 'conv_offset_mask.bias' in n:
+                v = torch.randn(t.shape, generator=g)
+            elif t.dim() == 4:
+                v = torch.randn(t.shape, generator=g) * math.sqrt(2.0 / (t.shape[1] * t.shape[2] * t.shape[3]))
+                v = v * 0.02 if 'conv_offset_mask' in n else v
+            elif n.endswith('running_var') or n.endswith('weight'):
+                v = 0.5 + torch.rand(t.shape, generator=g)
+            else:
+                v = torch.randn(t.shape, generator=g) * 0.1
+            t.copy_(v)
+    return mod
+
+
+def emit_running(case, mod):
+    for n, t in mod.state_dict().items():
+        if 'running' in n:
+            emit(case, n, t)
+
+
+def bn_case(case, fn, shape, with_res, batch_stats, only_res=False, **kw):
+    """fn = batch_norm_leaky or batch_norm_act on x of `shape`; only_res: the residual alone requires grad."""
+    g = torch.Generator().manual_seed(17)
+    x, res, up = (torch.randn(*shape, generator=g) for _ in range(3))
+    bn = seed_module(nn.BatchNorm2d(shape[-1]), g).to(DEV).eval()
+    bn.requires_grad_(not only_res)
+    leaves = dict(x=leaf(x, not only_res), gamma=bn.weight, beta=bn.bias)
+    if with_res:
+        leaves['res'] = leaf(res)
+    y = fn(leaves['x'], bn, batch_stats, leaves.get('res'), **kw)
+    emit(case, 'y', y)
+    backward_and_emit(case, [y], [up], leaves)
+    emit_running(case, bn)
+
+
+def module_case(case, fn, mod, x, batch_stats, seed):
+    """fn(x, mod, batch_stats) for a seeded module on NHWC x: y, every gradient, the running statistics afterwards."""
+    g = torch.Generator().manual_seed(seed)
+    mod = seed_module(mod, g).to(DEV).eval()
+    leaves = dict(x=leaf(torch.randn(*x, generator=g)))
+    leaves.update(mod.named_parameters())
+    y = fn(leaves['x'], mod, batch_stats)
+    emit(case, 'y', y)
+    backward_and_emit(case, [y], [torch.randn(*y.shape, generator=g)], leaves)
+    emit_running(case, mod)
+
+
+def deform_case(case, stride, bias):
+    g = torch.Generator().manual_seed(19)
+    B, H, W, Cin, Cout = 2, 6, 5, 32, 40
+    Ho, Wo = (down(H), down(W)) if stride == 2 else (H, W)
+    x, w, b, up = conv_inputs(g, 3, B, H, W, Cin, Cout, Ho=Ho, Wo=Wo)
+    leaves = dict(x=leaf(x), om=leaf(torch.randn(B, Ho, Wo, 27, generator=g)), w=leaf(w))
+    if bias:
+        leaves['b'] = leaf(b)
+    y = TO.deform_conv(leaves['x'], leaves['om'], leaves['w'], leaves.get('b'), stride)
+    emit(case, 'y', y)
+    backward_and_emit(case, [y], [up], leaves)
+
+
+def darknet_net():
+    """yolact_darknet53_config at 32 features around a seeded DarkNetBackbone of one block per stage."""
+    yolact_amd.set_cfg('yolact_darknet53_config')
+    cfg = yolact_amd.config.cfg
+    o = H.golden_cfg_overrides()
+    cfg.fpn = cfg.fpn.copy({'num_features': o.pop('num_features')})
+    cfg.update(o)
+    from yolact_amd.yolact import Yolact
+    torch.manual_seed(3)
+    net = Yolact()
+    net.backbone = seed_module(M.DarkNetBackbone((1, 1, 1, 1, 1)), torch.Generator().manual_seed(21))
+    return net.to(DEV)
+
+
+def fold_cases():
+    for stats in (False, True):
+        mode = 'stats' if stats else 'frozen'
+        for with_res in (False, True):
+            bn_case('bn_leaky 2x5x7x32 %s %s' % ('res' if with_res else 'nores', mode), TO.batch_norm_leaky, (2, 5, 7, 32), with_res, stats)
+        bn_case('bn_leaky 1x3x3x4 res ' + mode, TO.batch_norm_leaky, (1, 3, 3, 4), True, stats)
+        bn_case('bn_leaky 2x5x7x32 only_res ' + mode, TO.batch_norm_leaky, (2, 5, 7, 32), True, stats, only_res=True)
+        for relu in (True, False):
+            bn_case('bn_act 2x5x7x32 only_res %s %s' % ('relu' if relu else 'norelu', mode), TO.batch_norm_act, (2, 5, 7, 32), True, stats,
+                    only_res=True, relu=relu)
+    g = torch.Generator().manual_seed(18)
+    x4 = torch.nn.functional.pad(torch.randn(2, 9, 7, 3, generator=g), (0, 1)).to(DEV)
+    w, up = torch.randn(32, 3, 3, 3, generator=g) * (2.0 / 27) ** 0.5, torch.randn(2, 9, 7, 32, generator=g)
+    leaves = dict(w=leaf(w))
+    y = TO.preconv(x4, leaves['w'])
+    emit('preconv', 'y', y)
+    backward_and_emit('preconv', [y], [up], leaves)
+    for stats in (False, True):
+        mode = 'stats' if stats else 'frozen'
+        unit = nn.Sequential(nn.Conv2d(32, 64, 3, stride=2, padding=1, bias=False), nn.BatchNorm2d(64), nn.LeakyReLU(0.1))
+        module_case('dark_unit 3x3_s2_32to64 ' + mode, TO.dark_unit, unit, (2, 9, 7, 32), stats, 20)
+        module_case('dark_block 64 ' + mode, TO.dark_block, M.DarkNetBlock(64, 32), (2, 5, 7, 64), stats, 20)
+    for stride in (1, 2):
+        for bias in (True, False):
+            deform_case('deform_conv s%d %s' % (stride, 'bias' if bias else 'nobias'), stride, bias)
+    for variant in ('identity', 'proj_s2'):
+        inplanes, planes, stride, projection = BLOCK_SPECS[variant]
+        for stats in (False, True):
+            ds = nn.Sequential(nn.Conv2d(inplanes, 4 * planes, 1, stride=stride, bias=False), nn.BatchNorm2d(4 * planes)) if projection else None
+            module_case('dcn_bottleneck %s %s' % (variant, 'stats' if stats else 'frozen'), TO.dcn_bottleneck,
+                        M.Bottleneck(inplanes, planes, stride, ds, use_dcn=True), (2, 9, 7, inplanes), stats, 22)
+    for modes in (('fp16x2', 'fp32'), ('fp32', 'fp16x2'), ('fp16x2', 'fp16x2')):
+        for inside in (True, False):
+            tag = 'conv_%s wgrad_%s %s' % (modes[0], modes[1], 'inside' if inside else 'behind')
+            for geo in ((3, 1, 32, 128), (3, 2, 32, 128), (3, 1, 32, 40), (3, 2, 32, 40)):
+                plain_case('plain 3x3_s%d_32to%d %s' % (geo[1], geo[3], tag), geo, modes, inside)
+            down_case('down 3x3_32to12 ' + tag, DOWN_SHAPES[0], None, modes, inside)
+            multi_case('multi 16+81+32 ' + tag, 3, modes, inside)
+    net = darknet_net()
+    images = torch.randn(2, 3, 64, 64, generator=torch.Generator().manual_seed(23))
+    for stats in (False, True):
+        net_case('train_net.forward darknet ' + ('stats' if stats else 'frozen'), net, lambda: TN.forward(net, images.to(DEV), stats), [])
+
+
 def main():
+    global PER_CASE
+    if sys.argv[1:] == ['--per-case']:
+        PER_CASE = {}
+    elif sys.argv[1:]:
+        raise SystemExit('usage: train_digest.py [--per-case]')
     print('# %s, torch %s' % (torch.cuda.get_device_name(0), torch.__version__))
     name = lambda s: '%dx%d_b%d_%dx%d_%dto%d' % (s[0], s[0], s[1], s[2], s[3], s[4], s[5])
     for shape in ACT_SHAPES:
@@ -308,6 +469,10 @@ def main():
     stem_cases()
     wgrad_cases()
     net_cases()
+    fold_cases()
+    for case, lines in (PER_CASE or {}).items():
+        # the SHA-256 of the case's lines as the plain run prints them, each ended by a newline
+        print('%-62s %4d %s' % (case, len(lines), hashlib.sha256(''.join(l + '\n' for l in lines).encode()).hexdigest()))
 
 
 if __name__ == '__main__':

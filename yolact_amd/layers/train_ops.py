@@ -37,19 +37,13 @@ differentiable in x, every weight and every bias.  Each call packs its filters f
 cache), launches only what needs_input_grad asks for, and saves its inputs, so autograd's version check refuses a backward after an
 in-place edit.  CPU tensors raise: there is no CPU path.
 
-The four convolutions are one autograd.Function, Conv, behind four validators.  Geometry (_check_geometry, whose faces are check_conv,
-check_down and check_plain): 3x3 / pad 1 and 1x1 / pad 0, stride 1 or 2, dilation 1, groups 1, Cin % 32 == 0, any Cout; anything else
-raises NotImplementedError naming it.  Forward: one ymi_conv2d_nhwc_f32 launch over all outputs.  Backward:
+The four convolutions are one autograd.Function, Conv, behind four validators (_check_geometry, whose faces are check_conv, check_down
+and check_plain): 3x3 / pad 1 and 1x1 / pad 0, stride 1 or 2, dilation 1, groups 1, Cin % 32 == 0, any Cout.  Forward: one
+ymi_conv2d_nhwc_f32 launch over all outputs.  Backward:
   g    with a bias: ymi_act_bwd_f32 per output (g = dy * act'(y), act None too), side by side in one buffer whose channel stride ldg
        is ceil32 of the summed widths, padding zeroed by the last output's launch.  Without one (conv2d_plain): dy itself, F.pad-ed
        to ldg only when Cout % 32 != 0, and no activation launch.
-  dw   _weight_grad: ymi_conv_wgrad_nhwc_f32 once over all outputs (dw, and db when there is a bias), then _unpack_dw per output.
-       Under wgrad_mode('fp16x2') / set_wgrad_mode (read by the forward, kept on ctx): ymi_conv_wgrad_nhwc_h2 in its place.
-  Under conv_mode('fp16x2') / set_conv_mode (read by the forward, kept on ctx) the 3 x 3 convolutions (_h2_pays) run their forward, their
-  stride-1 dx and conv2d_down's zero-insert dx on the engine's fp16x2 tiles: _pack_h2 (one ymi_conv_pack_h2_f32 launch over the
-  parameters in place, both layouts), ymi_amax_f32 on x or g into a zeroed slot, then the same ymi_conv2d_nhwc_f32 with w_h2,
-  scale_h2 = winv_h2 (no BatchNorm is folded in training) and the tile of _h2_tile.  ymi_conv_dgrad_s2_nhwc_f32, dw, db, the 1 x 1
-  convolutions, the stem, the pre-convolution, the BatchNorm kernels and the mask-IoU net never read the mode.
+  dw   _weight_grad: the wgrad mode's entry once over all outputs (dw, and db when there is a bias), then _unpack_dw per output.
   dx   _data_grad.  Stride 1: ymi_conv2d_nhwc_f32 on g with the filters flipped in both taps and transposed in (Cin, Cout).
        Stride 2 has two routes.  conv2d_plain: ymi_conv_dgrad_s2_nhwc_f32 (csrc/conv_dgrad.hip: only the taps that exist).
        conv2d_down (zero_insert = True): g spread over a zeroed [B,H,W,ldg] buffer (gz[:, ::2, ::2] = g), then the stride-1 launch,
@@ -57,25 +51,13 @@ raises NotImplementedError naming it.  Forward: one ymi_conv2d_nhwc_f32 launch o
        faster one there: at 3x3 256 -> 256, B = 8, 18 x 18 and 9 x 9 the kernel's grid is 48 and 16 blocks for 256 CUs, and
        forward_fpn forward + backward measured 4712 us with the kernel against 4637 us with this route, the parent's own spread
        being 62 us (profiles/train_net_ab.txt).
-upsample_add: d_lat = dy, d_top = ymi_bilinear_size_bwd_nhwc_f32 (a gather in a fixed order).  batch_norm_act: ymi_bn_fwd_nhwc_f32 /
-ymi_bn_bwd_nhwc_f32 (csrc/bn_train.hip).
-deform_conv: the reference's im2col + GEMM split.  DeformCols (csrc/dcn_train.hip) materialises col [B,Ho,Wo,9*Cin] (ymi_dcn_cols_fwd_f32);
-the GEMM is Conv as a 1 x 1 convolution of col, so y, dw, db and dcol come from the kernels above.  DeformCols' backward:
-ymi_dcn_cols_entries_f32 writes one (target pixel, coefficient) entry per (output pixel, tap, corner), torch.sort(stable=True) orders
-the int32 keys, and ymi_dcn_cols_bwd_f32 gathers gx per input pixel over its entries in that order and forms g_om by fixed-tree dot
-products: no floating-point atomics, equal bits on every run.  col is saved for the weight gradient: 9x the input map.
-stem_conv: one ymi_conv2d_nhwc_f32 launch through the engine's Cin-4 loader with the filter's fourth input channel zero; the backward
-is ymi_stem_wgrad_nhwc_f32 on the SAME x4 (its fourth channel reaches nothing), then _unpack_dw.  It is differentiable in the weight
-only: an x4 that requires grad raises, since nothing upstream of the image needs a gradient and returning None would silently give a
-zero one.  max_pool_3x3_s2: ymi_maxpool_fwd_nhwc_f32 / ymi_maxpool_bwd_nhwc_f32 (csrc/stem_train.hip); the backward recomputes each
-window's argmax from the saved input, the first of equal maxima in row-major window order taking the gradient as in PyTorch.
-batch_norm_leaky: ymi_bn_leaky_fwd_nhwc_f32 / ymi_bn_leaky_bwd_nhwc_f32 (csrc/bn_train.hip).  The slope decision z > 0 is the forward's:
-without a residual the backward reads it from y, with one from the bit mask the forward wrote (1/32 of the map, saved beside y); the
-residual's gradient is the incoming one.  preconv: stem_conv's scheme at 3x3 / stride 1; the backward is ymi_preconv_wgrad_nhwc_f32
-(csrc/darknet_train.hip).  check_darknet names what of a DarkNetBackbone these do not take.
+Both modes are read by the forward and kept on ctx; set_wgrad_mode and set_conv_mode say what follows them and what does not.
+BatchNorm with none, ReLU or LeakyReLU(0.1) is one autograd.Function, Bn (csrc/bn_train.hip); the stem's and DarkNet's convolution of
+the image are one, ImageConv, driven by a spec (STEM, PRE); the plain and the DCN bottleneck are one body, _bottleneck.
 """
 from __future__ import annotations
 
+import collections
 import contextlib
 import ctypes as C
 import threading
@@ -265,14 +247,46 @@ def _cat_f32(ts):
     return ts[0] if len(ts) == 1 else torch.cat(ts, 0)
 
 
+def _engine_filters(ws, k, mode, ldg=None):
+    """The filters of an engine launch from the parameters ws, each [co,Cin,k,k] -> (wpk, h2) as _engine_conv takes them.  ldg None:
+    the forward layout (_pack_forward); an ldg: the data gradient's (_pack_dgrad(., ldg)).  mode 'fp16x2' where _h2_pays: the planes
+    of _pack_h2 with their inverse scales, the planes standing in for wpk; otherwise the packed fp32 filters and h2 = None."""
+    if mode == 'fp16x2' and _h2_pays(k):
+        h2 = _pack_h2(ws, int(ws[0].shape[1]), k, 0) if ldg is None else _pack_h2(ws, int(ws[0].shape[1]), k, 1, ldg)
+        return h2[0], h2
+    wcat = _cat_f32(ws)
+    return (_pack_forward(wcat) if ldg is None else _pack_dgrad(wcat, ldg)), None
+
+
 WGRAD_MODES = {'fp32': ('ymi_conv_wgrad_nhwc_f32', 'CONV_WGRAD'), 'fp16x2': ('ymi_conv_wgrad_nhwc_h2', 'CONV_WGRAD_H2')}
+CONV_MODES = ('fp32', 'fp16x2')
 _wgrad = threading.local()                               # .mode: this thread's weight-gradient mode, 'fp32' where never set
+_conv = threading.local()                                # .mode: this thread's forward / data-gradient mode, 'fp32' where never set
+
+
+def _check_mode(word, modes, mode):
+    if mode not in modes:
+        raise ValueError("%s mode %r: 'fp32' and 'fp16x2' are the modes" % (word, mode))
+    return mode
+
+
+def _set_mode(local, word, modes, mode):
+    old = getattr(local, 'mode', 'fp32')
+    local.mode = _check_mode(word, modes, mode)
+    return old
+
+
+@contextlib.contextmanager
+def _mode_scope(local, word, modes, mode):
+    old = _set_mode(local, word, modes, mode)
+    try:
+        yield
+    finally:
+        local.mode = old
 
 
 def check_wgrad_mode(mode):
-    if mode not in WGRAD_MODES:
-        raise ValueError("wgrad mode %r: 'fp32' and 'fp16x2' are the modes" % (mode,))
-    return mode
+    return _check_mode('wgrad', WGRAD_MODES, mode)
 
 
 def get_wgrad_mode():
@@ -285,29 +299,16 @@ def set_wgrad_mode(mode):
     ymi_conv_wgrad_nhwc_f32, the default, whose bits the goldens pin.  'fp16x2': ymi_conv_wgrad_nhwc_h2 (csrc/conv_wgrad_h2.hip), the
     same sums on the fp16 matrix pipe with both operands split in two fp16 planes: other bits, equal on every run, within the fp32
     bar of fp64.  The forward, dx, the stem, the pre-convolution and the mask-IoU net do not read the mode."""
-    old = get_wgrad_mode()
-    _wgrad.mode = check_wgrad_mode(mode)
-    return old
+    return _set_mode(_wgrad, 'wgrad', WGRAD_MODES, mode)
 
 
-@contextlib.contextmanager
 def wgrad_mode(mode):
     """with wgrad_mode('fp16x2'): the forwards inside record the mode; their backward uses it wherever and whenever it runs."""
-    old = set_wgrad_mode(mode)
-    try:
-        yield
-    finally:
-        _wgrad.mode = old
-
-
-CONV_MODES = ('fp32', 'fp16x2')
-_conv = threading.local()                                # .mode: this thread's forward / data-gradient mode, 'fp32' where never set
+    return _mode_scope(_wgrad, 'wgrad', WGRAD_MODES, mode)
 
 
 def check_conv_mode(mode):
-    if mode not in CONV_MODES:
-        raise ValueError("conv mode %r: 'fp32' and 'fp16x2' are the modes" % (mode,))
-    return mode
+    return _check_mode('conv', CONV_MODES, mode)
 
 
 def get_conv_mode():
@@ -324,20 +325,13 @@ def set_conv_mode(mode):
     1 x 1 convolutions, deform_conv's GEMM among them, keep the fp32 tiles and their bits.  The forward, the stride-1 dx and
     conv2d_down's zero-insert dx follow the mode; ymi_conv_dgrad_s2_nhwc_f32 (conv2d_plain's stride-2 dx), dw, db, the stem, the
     pre-convolution, the BatchNorm kernels and the mask-IoU net do not read it."""
-    old = get_conv_mode()
-    _conv.mode = check_conv_mode(mode)
-    return old
+    return _set_mode(_conv, 'conv', CONV_MODES, mode)
 
 
-@contextlib.contextmanager
 def conv_mode(mode):
     """with conv_mode('fp16x2'): the forwards inside run on the fp16x2 tiles and record the mode; their dx uses it wherever and
     whenever the backward runs."""
-    old = set_conv_mode(mode)
-    try:
-        yield
-    finally:
-        _conv.mode = old
+    return _mode_scope(_conv, 'conv', CONV_MODES, mode)
 
 
 def _weight_grad(xd, g, ldg, Cin, ctot, k, pad, stride, want_w, want_b, mode='fp32'):
@@ -374,11 +368,9 @@ def _data_grad(g, ldg, ws, B, H, W, k, pad, stride, zero_insert, mode='fp32'):
         gz[:, ::2, ::2] = g
         g, stride = gz, 1
     dx = torch.empty(B, H, W, Cin, dtype=torch.float32, device=dev)
-    if stride == 1 and mode == 'fp16x2' and _h2_pays(k):
-        planes, winv = _pack_h2(ws, Cin, k, 1, ldg)
-        _engine_conv(g, ldg, planes, None, ldg, Cin, k, k - 1 - pad, [(0, Cin, L.ACT_NONE, dx)], h2=(planes, winv))
-    elif stride == 1:
-        _engine_conv(g, ldg, _pack_dgrad(_cat_f32(ws), ldg), None, ldg, Cin, k, k - 1 - pad, [(0, Cin, L.ACT_NONE, dx)])
+    if stride == 1:
+        wpk, h2 = _engine_filters(ws, k, mode, ldg)
+        _engine_conv(g, ldg, wpk, None, ldg, Cin, k, k - 1 - pad, [(0, Cin, L.ACT_NONE, dx)], h2=h2)
     else:
         wpk = _pack_dgrad_s2(_cat_f32(ws), ldg)
         d = L.ConvDgradDesc()
@@ -411,11 +403,8 @@ class Conv(torch.autograd.Function):
                 n0 += co
             mode = get_conv_mode()
             bias = _cat_f32(bs).contiguous() if biased else None
-            if mode == 'fp16x2' and _h2_pays(k):
-                planes, winv = _pack_h2(ws, Cin, k, 0)
-                _engine_conv(xd, Cin, planes, bias, Cin, n0, k, pad, segs, stride=stride, h2=(planes, winv))
-            else:
-                _engine_conv(xd, Cin, _pack_forward(_cat_f32(ws)), bias, Cin, n0, k, pad, segs, stride=stride)
+            wpk, h2 = _engine_filters(ws, k, mode)
+            _engine_conv(xd, Cin, wpk, bias, Cin, n0, k, pad, segs, stride=stride, h2=h2)
         # the inputs are saved so that autograd's version check refuses a backward after x or a parameter was edited in place; the
         # outputs (this call's own tensors) are what an activation's backward reads
         ctx.save_for_backward(x, *((*params, *ys) if biased else ws))
@@ -652,13 +641,20 @@ def share_params(n, params):
     return [list(flat[u * len(params):(u + 1) * len(params)]) for u in range(n)]
 
 
-class BnAct(torch.autograd.Function):
-    """apply(stats, relu, eps, momentum, running_mean, running_var, x [..,C], residual or None, gamma, beta) -> y.  stats: batch
-    statistics (the running ones are updated in place) or the running ones as they are."""
+LEAKY_SLOPE = 0.1
+
+
+class Bn(torch.autograd.Function):
+    """apply(act, stats, eps, momentum, running_mean, running_var, x [..,C], residual or None, gamma, beta) -> y.  act None or 'relu':
+    act(bn(x) + residual) (ymi_bn_fwd_nhwc_f32 / ymi_bn_bwd_nhwc_f32); 'leaky': leaky_relu(bn(x), 0.1) + residual, the residual BEHIND
+    the activation (ymi_bn_leaky_fwd_nhwc_f32 / ymi_bn_leaky_bwd_nhwc_f32).  stats: batch statistics (the running ones are updated in
+    place) or the running ones as they are.  The leaky slope decision z > 0 is the forward's: without a residual the backward reads
+    it from y, with one from the bit mask the forward wrote (1/32 of the map, saved beside the residual)."""
 
     @staticmethod
-    def forward(ctx, stats, relu, eps, momentum, rmean, rvar, x, residual, gamma, beta):
+    def forward(ctx, act, stats, eps, momentum, rmean, rvar, x, residual, gamma, beta):
         dev = x.device
+        leaky, relu = act == 'leaky', int(act == 'relu')
         with torch.cuda.device(dev), torch.no_grad():
             xd = LC.f32(x, dev)
             Cc = xd.shape[-1]
@@ -667,18 +663,19 @@ class BnAct(torch.autograd.Function):
             mean = torch.empty(Cc, dtype=torch.float32, device=dev)
             invstd = torch.empty(Cc, dtype=torch.float32, device=dev)
             rd = None if residual is None else LC.f32(residual, dev)
+            mask = torch.empty((xd.numel() + 31) // 32, dtype=torch.int32, device=dev) if leaky and residual is not None else None
             gd, bd = LC.f32(gamma, dev), LC.f32(beta, dev)
             d = L.BnDesc()
             d.x, d.res, d.gamma, d.beta = xd.data_ptr(), (None if rd is None else rd.data_ptr()), gd.data_ptr(), bd.data_ptr()
             d.running_mean, d.running_var = rmean.data_ptr(), rvar.data_ptr()
             d.y, d.mean, d.invstd = y.data_ptr(), mean.data_ptr(), invstd.data_ptr()
-            d.npos, d.C, d.training, d.relu, d.eps, d.momentum = npos, Cc, int(stats), int(relu), eps, momentum
+            d.npos, d.C, d.training, d.relu, d.eps, d.momentum = npos, Cc, int(stats), relu, eps, momentum
             ws = LC.workspace('BN', d, dev)
             d.ws_bytes = ws.numel()
-            L.check(L.lib().ymi_bn_fwd_nhwc_f32(C.byref(d), L.stream_ptr()), 'ymi_bn_fwd_nhwc_f32')
+            _bn_launch('ymi_bn_leaky_fwd_nhwc_f32' if leaky else 'ymi_bn_fwd_nhwc_f32', leaky, d, mask)
         # the inputs are saved too: autograd's version check refuses a backward after x or a parameter was edited in place
-        ctx.save_for_backward(x, gamma, beta, y, mean, invstd, *(() if residual is None else (residual,)))
-        ctx.stats, ctx.relu, ctx.eps = int(stats), int(relu), eps
+        ctx.save_for_backward(x, gamma, beta, y, mean, invstd, *(t for t in (residual, mask) if t is not None))
+        ctx.stats, ctx.leaky, ctx.relu, ctx.eps = int(stats), leaky, relu, eps
         ctx.dtypes = [x.dtype, None if residual is None else residual.dtype, gamma.dtype, beta.dtype]
         return y
 
@@ -687,16 +684,16 @@ class BnAct(torch.autograd.Function):
     def backward(ctx, dy):
         want_x, want_r, want_g, want_b = ctx.needs_input_grad[6:]
         x, gamma, beta, y, mean, invstd = ctx.saved_tensors[:6]      # (the version check)
+        mask = ctx.saved_tensors[7] if len(ctx.saved_tensors) > 7 else None
         if not (want_x or want_r or want_g or want_b):
             return (None,) * 10
         dev = x.device
         with torch.cuda.device(dev), torch.no_grad():
             xd, dyd, gd = LC.f32(x, dev), LC.f32(dy, dev), LC.f32(gamma, dev)
             Cc = xd.shape[-1]
-            new = lambda like: torch.empty_like(like)
-            dx = new(xd) if want_x else None
-            # without a ReLU d_res is dy itself
-            dres = new(xd) if (want_r and ctx.relu) else None
+            dx = torch.empty_like(xd) if want_x else None
+            # d_res is a kernel output only under a ReLU; otherwise it is dy itself
+            dres = torch.empty_like(xd) if (want_r and ctx.relu) else None
             dg = torch.empty(Cc, dtype=torch.float32, device=dev) if want_g else None
             db = torch.empty(Cc, dtype=torch.float32, device=dev) if want_b else None
             if dx is not None or dres is not None or dg is not None or db is not None:
@@ -707,11 +704,17 @@ class BnAct(torch.autograd.Function):
                 d.npos, d.C, d.training, d.relu, d.eps = xd.numel() // Cc, Cc, ctx.stats, ctx.relu, ctx.eps
                 ws = LC.workspace('BN', d, dev)
                 d.ws_bytes = ws.numel()
-                L.check(L.lib().ymi_bn_bwd_nhwc_f32(C.byref(d), L.stream_ptr()), 'ymi_bn_bwd_nhwc_f32')
+                _bn_launch('ymi_bn_leaky_bwd_nhwc_f32' if ctx.leaky else 'ymi_bn_bwd_nhwc_f32', ctx.leaky, d, mask)
             if want_r and not ctx.relu:
                 dres = dyd
         out = [dx, dres, dg, db]
         return (None,) * 6 + tuple(None if (t is None or dt is None) else t.to(dt) for t, dt in zip(out, ctx.dtypes))
+
+
+def _bn_launch(entry, leaky, d, mask):
+    """A BatchNorm entry on its descriptor; the leaky ones take the bit mask (or null) behind it."""
+    args = (C.byref(d), None if mask is None else mask.data_ptr(), L.stream_ptr()) if leaky else (C.byref(d), L.stream_ptr())
+    L.check(getattr(L.lib(), entry)(*args), entry)
 
 
 def _check_bn(who, x, bn, batch_stats, residual):
@@ -753,123 +756,70 @@ def _bn_stats_written(bn):
         torch.autograd.graph.increment_version(t)
 
 
-def batch_norm_act(x, bn, batch_stats=None, residual=None, relu=False):
-    """relu(bn(x) + residual) on NHWC x for an nn.BatchNorm2d `bn`.  batch_stats None follows bn.training; True: the batch statistics
-    (running_mean / running_var updated in place, num_batches_tracked incremented); False: the running statistics (frozen)."""
-    stats = _check_bn('batch_norm_act', x, bn, batch_stats, residual)
-    y = BnAct.apply(stats, bool(relu), float(bn.eps), float(bn.momentum), bn.running_mean, bn.running_var, x, residual, bn.weight,
-                    bn.bias)
+def _batch_norm(who, act, x, bn, batch_stats, residual):
+    stats = _check_bn(who, x, bn, batch_stats, residual)
+    y = Bn.apply(act, stats, float(bn.eps), float(bn.momentum), bn.running_mean, bn.running_var, x, residual, bn.weight, bn.bias)
     if stats:
         _bn_stats_written(bn)
     return y
 
 
-LEAKY_SLOPE = 0.1
-
-
-class BnLeaky(torch.autograd.Function):
-    """apply(stats, eps, momentum, running_mean, running_var, x [..,C], residual or None, gamma, beta) -> leaky_relu(bn(x), 0.1) +
-    residual (ymi_bn_leaky_fwd_nhwc_f32 / ymi_bn_leaky_bwd_nhwc_f32).  With a residual the forward's decisions z > 0 are kept as a bit
-    mask (1/32 of the map) and the backward reads them; without one it reads them from y."""
-
-    @staticmethod
-    def forward(ctx, stats, eps, momentum, rmean, rvar, x, residual, gamma, beta):
-        dev = x.device
-        with torch.cuda.device(dev), torch.no_grad():
-            xd = LC.f32(x, dev)
-            Cc = xd.shape[-1]
-            npos = xd.numel() // Cc
-            y = torch.empty_like(xd)
-            mean = torch.empty(Cc, dtype=torch.float32, device=dev)
-            invstd = torch.empty(Cc, dtype=torch.float32, device=dev)
-            rd = None if residual is None else LC.f32(residual, dev)
-            mask = None if residual is None else torch.empty((xd.numel() + 31) // 32, dtype=torch.int32, device=dev)
-            gd, bd = LC.f32(gamma, dev), LC.f32(beta, dev)
-            d = L.BnDesc()
-            d.x, d.res, d.gamma, d.beta = xd.data_ptr(), (None if rd is None else rd.data_ptr()), gd.data_ptr(), bd.data_ptr()
-            d.running_mean, d.running_var = rmean.data_ptr(), rvar.data_ptr()
-            d.y, d.mean, d.invstd = y.data_ptr(), mean.data_ptr(), invstd.data_ptr()
-            d.npos, d.C, d.training, d.relu, d.eps, d.momentum = npos, Cc, int(stats), 0, eps, momentum
-            ws = LC.workspace('BN', d, dev)
-            d.ws_bytes = ws.numel()
-            L.check(L.lib().ymi_bn_leaky_fwd_nhwc_f32(C.byref(d), None if mask is None else mask.data_ptr(), L.stream_ptr()),
-                    'ymi_bn_leaky_fwd_nhwc_f32')
-        # the inputs are saved too: autograd's version check refuses a backward after x or a parameter was edited in place
-        ctx.save_for_backward(x, gamma, beta, y, mean, invstd, *(() if residual is None else (residual, mask)))
-        ctx.stats, ctx.eps = int(stats), eps
-        ctx.dtypes = [x.dtype, None if residual is None else residual.dtype, gamma.dtype, beta.dtype]
-        return y
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, dy):
-        want_x, want_r, want_g, want_b = ctx.needs_input_grad[5:]
-        x, gamma, beta, y, mean, invstd = ctx.saved_tensors[:6]      # (the version check)
-        mask = ctx.saved_tensors[7] if len(ctx.saved_tensors) > 6 else None
-        if not (want_x or want_r or want_g or want_b):
-            return (None,) * 9
-        dev = x.device
-        with torch.cuda.device(dev), torch.no_grad():
-            xd, dyd, gd = LC.f32(x, dev), LC.f32(dy, dev), LC.f32(gamma, dev)
-            Cc = xd.shape[-1]
-            dx = torch.empty_like(xd) if want_x else None
-            dg = torch.empty(Cc, dtype=torch.float32, device=dev) if want_g else None
-            db = torch.empty(Cc, dtype=torch.float32, device=dev) if want_b else None
-            if dx is not None or dg is not None or db is not None:
-                d = L.BnDesc()
-                d.x, d.gamma, d.y, d.mean, d.invstd, d.dy = (xd.data_ptr(), gd.data_ptr(), y.data_ptr(), mean.data_ptr(),
-                                                             invstd.data_ptr(), dyd.data_ptr())
-                d.dx, d.dgamma, d.dbeta = (None if t is None else t.data_ptr() for t in (dx, dg, db))
-                d.npos, d.C, d.training, d.relu, d.eps = xd.numel() // Cc, Cc, ctx.stats, 0, ctx.eps
-                ws = LC.workspace('BN', d, dev)
-                d.ws_bytes = ws.numel()
-                L.check(L.lib().ymi_bn_leaky_bwd_nhwc_f32(C.byref(d), None if mask is None else mask.data_ptr(), L.stream_ptr()),
-                        'ymi_bn_leaky_bwd_nhwc_f32')
-            # the residual is added behind the activation: its gradient is dy itself
-            dres = dyd if want_r else None
-        out = [dx, dres, dg, db]
-        return (None,) * 5 + tuple(None if (t is None or dt is None) else t.to(dt) for t, dt in zip(out, ctx.dtypes))
+def batch_norm_act(x, bn, batch_stats=None, residual=None, relu=False):
+    """relu(bn(x) + residual) on NHWC x for an nn.BatchNorm2d `bn`.  batch_stats None follows bn.training; True: the batch statistics
+    (running_mean / running_var updated in place, num_batches_tracked incremented); False: the running statistics (frozen)."""
+    return _batch_norm('batch_norm_act', 'relu' if relu else None, x, bn, batch_stats, residual)
 
 
 def batch_norm_leaky(x, bn, batch_stats=None, residual=None):
     """leaky_relu(bn(x), 0.1) + residual on NHWC x for an nn.BatchNorm2d `bn`: the residual is added AFTER the activation (a
     DarkNetBlock's `conv2(conv1(x)) + x`).  batch_stats as in batch_norm_act."""
-    stats = _check_bn('batch_norm_leaky', x, bn, batch_stats, residual)
-    y = BnLeaky.apply(stats, float(bn.eps), float(bn.momentum), bn.running_mean, bn.running_var, x, residual, bn.weight, bn.bias)
-    if stats:
-        _bn_stats_written(bn)
-    return y
+    return _batch_norm('batch_norm_leaky', 'leaky', x, bn, batch_stats, residual)
 
 
-def check_bottleneck(block, name='block'):
-    """NotImplementedError naming what of a backbone block the kernels do not take."""
+def _check_block(who, block, name, dcn):
+    """What bottleneck (dcn False) and dcn_bottleneck (dcn True) refuse alike, named: the block's kind and every plain convolution
+    of it, in forward order."""
     from .. import modules as M
     if not isinstance(block, M.Bottleneck):
-        raise NotImplementedError('yolact_amd bottleneck: %s is a %s, which is not supported (a Bottleneck is)' % (name, type(block).__name__))
-    if block.use_dcn or not isinstance(block.conv2, torch.nn.Conv2d):
-        raise NotImplementedError('yolact_amd bottleneck: %s is a DCN block (use_dcn = True), which is not supported yet' % name)
-    convs = [('conv1', block.conv1, 1, 1), ('conv2', block.conv2, 3, block.stride), ('conv3', block.conv3, 1, 1)]
+        raise NotImplementedError('yolact_amd %s: %s is a %s, which is not supported (a Bottleneck is)' % (who, name, type(block).__name__))
+    if dcn and (not block.use_dcn or not isinstance(block.conv2, M.DCN)):
+        raise NotImplementedError('yolact_amd %s: %s is not a DCN block (use_dcn = False), which is not supported (bottleneck takes it)'
+                                  % (who, name))
+    if not dcn and (block.use_dcn or not isinstance(block.conv2, torch.nn.Conv2d)):
+        raise NotImplementedError('yolact_amd %s: %s is a DCN block (use_dcn = True), which is not supported yet' % (who, name))
+    convs = [('conv1', block.conv1, 1, 1)] + ([] if dcn else [('conv2', block.conv2, 3, block.stride)]) + [('conv3', block.conv3, 1, 1)]
     if block.downsample is not None:
         convs.append(('downsample.0', block.downsample[0], 1, block.stride))
     for n, m, k, st in convs:
         if (tuple(m.kernel_size), tuple(m.stride), tuple(m.padding), tuple(m.dilation), m.groups, m.bias is None) != \
                 ((k, k), (st, st), (k // 2, k // 2), (1, 1), 1, True):
-            raise NotImplementedError('yolact_amd bottleneck: %s.%s = %r is not supported (a bias-free %d x %d / stride %d / padding %d '
-                                      'is)' % (name, n, m, k, k, st, k // 2))
-        check_plain(m.weight, st, 'bottleneck %s.%s' % (name, n))
+            raise NotImplementedError('yolact_amd %s: %s.%s = %r is not supported (a bias-free %d x %d / stride %d / padding %d is)'
+                                      % (who, name, n, m, k, k, st, k // 2))
+        check_plain(m.weight, st, '%s %s.%s' % (who, name, n))
+
+
+def _bottleneck(x, block, batch_stats, conv2):
+    """backbone.py:37-57 on NHWC x: relu(bn1(conv1 x)), relu(bn2(conv2(.))), relu(bn3(conv3 .) + (downsample(x) or x)); conv2(map) is
+    how the block's middle convolution runs.  The order of the calls is part of train_net's gradient-summation contract."""
+    out = batch_norm_act(conv2d_plain(x, block.conv1.weight), block.bn1, batch_stats, relu=True)
+    out = batch_norm_act(conv2(out), block.bn2, batch_stats, relu=True)
+    out = conv2d_plain(out, block.conv3.weight)
+    res = x
+    if block.downsample is not None:
+        res = batch_norm_act(conv2d_plain(x, block.downsample[0].weight, block.stride), block.downsample[1], batch_stats)
+    return batch_norm_act(out, block.bn3, batch_stats, residual=res, relu=True)
+
+
+def check_bottleneck(block, name='block'):
+    """NotImplementedError naming what of a backbone block the kernels do not take."""
+    _check_block('bottleneck', block, name, False)
 
 
 def bottleneck(x, block, batch_stats=None):
     """backbone.py:37-57 on NHWC x: relu(bn1(conv1 x)), relu(bn2(conv2 .)), relu(bn3(conv3 .) + (downsample(x) or x))."""
     L.require_cuda(x, 'bottleneck x')
     check_bottleneck(block)
-    out = batch_norm_act(conv2d_plain(x, block.conv1.weight), block.bn1, batch_stats, relu=True)
-    out = batch_norm_act(conv2d_plain(out, block.conv2.weight, block.stride), block.bn2, batch_stats, relu=True)
-    out = conv2d_plain(out, block.conv3.weight)
-    res = x
-    if block.downsample is not None:
-        res = batch_norm_act(conv2d_plain(x, block.downsample[0].weight, block.stride), block.downsample[1], batch_stats)
-    return batch_norm_act(out, block.bn3, batch_stats, residual=res, relu=True)
+    return _bottleneck(x, block, batch_stats, lambda t: conv2d_plain(t, block.conv2.weight, block.stride))
 
 
 def check_deform(weight, stride=1, padding=1, dilation=1, deformable_groups=1, who='deform_conv'):
@@ -990,22 +940,7 @@ def deform_conv(x, om, weight, bias, stride=1):
 
 def check_dcn_bottleneck(block, name='block'):
     """NotImplementedError naming what of a DCN backbone block (a modules.Bottleneck with use_dcn = True) the kernels do not take."""
-    from .. import modules as M
-    if not isinstance(block, M.Bottleneck):
-        raise NotImplementedError('yolact_amd dcn_bottleneck: %s is a %s, which is not supported (a Bottleneck is)'
-                                  % (name, type(block).__name__))
-    if not block.use_dcn or not isinstance(block.conv2, M.DCN):
-        raise NotImplementedError('yolact_amd dcn_bottleneck: %s is not a DCN block (use_dcn = False), which is not supported '
-                                  '(bottleneck takes it)' % name)
-    convs = [('conv1', block.conv1, 1, 1), ('conv3', block.conv3, 1, 1)]
-    if block.downsample is not None:
-        convs.append(('downsample.0', block.downsample[0], 1, block.stride))
-    for n, m, k, st in convs:
-        if (tuple(m.kernel_size), tuple(m.stride), tuple(m.padding), tuple(m.dilation), m.groups, m.bias is None) != \
-                ((k, k), (st, st), (k // 2, k // 2), (1, 1), 1, True):
-            raise NotImplementedError('yolact_amd dcn_bottleneck: %s.%s = %r is not supported (a bias-free %d x %d / stride %d / '
-                                      'padding %d is)' % (name, n, m, k, k, st, k // 2))
-        check_plain(m.weight, st, 'dcn_bottleneck %s.%s' % (name, n))
+    _check_block('dcn_bottleneck', block, name, True)
     dcn, st = block.conv2, block.stride
     if tuple(dcn.stride) != (st, st):
         raise NotImplementedError('yolact_amd dcn_bottleneck: %s.conv2 has stride %r in a block of stride %r, which is not supported'
@@ -1026,32 +961,32 @@ def dcn_bottleneck(x, block, batch_stats=None):
     check_dcn_bottleneck(block)
     dcn = block.conv2
     com = dcn.conv_offset_mask
-    out = batch_norm_act(conv2d_plain(x, block.conv1.weight), block.bn1, batch_stats, relu=True)
-    om = conv2d_act(out, com.weight, com.bias, 1) if block.stride == 1 else conv2d_down(out, com.weight, com.bias)
-    out = deform_conv(out, om, dcn.weight, dcn.bias, block.stride)
-    out = batch_norm_act(out, block.bn2, batch_stats, relu=True)
-    out = conv2d_plain(out, block.conv3.weight)
-    res = x
-    if block.downsample is not None:
-        res = batch_norm_act(conv2d_plain(x, block.downsample[0].weight, block.stride), block.downsample[1], batch_stats)
-    return batch_norm_act(out, block.bn3, batch_stats, residual=res, relu=True)
+
+    def conv2(out):
+        om = conv2d_act(out, com.weight, com.bias, 1) if block.stride == 1 else conv2d_down(out, com.weight, com.bias)
+        return deform_conv(out, om, dcn.weight, dcn.bias, block.stride)
+    return _bottleneck(x, block, batch_stats, conv2)
 
 
-STEM_K, STEM_PAD, STEM_STRIDE = 7, 3, 2
+# the two convolutions of the 3-channel image: (name, k, pad, stride, weight-gradient descriptor, its workspace kind, its entry)
+ImageConvSpec = collections.namedtuple('ImageConvSpec', 'name k pad stride desc ws entry')
+STEM = ImageConvSpec('stem_conv', 7, 3, 2, L.StemWgradDesc, 'STEM_WGRAD', 'ymi_stem_wgrad_nhwc_f32')
+PRE = ImageConvSpec('preconv', 3, 1, 1, L.PreconvWgradDesc, 'PRECONV_WGRAD', 'ymi_preconv_wgrad_nhwc_f32')
 
 
-def check_stem(weight, stride=2, padding=3, dilation=1, groups=1, bias=None, who='stem_conv'):
-    """NotImplementedError naming what of the stem convolution the kernels do not take: anything but a bias-free 7 x 7 / stride 2 /
-    padding 3 / dilation 1 / groups 1 convolution of 3 input channels."""
+def _check_image_conv(s, who, weight, stride, padding, dilation, groups, bias):
+    """NotImplementedError naming what of a convolution of the image the kernels do not take: anything but a bias-free s.k x s.k /
+    stride s.stride / padding s.pad / dilation 1 / groups 1 convolution of 3 input channels to a multiple of 32 output channels."""
     if weight.dim() != 4:
-        raise NotImplementedError('yolact_amd %s: a weight of shape %s is not supported ([Cout,3,7,7] is)' % (who, tuple(weight.shape)))
+        raise NotImplementedError('yolact_amd %s: a weight of shape %s is not supported ([Cout,3,%d,%d] is)'
+                                  % (who, tuple(weight.shape), s.k, s.k))
     Cout, Cin, kh, kw = weight.shape
-    if (kh, kw) != (STEM_K, STEM_K):
-        raise NotImplementedError('yolact_amd %s: a %d x %d kernel is not supported (7 x 7 is)' % (who, kh, kw))
-    if isinstance(stride, str) or _pair(stride) != (STEM_STRIDE, STEM_STRIDE):
-        raise NotImplementedError('yolact_amd %s: stride = %r is not supported (stride 2 is)' % (who, stride))
-    if isinstance(padding, str) or _pair(padding) != (STEM_PAD, STEM_PAD):
-        raise NotImplementedError('yolact_amd %s: padding = %r is not supported (padding 3 is)' % (who, padding))
+    if (kh, kw) != (s.k, s.k):
+        raise NotImplementedError('yolact_amd %s: a %d x %d kernel is not supported (%d x %d is)' % (who, kh, kw, s.k, s.k))
+    if isinstance(stride, str) or _pair(stride) != (s.stride, s.stride):
+        raise NotImplementedError('yolact_amd %s: stride = %r is not supported (stride %d is)' % (who, stride, s.stride))
+    if isinstance(padding, str) or _pair(padding) != (s.pad, s.pad):
+        raise NotImplementedError('yolact_amd %s: padding = %r is not supported (padding %d is)' % (who, padding, s.pad))
     if _pair(dilation) != (1, 1):
         raise NotImplementedError('yolact_amd %s: dilation = %r is not supported (dilation 1 is)' % (who, dilation))
     if groups != 1:
@@ -1064,66 +999,90 @@ def check_stem(weight, stride=2, padding=3, dilation=1, groups=1, bias=None, who
         raise NotImplementedError('yolact_amd %s: Cout = %d is not supported (a multiple of 32 output channels is)' % (who, Cout))
 
 
-def _pack_stem(w):
-    """[Cout,3,7,7] -> [ceil128(Cout)][224], k = (ky*7 + kx)*4 + c with c = 3 and k >= 196 zero (a permute of the CURRENT values)."""
-    Cout = int(w.shape[0])
-    out = torch.zeros(_ceil(Cout, 128), _ceil(STEM_K * STEM_K * 4, 32), dtype=torch.float32, device=w.device)
-    out[:Cout, :STEM_K * STEM_K * 4] = F.pad(w.permute(0, 2, 3, 1), (0, 1)).reshape(Cout, STEM_K * STEM_K * 4)
+def check_stem(weight, stride=2, padding=3, dilation=1, groups=1, bias=None, who='stem_conv'):
+    """What of the stem convolution (7 x 7 / stride 2 / padding 3, backbone.py:77) the kernels do not take (_check_image_conv)."""
+    _check_image_conv(STEM, who, weight, stride, padding, dilation, groups, bias)
+
+
+def check_preconv(weight, stride=1, padding=1, dilation=1, groups=1, bias=None, who='preconv'):
+    """What of DarkNet's pre-convolution (3 x 3 / stride 1 / padding 1, backbone.py:268) the kernels do not take (_check_image_conv)."""
+    _check_image_conv(PRE, who, weight, stride, padding, dilation, groups, bias)
+
+
+def _pack_image(w):
+    """[Cout,3,k,k] -> [ceil128(Cout)][ceil32(4*k*k)], column (ky*k + kx)*4 + c with c = 3 and the columns from 4*k*k on zero (a
+    permute of the CURRENT values): [..][224] for the stem, [..][64] for the pre-convolution."""
+    Cout, _, k, _ = w.shape
+    out = torch.zeros(_ceil(Cout, 128), _ceil(k * k * 4, 32), dtype=torch.float32, device=w.device)
+    out[:Cout, :k * k * 4] = F.pad(w.permute(0, 2, 3, 1), (0, 1)).reshape(Cout, k * k * 4)
     return out
 
 
-class StemConv(torch.autograd.Function):
-    """apply(x4 [B,H,W,4], weight [Cout,3,7,7]) -> [B,Ho,Wo,Cout]; differentiable in the weight."""
+class ImageConv(torch.autograd.Function):
+    """apply(spec, x4 [B,H,W,4], weight [Cout,3,k,k]) -> [B,Ho,Wo,Cout]; differentiable in the weight.  One ymi_conv2d_nhwc_f32 launch
+    through the engine's Cin-4 loader with the filter's fourth input channel zero; the backward is the spec's weight-gradient entry
+    on the SAME x4 (its fourth channel reaches nothing), then _unpack_dw."""
 
     @staticmethod
-    def forward(ctx, x4, weight):
+    def forward(ctx, s, x4, weight):
         dev = x4.device
         Cout = int(weight.shape[0])
         with torch.cuda.device(dev), torch.no_grad():
             xd = LC.f32(x4, dev)
             B, H, W, _ = xd.shape
-            Ho, Wo = _out_size(H, W, STEM_K, STEM_PAD, STEM_STRIDE)
+            Ho, Wo = _out_size(H, W, s.k, s.pad, s.stride)
             y = torch.empty(B, Ho, Wo, Cout, dtype=torch.float32, device=dev)
-            _engine_conv(xd, 4, _pack_stem(weight.detach().float()), None, 4, Cout, STEM_K, STEM_PAD, [(0, Cout, L.ACT_NONE, y)],
-                         stride=STEM_STRIDE)
+            _engine_conv(xd, 4, _pack_image(weight.detach().float()), None, 4, Cout, s.k, s.pad, [(0, Cout, L.ACT_NONE, y)],
+                         stride=s.stride)
         ctx.save_for_backward(x4, weight)                   # (the version check)
-        ctx.dtype = weight.dtype
+        ctx.spec, ctx.dtype = s, weight.dtype
         return y
 
     @staticmethod
     @once_differentiable
     def backward(ctx, dy):
         x4, weight = ctx.saved_tensors                      # (the version check)
-        if not ctx.needs_input_grad[1]:
-            return None, None
-        dev = x4.device
+        if not ctx.needs_input_grad[2]:
+            return None, None, None
+        s, dev = ctx.spec, x4.device
         Cout = int(weight.shape[0])
         with torch.cuda.device(dev), torch.no_grad():
             xd, g = LC.f32(x4, dev), LC.f32(dy, dev)
             B, H, W, _ = xd.shape
-            dw = torch.empty(STEM_K * STEM_K * 3, Cout, dtype=torch.float32, device=dev)
-            d = L.StemWgradDesc()
+            dw = torch.empty(s.k * s.k * 3, Cout, dtype=torch.float32, device=dev)
+            d = s.desc()
             d.x, d.g, d.dw = xd.data_ptr(), g.data_ptr(), dw.data_ptr()
             d.B, d.H, d.W, d.Cout, d.ldg = B, H, W, Cout, Cout
-            ws = LC.workspace('STEM_WGRAD', d, dev)
+            ws = LC.workspace(s.ws, d, dev)
             d.ws_bytes = ws.numel()
-            L.check(L.lib().ymi_stem_wgrad_nhwc_f32(C.byref(d), L.stream_ptr()), 'ymi_stem_wgrad_nhwc_f32')
-            out = _unpack_dw(dw, STEM_K, 3)
-        return None, out.to(ctx.dtype)
+            L.check(getattr(L.lib(), s.entry)(C.byref(d), L.stream_ptr()), s.entry)
+            out = _unpack_dw(dw, s.k, 3)
+        return None, None, out.to(ctx.dtype)
+
+
+def _image_conv(s, x4, weight, bias, stride, padding, dilation, groups):
+    L.require_cuda(x4, s.name + ' x4')
+    L.require_cuda(weight, s.name + ' weight')
+    _check_image_conv(s, s.name, weight, stride, padding, dilation, groups, bias)
+    if x4.dim() != 4 or x4.shape[3] != 4:
+        raise ValueError('%s: x4 %s ([B,H,W,4], the image padded to 4 channels, is expected)' % (s.name, tuple(x4.shape)))
+    # nothing upstream of the image needs a gradient, and returning None would silently give a zero one
+    if x4.requires_grad:
+        raise NotImplementedError('yolact_amd %s: an x4 that requires grad is not supported (the gradient with respect to the '
+                                  'image is not computed; detach it)' % s.name)
+    return ImageConv.apply(s, x4, weight)
 
 
 def stem_conv(x4, weight, bias=None, stride=2, padding=3, dilation=1, groups=1):
     """conv2d(x, weight, None, stride 2, padding 3) for a [Cout,3,7,7] weight on x4 [B,H,W,4], the NHWC image with a fourth channel of
     zeros -> NHWC.  Differentiable in the weight only."""
-    L.require_cuda(x4, 'stem_conv x4')
-    L.require_cuda(weight, 'stem_conv weight')
-    check_stem(weight, stride, padding, dilation, groups, bias)
-    if x4.dim() != 4 or x4.shape[3] != 4:
-        raise ValueError('stem_conv: x4 %s ([B,H,W,4], the image padded to 4 channels, is expected)' % (tuple(x4.shape),))
-    if x4.requires_grad:
-        raise NotImplementedError('yolact_amd stem_conv: an x4 that requires grad is not supported (the gradient with respect to the '
-                                  'image is not computed; detach it)')
-    return StemConv.apply(x4, weight)
+    return _image_conv(STEM, x4, weight, bias, stride, padding, dilation, groups)
+
+
+def preconv(x4, weight, bias=None, stride=1, padding=1, dilation=1, groups=1):
+    """conv2d(x, weight, None, stride 1, padding 1) for a [Cout,3,3,3] weight (DarkNet's _preconv, backbone.py:268) on x4 [B,H,W,4], the
+    NHWC image with a fourth channel of zeros -> NHWC.  Differentiable in the weight only, like stem_conv."""
+    return _image_conv(PRE, x4, weight, bias, stride, padding, dilation, groups)
 
 
 class MaxPool3x3S2(torch.autograd.Function):
@@ -1163,94 +1122,6 @@ def max_pool_3x3_s2(x):
     if x.dim() != 4 or x.shape[3] % 4 != 0 or min(x.shape) < 1:
         raise NotImplementedError('yolact_amd max_pool_3x3_s2: x %s is not supported ([B,H,W,C] with C %% 4 == 0 is)' % (tuple(x.shape),))
     return MaxPool3x3S2.apply(x)
-
-
-PRE_K, PRE_PAD, PRE_STRIDE = 3, 1, 1
-
-
-def check_preconv(weight, stride=1, padding=1, dilation=1, groups=1, bias=None, who='preconv'):
-    """NotImplementedError naming what of DarkNet's pre-convolution the kernels do not take: anything but a bias-free 3 x 3 / stride 1 /
-    padding 1 / dilation 1 / groups 1 convolution of 3 input channels to a multiple of 32 output channels."""
-    if weight.dim() != 4:
-        raise NotImplementedError('yolact_amd %s: a weight of shape %s is not supported ([Cout,3,3,3] is)' % (who, tuple(weight.shape)))
-    Cout, Cin, kh, kw = weight.shape
-    if (kh, kw) != (PRE_K, PRE_K):
-        raise NotImplementedError('yolact_amd %s: a %d x %d kernel is not supported (3 x 3 is)' % (who, kh, kw))
-    if isinstance(stride, str) or _pair(stride) != (PRE_STRIDE, PRE_STRIDE):
-        raise NotImplementedError('yolact_amd %s: stride = %r is not supported (stride 1 is)' % (who, stride))
-    if isinstance(padding, str) or _pair(padding) != (PRE_PAD, PRE_PAD):
-        raise NotImplementedError('yolact_amd %s: padding = %r is not supported (padding 1 is)' % (who, padding))
-    if _pair(dilation) != (1, 1):
-        raise NotImplementedError('yolact_amd %s: dilation = %r is not supported (dilation 1 is)' % (who, dilation))
-    if groups != 1:
-        raise NotImplementedError('yolact_amd %s: groups = %r is not supported (groups 1 is)' % (who, groups))
-    if Cin != 3:
-        raise NotImplementedError('yolact_amd %s: Cin = %d is not supported (3 input channels are, on an input padded to 4)' % (who, Cin))
-    if bias is not None:
-        raise NotImplementedError('yolact_amd %s: a bias is not supported (a bias-free convolution is)' % who)
-    if Cout % 32 != 0:
-        raise NotImplementedError('yolact_amd %s: Cout = %d is not supported (a multiple of 32 output channels is)' % (who, Cout))
-
-
-def _pack_preconv(w):
-    """[Cout,3,3,3] -> [ceil128(Cout)][64], k = (ky*3 + kx)*4 + c with c = 3 and k >= 36 zero (a permute of the CURRENT values)."""
-    Cout = int(w.shape[0])
-    out = torch.zeros(_ceil(Cout, 128), _ceil(PRE_K * PRE_K * 4, 32), dtype=torch.float32, device=w.device)
-    out[:Cout, :PRE_K * PRE_K * 4] = F.pad(w.permute(0, 2, 3, 1), (0, 1)).reshape(Cout, PRE_K * PRE_K * 4)
-    return out
-
-
-class PreConv(torch.autograd.Function):
-    """apply(x4 [B,H,W,4], weight [Cout,3,3,3]) -> [B,H,W,Cout]; differentiable in the weight."""
-
-    @staticmethod
-    def forward(ctx, x4, weight):
-        dev = x4.device
-        Cout = int(weight.shape[0])
-        with torch.cuda.device(dev), torch.no_grad():
-            xd = LC.f32(x4, dev)
-            B, H, W, _ = xd.shape
-            y = torch.empty(B, H, W, Cout, dtype=torch.float32, device=dev)
-            _engine_conv(xd, 4, _pack_preconv(weight.detach().float()), None, 4, Cout, PRE_K, PRE_PAD, [(0, Cout, L.ACT_NONE, y)],
-                         stride=PRE_STRIDE)
-        ctx.save_for_backward(x4, weight)                   # (the version check)
-        ctx.dtype = weight.dtype
-        return y
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, dy):
-        x4, weight = ctx.saved_tensors                      # (the version check)
-        if not ctx.needs_input_grad[1]:
-            return None, None
-        dev = x4.device
-        Cout = int(weight.shape[0])
-        with torch.cuda.device(dev), torch.no_grad():
-            xd, g = LC.f32(x4, dev), LC.f32(dy, dev)
-            B, H, W, _ = xd.shape
-            dw = torch.empty(PRE_K * PRE_K * 3, Cout, dtype=torch.float32, device=dev)
-            d = L.PreconvWgradDesc()
-            d.x, d.g, d.dw = xd.data_ptr(), g.data_ptr(), dw.data_ptr()
-            d.B, d.H, d.W, d.Cout, d.ldg = B, H, W, Cout, Cout
-            ws = LC.workspace('PRECONV_WGRAD', d, dev)
-            d.ws_bytes = ws.numel()
-            L.check(L.lib().ymi_preconv_wgrad_nhwc_f32(C.byref(d), L.stream_ptr()), 'ymi_preconv_wgrad_nhwc_f32')
-            out = _unpack_dw(dw, PRE_K, 3)
-        return None, out.to(ctx.dtype)
-
-
-def preconv(x4, weight, bias=None, stride=1, padding=1, dilation=1, groups=1):
-    """conv2d(x, weight, None, stride 1, padding 1) for a [Cout,3,3,3] weight (DarkNet's _preconv, backbone.py:268) on x4 [B,H,W,4], the
-    NHWC image with a fourth channel of zeros -> NHWC.  Differentiable in the weight only, like stem_conv."""
-    L.require_cuda(x4, 'preconv x4')
-    L.require_cuda(weight, 'preconv weight')
-    check_preconv(weight, stride, padding, dilation, groups, bias)
-    if x4.dim() != 4 or x4.shape[3] != 4:
-        raise ValueError('preconv: x4 %s ([B,H,W,4], the image padded to 4 channels, is expected)' % (tuple(x4.shape),))
-    if x4.requires_grad:
-        raise NotImplementedError('yolact_amd preconv: an x4 that requires grad is not supported (the gradient with respect to the '
-                                  'image is not computed; detach it)')
-    return PreConv.apply(x4, weight)
 
 
 def _check_unit(seq, who, name):

@@ -15,6 +15,18 @@ from .config import act_name, make_priors_host
 from .layers import train_ops as TO
 
 
+def conv_of(x, m, act, w=None, b=None):
+    """TO.conv2d_act with the geometry of the nn.Conv2d m, on its own parameters or on the aliases (w, b) of them."""
+    return TO.conv2d_act(x, m.weight if w is None else w, m.bias if b is None else b, m.padding, act, stride=m.stride,
+                         dilation=m.dilation, groups=m.groups)
+
+
+def image4(x_nchw):
+    """The NCHW image as NHWC fp32 with a fourth channel of zeros, built once with torch operations and detached: what stem_conv and
+    preconv read, forward and backward."""
+    return nn.functional.pad(x_nchw.detach().to(torch.float32).permute(0, 2, 3, 1), (0, 1)).contiguous()
+
+
 def apply_net(seq, x, last_act=None, params=None):
     """A make_net Sequential (utils/functions.py:163-213) on NHWC x through layers/train_ops: Conv2d (+ the ReLU behind it),
     InterpolateModule (+ the ReLU behind it).  last_act: the activation applied after a final layer that has no ReLU of its own.
@@ -27,8 +39,7 @@ def apply_net(seq, x, last_act=None, params=None):
         relu = i + 1 < len(mods) and isinstance(mods[i + 1], nn.ReLU)
         act = 'relu' if relu else (last_act if i == len(mods) - 1 else None)
         if isinstance(m, nn.Conv2d):
-            w, b = (m.weight, m.bias) if params is None else (params.pop(0), params.pop(0))
-            x = TO.conv2d_act(x, w, b, m.padding, act, stride=m.stride, dilation=m.dilation, groups=m.groups)
+            x = conv_of(x, m, act) if params is None else conv_of(x, m, act, params.pop(0), params.pop(0))
         elif isinstance(m, M.InterpolateModule):
             if m.scale_factor != 2 or act not in (None, 'relu'):
                 raise NotImplementedError('yolact_amd forward_heads: an interpolation by %r followed by %r is not supported '
@@ -64,8 +75,7 @@ def stem(net, x_nchw, batch_stats=None):
     operations; the convolution's backward reads that same tensor."""
     bb = net.backbone
     with torch.cuda.device(x_nchw.device):
-        x4 = nn.functional.pad(x_nchw.detach().to(torch.float32).permute(0, 2, 3, 1), (0, 1)).contiguous()
-        y = TO.stem_conv(x4, bb.conv1.weight)
+        y = TO.stem_conv(image4(x_nchw), bb.conv1.weight)
         y = TO.batch_norm_act(y, bb.bn1, batch_stats, relu=True)
         return TO.max_pool_3x3_s2(y)
 
@@ -94,9 +104,8 @@ def darknet(net, x_nchw, batch_stats=None):
     TO.check_darknet(bb)
     outs = []
     with torch.cuda.device(x_nchw.device):
-        x4 = nn.functional.pad(x_nchw.detach().to(torch.float32).permute(0, 2, 3, 1), (0, 1)).contiguous()
         conv, bn = bb._preconv[0], bb._preconv[1]
-        x = TO.batch_norm_leaky(TO.preconv(x4, conv.weight), bn, batch_stats)
+        x = TO.batch_norm_leaky(TO.preconv(image4(x_nchw), conv.weight), bn, batch_stats)
         for layer in bb.layers:
             mods = list(layer)
             x = TO.dark_unit(x, mods[0], batch_stats)
@@ -111,18 +120,17 @@ def fpn(net, feats):
     """FPN.forward (yolact.py:311-360) on the selected stage outputs, finest first, for the variant Yolact.__init__ insists on."""
     f = net.fpn
     n = len(feats)
-    conv = lambda x, m, act: TO.conv2d_act(x, m.weight, m.bias, m.padding, act, stride=m.stride, dilation=m.dilation, groups=m.groups)
     with torch.cuda.device(feats[0].device):
         # lat_layers and pred_layers are stored deepest level first (yolact.py:286-296, 324-341)
         out, x = [None] * n, None
         for i, lat in enumerate(f.lat_layers):
             j = n - 1 - i
-            lateral = conv(feats[j], lat, None)
+            lateral = conv_of(feats[j], lat, None)
             x = lateral if x is None else TO.upsample_add(x, lateral)
             out[j] = x
         for i, pred in enumerate(f.pred_layers):
             j = n - 1 - i
-            out[j] = conv(out[j], pred, 'relu')
+            out[j] = conv_of(out[j], pred, 'relu')
         for down in f.downsample_layers:
             if tuple(down.stride) != (2, 2) or tuple(down.padding) != (down.kernel_size[0] // 2,) * 2 or \
                     tuple(down.dilation) != (1, 1) or down.groups != 1:
@@ -160,10 +168,7 @@ def heads(net, feats):
         pred = {'loc': torch.cat(loc, 1), 'conf': torch.cat(conf, 1), 'mask': torch.cat(mask, 1),
                 'priors': priors(net, [tuple(f.shape[1:3]) for f in feats], cfg, feats[0].device), 'proto': proto}
         if cfg.use_semantic_segmentation_loss:
-            sc = net.semantic_seg_conv
-            segm = TO.conv2d_act(feats[0], sc.weight, sc.bias, sc.padding, None, stride=sc.stride, dilation=sc.dilation,
-                                 groups=sc.groups)
-            pred['segm'] = segm.permute(0, 3, 1, 2)
+            pred['segm'] = conv_of(feats[0], net.semantic_seg_conv, None).permute(0, 3, 1, 2)
     return pred
 
 
