@@ -580,6 +580,51 @@ int ymi_jpeg_encode_bgr_u8(const ymi_jpeg_enc_desc *d, void *stream);
 int ymi_coco_poly_fill_u8(const double *xy, int k, int h, int w, uint8_t *mask);          /* k vertices, x0 y0 x1 y1 ... */
 int ymi_coco_rle_fill_u8(const uint32_t *counts, long n, int h, int w, uint8_t *mask);    /* uncompressed counts */
 int ymi_coco_rle_string_fill_u8(const char *s, long len, int h, int w, uint8_t *mask);    /* compressed 'counts' string */
+/* HOST.  rleFrString alone: the compressed string's counts (at most len of them) into counts[cap]; returns how many, or
+ * YMI_ENULL / YMI_EARG (len, cap < 0, cap too small) / YMI_EFORMAT (what ymi_coco_rle_string_fill_u8 returns for the string). */
+int64_t ymi_coco_rle_string_counts(const char *s, long len, uint32_t *counts, int64_t cap);
+
+/* -- the same masks rasterised on the DEVICE (csrc/coco_mask.hip): all annotations of one image, or of a batch of images with
+ * their own h, w, in ONE call and ONE upload.  Record i writes out [h,w] uint8 ROW-major, every byte 0 or 1 (nothing is
+ * OR-ed: the caller zeroes nothing), byte-equal to ymi_coco_poly_fill_u8 looped over the record's polygons
+ * (YMI_COCO_POLY) or to ymi_coco_rle_fill_u8 (YMI_COCO_COUNTS; a compressed string goes through
+ * ymi_coco_rle_string_counts first) on a zeroed mask.
+ *   One workgroup per record.  Polygon: every point of the 5x upsampled boundary walk is recomputed from its edge in fp64
+ *   with the host's operations in the host's order ((int)(5 v + .5), s = (double)(ye - ys) / dx, (int)(ys + s t + .5),
+ *   (xd + .5) / 5 - .5, floor / clamp / ceil; no contraction, IEEE division), compared with its predecessor (an edge's
+ *   first point: the previous edge's last), and a qualifying crossing toggles bit x h + y of a COLUMN-major bitmap of
+ *   h w + 1 bits in LDS (integer atomic XOR: commutative, so the bits do not depend on the order).  A prefix XOR over the
+ *   whole bitmap, carried across column ends as the host's sorted run lengths carry it, is the polygon; it is OR-ed into the
+ *   record's union bitmap.  Counts: the prefix sums of the counts are the toggled bits, then the same prefix XOR.  Last, the
+ *   union bitmap is transposed into the row-major bytes with 4-byte stores (single bytes up to out's alignment and at the end).
+ * LIMIT: the two bitmaps of a record must fit the 160 KiB of LDS a gfx950 workgroup may declare:
+ * h * w <= YMI_COCO_MASK_MAX_PIXELS = 640000 (800 x 800), otherwise YMI_EUNSUPPORTED (rasterise that annotation on the host).
+ * Validated on the host before anything is copied or launched, with the host codec's rules and codes -- the kernel reports
+ * nothing.  YMI_ENULL: the descriptor, recs, ws, a record's out, xy / poly_len with a polygon record, counts with a counts
+ * record; YMI_EARG: n < 1, a record's h, w <= 0, an unknown kind, n < 0 (a polygon record without polygons is the empty mask), a polygon
+ * of < 1 vertices, a coordinate that is NaN or |c| > 3 max(w, h) + 1024; YMI_EFORMAT: a run past h w, counts that do not sum to
+ * h w; YMI_ESHAPE: a record's range outside its table (n_vert, n_poly, n_counts), ws_bytes too small, ws not 16-byte
+ * aligned; YMI_EUNSUPPORTED: above.  The table (vertices, records, polygon lengths, counts) reaches the device in one copy
+ * into ws from pageable host memory, enqueued on `stream`: the caller's arrays may be reused when the call returns. */
+#define YMI_COCO_MASK_MAX_PIXELS 640000
+enum { YMI_COCO_POLY = 0, YMI_COCO_COUNTS = 1 };
+typedef struct ymi_coco_mask_rec {
+  uint8_t *out;             /* DEVICE [h,w] */
+  int32_t kind, h, w, n;    /* n: polygons (YMI_COCO_POLY) | counts (YMI_COCO_COUNTS) */
+  int32_t first;            /* POLY: the record's first entry of poly_len; COUNTS: its first entry of counts */
+  int32_t xy_first;         /* POLY: its first VERTEX of xy (the polygons' vertices follow one another) */
+} ymi_coco_mask_rec;
+typedef struct ymi_coco_mask_desc {
+  const ymi_coco_mask_rec *recs;  /* HOST [n] */
+  const double *xy;               /* HOST [n_vert,2]: x0 y0 x1 y1 ... of every polygon of every record */
+  const int32_t *poly_len;        /* HOST [n_poly]: vertices of each polygon */
+  const uint32_t *counts;         /* HOST [n_counts] */
+  void *ws;                       /* DEVICE, ymi_workspace_bytes(YMI_WS_COCO_MASK, desc) bytes, 16-byte aligned */
+  int64_t ws_bytes;
+  int64_t n_vert, n_poly, n_counts;
+  int32_t n, _pad0;
+} ymi_coco_mask_desc;
+int ymi_coco_masks_u8(const ymi_coco_mask_desc *d, void *stream);
 
 /* -- DCNv2 forward (external/DCNv2/src/vision.cpp:5, dcn_v2.h:9-39, dcn_v2_cuda.cu:42-172) ---- */
 typedef struct {
@@ -1227,9 +1272,11 @@ enum {
   YMI_WS_AUGMENT = 27,          /* desc: ymi_augment_desc, B / n_masks read -> its ws: B records, n_masks (image, instance) pairs and B
                                  * pairs of resize scales, B * sizeof(ymi_augment_rec) + 8 n_masks + 16 B bytes, each part padded to 16 */
   YMI_WS_PRECONV_WGRAD = 28,    /* desc: ymi_preconv_wgrad_desc, the shape read -> its ws: chunks * 27 * Cout floats, padded to 16 */
-  YMI_WS_CONV_WGRAD_H2 = 29     /* desc: ymi_conv_wgrad_desc, the shape read -> ymi_conv_wgrad_nhwc_h2's ws: the two parts of
+  YMI_WS_CONV_WGRAD_H2 = 29,    /* desc: ymi_conv_wgrad_desc, the shape read -> ymi_conv_wgrad_nhwc_h2's ws: the two parts of
                                  * YMI_WS_CONV_WGRAD, then kh*kw * chunks * per + 64 and chunks * per + 64 table entries (per = the
                                  * positions of a chunk) and 2048 partial bounds, 4 bytes each, each part padded to 16 */
+  YMI_WS_COCO_MASK = 30         /* desc: ymi_coco_mask_desc, n / n_vert / n_poly / n_counts read -> its ws: 16 n_vert +
+                                 * n * sizeof(ymi_coco_mask_rec) + 4 n_poly + 4 n_counts bytes, each part padded to 16 */
 };
 typedef struct { int32_t A, B; int64_t n; } ymi_mask_iou_shape;
 typedef struct { int32_t N, h, w, cap; } ymi_rle_shape;      /* cap <= 0: the safe capacity h*w + 1 */

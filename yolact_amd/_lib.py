@@ -247,6 +247,23 @@ class AugmentDesc(C.Structure):
                 ('masks_u8', C.c_int32), ('mean_bgr', C.c_float * 3), ('std_bgr', C.c_float * 3)]
 
 
+COCO_POLY, COCO_COUNTS = 0, 1              # ymi_coco_mask_rec.kind (include/yolact_amd.h YMI_COCO_*)
+COCO_MASK_MAX_PIXELS = 640000               # include/yolact_amd.h YMI_COCO_MASK_MAX_PIXELS: h * w of one device-rasterised mask
+
+
+class CocoMaskRec(C.Structure):
+    """include/yolact_amd.h ymi_coco_mask_rec."""
+    _fields_ = [('out', C.c_void_p), ('kind', C.c_int32), ('h', C.c_int32), ('w', C.c_int32), ('n', C.c_int32),
+                ('first', C.c_int32), ('xy_first', C.c_int32)]
+
+
+class CocoMaskDesc(C.Structure):
+    """include/yolact_amd.h ymi_coco_mask_desc."""
+    _fields_ = [('recs', C.POINTER(CocoMaskRec)), ('xy', C.c_void_p), ('poly_len', C.c_void_p), ('counts', C.c_void_p),
+                ('ws', C.c_void_p), ('ws_bytes', C.c_int64),
+                ('n_vert', C.c_int64), ('n_poly', C.c_int64), ('n_counts', C.c_int64), ('n', C.c_int32), ('_pad0', C.c_int32)]
+
+
 SGD_CHUNK = 4096                    # include/yolact_amd.h YMI_SGD_CHUNK: elements of one tensor a block updates at a time
 
 
@@ -363,7 +380,7 @@ class RleShape(C.Structure):
 (WS_WINO_V, WS_WINO_M, WS_SPLITK, WS_MASK_IOU, WS_JPEG_COEFS, WS_JPEG_PLANES, WS_DETECT_SCORES_T, WS_DETECT_PER_PRIOR,
  WS_DETECT_CAND, WS_DETECT_REC, WS_AMAX_SLOT, WS_RLE_COUNTS, WS_DETECT_GREEDY, WS_JPEG_ENC, WS_JPEG_ENC_OUT,
  WS_MASK_LOSS, WS_MATCH, WS_BOX_LOSS, WS_CLASS_LOSS, WS_SEGM_LOSS, WS_MASKIOU_INPUT, WS_CONV_BWD, WS_MASKIOU_HEAD,
- WS_CONV_WGRAD, WS_BN, WS_STEM_WGRAD, WS_AUGMENT, WS_PRECONV_WGRAD, WS_CONV_WGRAD_H2) = range(1, 30)
+ WS_CONV_WGRAD, WS_BN, WS_STEM_WGRAD, WS_AUGMENT, WS_PRECONV_WGRAD, WS_CONV_WGRAD_H2, WS_COCO_MASK) = range(1, 31)
 
 EFORMAT, EUNSUPPORTED = -4, -5
 UP_FLAT, UP_BAND, UP_ROWS16, UP_ROWS32 = 1, 2, 3, 4       # ymi_mask_upsample_kernel (include/yolact_amd.h YMI_UP_*)
@@ -452,6 +469,8 @@ SYMBOLS = [
     ('ymi_coco_poly_fill_u8', C.c_int, [_P, _I, _I, _I, _P]),
     ('ymi_coco_rle_fill_u8', C.c_int, [_P, C.c_long, _I, _I, _P]),
     ('ymi_coco_rle_string_fill_u8', C.c_int, [C.c_char_p, C.c_long, _I, _I, _P]),
+    ('ymi_coco_rle_string_counts', C.c_int64, [C.c_char_p, C.c_long, _P, C.c_int64]),
+    ('ymi_coco_masks_u8', C.c_int, [C.POINTER(CocoMaskDesc), _P]),
     ('ymi_event_create', C.c_int, [C.POINTER(C.c_void_p)]),
     ('ymi_event_destroy', C.c_int, [_P]),
     ('ymi_plan_run', C.c_int, [C.POINTER(PlanOp), _I, _I, _P, _P, C.POINTER(C.c_void_p), _I, _I, C.POINTER(C.c_int32)]),

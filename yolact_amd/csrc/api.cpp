@@ -20,6 +20,7 @@ int64_t ymi_stem_wgrad_ws_bytes(const ymi_stem_wgrad_desc *d);                //
 int64_t ymi_augment_ws_bytes(const ymi_augment_desc *d);                      // csrc/augment.hip
 int64_t ymi_preconv_wgrad_ws_bytes(const ymi_preconv_wgrad_desc *d);          // csrc/darknet_train.hip
 int64_t ymi_conv_wgrad_h2_ws_bytes(const ymi_conv_wgrad_desc *d);             // csrc/conv_wgrad_h2.hip
+int64_t ymi_coco_mask_ws_bytes(const ymi_coco_mask_desc *d);                  // csrc/coco_mask.hip
 
 int ymi_abi_version(void) { return YMI_ABI_VERSION; }
 
@@ -102,6 +103,7 @@ int64_t ymi_workspace_bytes(int what, const void *desc) {
     case YMI_WS_AUGMENT: return ymi_augment_ws_bytes((const ymi_augment_desc *)desc);
     case YMI_WS_PRECONV_WGRAD: return ymi_preconv_wgrad_ws_bytes((const ymi_preconv_wgrad_desc *)desc);
     case YMI_WS_CONV_WGRAD_H2: return ymi_conv_wgrad_h2_ws_bytes((const ymi_conv_wgrad_desc *)desc);
+    case YMI_WS_COCO_MASK: return ymi_coco_mask_ws_bytes((const ymi_coco_mask_desc *)desc);
     case YMI_WS_RLE_COUNTS: {
       const ymi_rle_shape *d = (const ymi_rle_shape *)desc;
       if (d->N < 0 || d->h < 1 || d->w < 1) return -1;

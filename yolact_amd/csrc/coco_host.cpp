@@ -33,6 +33,30 @@ int fill_runs(const uint32_t *cnt, long n, int h, int w, uint8_t *mask) {
   return pos == total ? YMI_OK : YMI_EFORMAT;
 }
 
+// maskApi.c rleFrString: the compressed 'counts' string -> counts (shared by the host fill and, through
+// ymi_coco_rle_string_counts, by the packer of the device rasteriser csrc/coco_mask.hip)
+int string_counts(const char *s, long len, std::vector<uint32_t> &cnts) {
+  long p = 0;
+  while (p < len) {
+    long x = 0;
+    int k = 0, more = 1;
+    while (more) {
+      if (p >= len) return YMI_EFORMAT;
+      const long c = (long)(unsigned char)s[p] - 48;
+      x |= (c & 0x1f) << (5 * k);
+      more = (int)(c & 0x20);
+      ++p;
+      ++k;
+      if (k > 12) return YMI_EFORMAT;                           // before the shift below: 5 * 13 = 65 bits would be undefined
+      if (!more && (c & 0x10)) x |= (long)(~0UL << (5 * k));   // sign extension (maskApi.c: x |= -1 << 5*k)
+    }
+    if (cnts.size() > 2) x += (long)cnts[cnts.size() - 2];
+    if (x < 0) return YMI_EFORMAT;
+    cnts.push_back((uint32_t)x);
+  }
+  return YMI_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -117,29 +141,23 @@ int ymi_coco_rle_fill_u8(const uint32_t *counts, long n, int h, int w, uint8_t *
   return fill_runs(counts, n, h, w, mask);
 }
 
+int64_t ymi_coco_rle_string_counts(const char *s, long len, uint32_t *counts, int64_t cap) {
+  if (!s || !counts) return YMI_ENULL;
+  if (len < 0 || cap < 0) return YMI_EARG;
+  std::vector<uint32_t> cnts;
+  const int rc = string_counts(s, len, cnts);
+  if (rc != YMI_OK) return rc;
+  if ((int64_t)cnts.size() > cap) return YMI_EARG;
+  std::copy(cnts.begin(), cnts.end(), counts);
+  return (int64_t)cnts.size();
+}
+
 int ymi_coco_rle_string_fill_u8(const char *s, long len, int h, int w, uint8_t *mask) {
   if (!s || !mask) return YMI_ENULL;
   if (len < 0 || h <= 0 || w <= 0) return YMI_EARG;
-  // maskApi.c rleFrString
   std::vector<uint32_t> cnts;
-  long p = 0;
-  while (p < len) {
-    long x = 0;
-    int k = 0, more = 1;
-    while (more) {
-      if (p >= len) return YMI_EFORMAT;
-      const long c = (long)(unsigned char)s[p] - 48;
-      x |= (c & 0x1f) << (5 * k);
-      more = (int)(c & 0x20);
-      ++p;
-      ++k;
-      if (k > 12) return YMI_EFORMAT;                           // before the shift below: 5 * 13 = 65 bits would be undefined
-      if (!more && (c & 0x10)) x |= (long)(~0UL << (5 * k));   // sign extension (maskApi.c: x |= -1 << 5*k)
-    }
-    if (cnts.size() > 2) x += (long)cnts[cnts.size() - 2];
-    if (x < 0) return YMI_EFORMAT;
-    cnts.push_back((uint32_t)x);
-  }
+  const int rc = string_counts(s, len, cnts);
+  if (rc != YMI_OK) return rc;
   return fill_runs(cnts.data(), (long)cnts.size(), h, w, mask);
 }
 

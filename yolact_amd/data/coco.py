@@ -4,7 +4,9 @@ The reference's eval loop reads every validation item through `dataset.pull_item
     cv2.imread -> annToMask per object -> target transform -> BaseTransform -> torch tensor.
 Here the image half runs on the GPU (data/jpeg.py: host entropy decode, device reconstruction; BaseTransform = the
 FastBaseTransform kernel), the annotation half is host code like the reference's: the JSON index is plain Python, the
-polygon / RLE rasteriser is native (csrc/coco_host.cpp, pycocotools' maskApi.c restated).  Same constructor arguments,
+polygon / RLE rasteriser is native (csrc/coco_host.cpp, pycocotools' maskApi.c restated) — or, with
+`COCODetection(device_masks=True)` / `ann_to_masks_device`, the device's (csrc/coco_mask.hip: all annotations of an item in one
+launch from one packed upload, byte-equal to the host's, the masks never on the host).  Same constructor arguments,
 same return tuple, same crowd ordering, same "no ground truth -> resample" rule; the image tensor is on the GPU (the
 reference returns a CPU tensor that eval.py then moves with `.cuda()`, eval.py:938-940).
 """
@@ -64,6 +66,16 @@ class COCOIndex:
         t = self.imgs[ann['image_id']]
         return ann_to_mask(ann, t['height'], t['width'])
 
+    def annToMasks(self, anns, device=None):
+        """`annToMask` of a list of annotations (of one image or of several) in one device call, each at its own image's JSON
+        height and width: a uint8 [n,h,w] device tensor when the sizes agree, else a list of [h_i,w_i] device tensors."""
+        anns = list(anns)
+        sizes = [(int(self.imgs[a['image_id']]['height']), int(self.imgs[a['image_id']]['width'])) for a in anns]
+        flat, offs = _masks_device(anns, sizes, device)
+        if len(set(sizes)) == 1:
+            return flat.view(len(anns), *sizes[0])
+        return [flat[int(offs[i]):int(offs[i + 1])].view(h, w) for i, (h, w) in enumerate(sizes)]
+
 
 def ann_to_mask(ann, h: int, w: int) -> np.ndarray:
     """pycocotools annToRLE + decode: polygon list (union) | uncompressed RLE | compressed RLE string."""
@@ -88,6 +100,114 @@ def ann_to_mask(ann, h: int, w: int) -> np.ndarray:
         s = counts.encode('ascii') if isinstance(counts, str) else bytes(counts)
         L.check(lib.ymi_coco_rle_string_fill_u8(s, len(s), h, w, mask.ctypes.data), 'ymi_coco_rle_string_fill_u8')
     return mask
+
+
+class PackedAnnotations:
+    """The tables of one ymi_coco_masks_u8 call (include/yolact_amd.h ymi_coco_mask_rec / ymi_coco_mask_desc), as numpy arrays:
+    per annotation `kind`, `h`, `w`, `n` (polygons | counts), `first` (into poly_len | counts), `xy_first` (first vertex of
+    xy), all int32 [n]; `xy` float64 [n_vert,2]; `poly_len` int32 [n_poly]; `counts` uint32 [n_counts]."""
+
+    def __init__(self, kind, h, w, n, first, xy_first, xy, poly_len, counts):
+        self.kind, self.h, self.w, self.n, self.first, self.xy_first = kind, h, w, n, first, xy_first
+        self.xy, self.poly_len, self.counts = xy, poly_len, counts
+
+    def __len__(self):
+        return len(self.kind)
+
+
+def string_counts(counts) -> np.ndarray:
+    """A compressed RLE 'counts' string (str or bytes) -> its counts, uint32 (maskApi.c rleFrString, csrc/coco_host.cpp)."""
+    s = counts.encode('ascii') if isinstance(counts, str) else bytes(counts)
+    out = np.empty(max(len(s), 1), dtype=np.uint32)
+    n = L.lib().ymi_coco_rle_string_counts(s, len(s), out.ctypes.data, out.size)
+    if n < 0:
+        L.check(int(n), 'ymi_coco_rle_string_counts')
+    return out[:n].copy()
+
+
+def pack_annotations(anns, sizes) -> PackedAnnotations:
+    """Annotation dicts and their (h, w) -> the packed tables of the device rasteriser.  The host half of
+    `ann_to_masks_device`: the shape checks of `ann_to_mask` (same ValueErrors), a compressed string decoded to counts."""
+    kind, hs, ws, ns, first, xy_first = [], [], [], [], [], []
+    xy, poly_len, counts = [], [], []
+    n_vert = n_counts = 0
+    for ann, (h, w) in zip(anns, sizes):
+        seg = ann['segmentation']
+        hs.append(int(h))
+        ws.append(int(w))
+        if isinstance(seg, list):
+            kind.append(L.COCO_POLY)
+            ns.append(len(seg))
+            first.append(len(poly_len))
+            xy_first.append(n_vert)
+            for poly in seg:
+                p = np.ascontiguousarray(poly, dtype=np.float64).reshape(-1)
+                if p.size < 2 or p.size % 2:
+                    raise ValueError('polygon with %d coordinates' % p.size)
+                xy.append(p)
+                poly_len.append(p.size // 2)
+                n_vert += p.size // 2
+            continue
+        size = seg.get('size')
+        if size is not None and (int(size[0]) != h or int(size[1]) != w):
+            raise ValueError('RLE size %s does not match the image (%d, %d)' % (size, h, w))
+        c = seg['counts']
+        c = np.ascontiguousarray(c, dtype=np.uint32).reshape(-1) if isinstance(c, list) else string_counts(c)
+        kind.append(L.COCO_COUNTS)
+        ns.append(c.size)
+        first.append(n_counts)
+        xy_first.append(0)
+        counts.append(c)
+        n_counts += c.size
+    i32 = lambda v: np.asarray(v, dtype=np.int32).reshape(-1)
+    return PackedAnnotations(
+        i32(kind), i32(hs), i32(ws), i32(ns), i32(first), i32(xy_first),
+        np.concatenate(xy).reshape(-1, 2) if xy else np.zeros((0, 2), dtype=np.float64), i32(poly_len),
+        np.concatenate(counts).astype(np.uint32, copy=False) if counts else np.zeros(0, dtype=np.uint32))
+
+
+def _masks_device(anns, sizes, device=None):
+    """-> (flat uint8 device buffer, [offset of annotation i]): mask i is flat[off_i : off_i + h_i w_i] viewed [h_i, w_i].
+    One packed upload and one ymi_coco_masks_u8 call for every annotation under the LDS cap (L.COCO_MASK_MAX_PIXELS pixels);
+    one above it is rasterised by `ann_to_mask` on the host and uploaded into its place."""
+    device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+    sizes = [(int(h), int(w)) for h, w in sizes]
+    offs = np.concatenate(([0], np.cumsum([h * w for h, w in sizes], dtype=np.int64)))
+    on_dev = [i for i, (h, w) in enumerate(sizes) if h * w <= L.COCO_MASK_MAX_PIXELS]
+    pk = pack_annotations([anns[i] for i in on_dev], [sizes[i] for i in on_dev])    # (before any allocation: it validates)
+    if device.type != 'cuda':
+        L.require_cuda(torch.empty(0), 'the mask buffer')
+    lib = L.lib()
+    with torch.cuda.device(device):
+        flat = torch.empty(int(offs[-1]), dtype=torch.uint8, device=device)
+        if on_dev:
+            recs = (L.CocoMaskRec * len(on_dev))()
+            for j, i in enumerate(on_dev):
+                r = recs[j]
+                r.out = flat.data_ptr() + int(offs[i])
+                r.kind, r.h, r.w, r.n = int(pk.kind[j]), int(pk.h[j]), int(pk.w[j]), int(pk.n[j])
+                r.first, r.xy_first = int(pk.first[j]), int(pk.xy_first[j])
+            d = L.CocoMaskDesc()
+            d.recs = recs
+            d.xy, d.poly_len, d.counts = pk.xy.ctypes.data, pk.poly_len.ctypes.data, pk.counts.ctypes.data
+            d.n, d.n_vert, d.n_poly, d.n_counts = len(on_dev), pk.xy.shape[0], pk.poly_len.size, pk.counts.size
+            d.ws_bytes = lib.ymi_workspace_bytes(L.WS_COCO_MASK, C.byref(d))
+            ws = torch.empty(max(int(d.ws_bytes), 16), dtype=torch.uint8, device=device)
+            d.ws = ws.data_ptr()
+            L.check(lib.ymi_coco_masks_u8(C.byref(d), L.stream_ptr()), 'ymi_coco_masks_u8')
+        for i, (h, w) in enumerate(sizes):
+            if h * w > L.COCO_MASK_MAX_PIXELS:
+                flat[int(offs[i]):int(offs[i + 1])].copy_(torch.from_numpy(ann_to_mask(anns[i], h, w).reshape(-1)))
+    return flat, offs
+
+
+def ann_to_masks_device(anns, h: int, w: int, device=None) -> torch.Tensor:
+    """`ann_to_mask` for a list of annotations of one image size, rasterised on the GPU (csrc/coco_mask.hip): uint8 [n,h,w]
+    device tensor, byte-equal to np.stack([ann_to_mask(a, h, w) for a in anns]).  Vertices and counts cross to the device in
+    one packed upload; the same bad inputs raise what `ann_to_mask` raises."""
+    anns = list(anns)
+    flat, _ = _masks_device(anns, [(h, w)] * len(anns), device)
+    return flat.view(len(anns), int(h), int(w))
 
 
 class COCOAnnotationTransform:
@@ -128,7 +248,7 @@ class COCODetection(torch.utils.data.Dataset):
     yolact_amd.utils.augmentations.BaseTransform the image goes in and comes out as a device tensor."""
 
     def __init__(self, image_path, info_file, transform=None, target_transform=None, dataset_name='MS COCO', has_gt=True,
-                 device=None):
+                 device=None, device_masks=False):
         self.root = image_path
         self.coco = COCOIndex(info_file)
         annotated = list(self.coco.imgToAnns.keys())
@@ -138,6 +258,7 @@ class COCODetection(torch.utils.data.Dataset):
         self.name = dataset_name
         self.has_gt = has_gt
         self.device = device
+        self.device_masks = bool(device_masks)      # ground-truth masks rasterised on the GPU (COCOIndex.annToMasks)
 
     def __len__(self):
         return len(self.ids)
@@ -155,7 +276,8 @@ class COCODetection(torch.utils.data.Dataset):
         return path
 
     def pull_item(self, index):
-        """-> (image [3,S,S] float32 on the GPU, target [n,5] float ndarray, masks [n,h,w] uint8 ndarray, height, width,
+        """-> (image [3,S,S] float32 on the GPU, target [n,5] float ndarray, masks [n,h,w] uint8 ndarray — with
+        `device_masks=True` a uint8 device tensor, rasterised there in one call and never on the host —, height, width,
         num_crowds) — data/coco.py:100-176.  No annotations (has_gt=False): target and masks are None (what the
         reference's else-branch assigns, data/coco.py:163-167; its next line then dereferences the None and raises — an
         evident slip, not reproduced)."""
@@ -172,7 +294,11 @@ class COCODetection(torch.utils.data.Dataset):
         if anns:
             # data/coco.py:146-148: annToMask rasterises at the JSON's (height, width); the flat masks are then reshaped to
             # the DECODED size (they differ only for EXIF-rotated files: the reference carries on, and so does this)
-            masks = np.vstack([self.coco.annToMask(a).reshape(-1) for a in anns]).reshape(-1, height, width)
+            if self.device_masks:
+                masks = self.coco.annToMasks(anns, img.device)
+                masks = (masks if torch.is_tensor(masks) else torch.cat([m.reshape(-1) for m in masks])).reshape(-1, height, width)
+            else:
+                masks = np.vstack([self.coco.annToMask(a).reshape(-1) for a in anns]).reshape(-1, height, width)
             target = np.array(self.target_transform(anns, width, height))
 
         if self.transform is not None:

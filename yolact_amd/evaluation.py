@@ -145,7 +145,7 @@ class APEvaluator:
     def add_detections(self, classes, scores, boxes_px, mask_bits, gt, gt_masks, h, w, num_crowd):
         """The same from postprocessed device tensors: classes [N] int, scores [N] (or the YOLACT++ [box_scores, mask_scores]),
         boxes_px [N,4] integer pixels, mask_bits int64 [N, ceil(h*w/64)] (output_utils.postprocess_bits / box_utils.mask_bits);
-        gt [n,5] relative xyxy + class (host), gt_masks [n,h,w] 0/1 (host), crowds last."""
+        gt [n,5] relative xyxy + class (host), gt_masks [n,h,w] 0/1 (host, or a device tensor, which stays there), crowds last."""
         if isinstance(classes, (list, tuple)) or classes.shape[0] == 0:
             return                                  # eval.py:405-406: the GT of an image without detections is not counted
         N = int(classes.shape[0])
@@ -182,8 +182,11 @@ class APEvaluator:
             cls_gt = _upload(gt_cls, np.int32, dev)
             ious = [None] * 4                       # box, mask, crowd box, crowd mask
             if n_all:
-                gm = gt_masks.cpu().numpy() if torch.is_tensor(gt_masks) else np.asarray(gt_masks)
-                gm_f = _upload(gm.reshape(n_all, n), np.uint8, dev).float()
+                if torch.is_tensor(gt_masks) and gt_masks.is_cuda:      # COCODetection(device_masks=True): used where they are
+                    gm_f = gt_masks.to(dev).reshape(n_all, n).to(torch.uint8).float()
+                else:
+                    gm = gt_masks.cpu().numpy() if torch.is_tensor(gt_masks) else np.asarray(gt_masks)
+                    gm_f = _upload(gm.reshape(n_all, n), np.uint8, dev).float()
                 gt_bits = torch.empty(n_all, W64, dtype=torch.int64, device=dev)
                 L.check(lib.ymi_mask_bits_f32(gm_f.data_ptr(), n_all, n, gt_bits.data_ptr(), s), 'ymi_mask_bits_f32')
                 for slot, lo, hi, crowd in ((0, 0, G, 0), (2, G, n_all, 1)):

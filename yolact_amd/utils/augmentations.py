@@ -125,7 +125,8 @@ class BaseTransform:
             w = boxes[:, 2] - boxes[:, 0]
             h = boxes[:, 3] - boxes[:, 1]
             keep = (w > getattr(cfg, 'discard_box_width', 4 / 550)) * (h > getattr(cfg, 'discard_box_height', 4 / 550))
-            masks = masks[keep]
+            # (device masks, COCODetection(device_masks=True): the index goes where the masks are)
+            masks = masks[torch.from_numpy(np.asarray(keep, dtype=bool)).to(masks.device)] if torch.is_tensor(masks) else masks[keep]
             boxes = boxes[keep]
             labels['labels'] = labels['labels'][keep]
             labels['num_crowds'] = (labels['labels'] < 0).sum()
