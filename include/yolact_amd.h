@@ -1177,6 +1177,23 @@ typedef struct ymi_chain_desc {
    * filters (engine.Packed.l1_gain()); res_amax = the magnitude-bound slot of the residual tensor (required when res != NULL). */
   const float *res_amax;
   float gain_a, bias_max_a;
+  /* additive within ABI 9, P = 64 only: the ENTRY form (csrc/chain.hip, chain_h2_k<64, true>).  All zero = the launch above, bit
+   * for bit.  x0 != NULL: the residual is not read but COMPUTED in the launch as the block's projection shortcut (backbone.py:52-53),
+   *     res = scale_d * (W_d x0) + bias_d              1x1, stride 1, 64 -> 256, no activation
+   * from the block input x0 [M,ldx0] (64 channels; ldx0 >= 64) with x0's OWN magnitude slot x0_amax (required; independent of
+   * x_amax); w_d_h2 / scale_d_h2 / bias_d / cout_pad_d as the other two layers'.  y = act_a(scale_a * (W_a x) + bias_a + res) in
+   * that expression order: against the shortcut through ymi_conv2d_nhwc_f32 followed by this launch with `res` only the summation
+   * order inside W_d x0 differs.  z may be NULL.
+   * Requires res == NULL and (k_a, n_a) = (64, 256), else YMI_EARG (ymi_stage_exit_chain_f32 and the P = 128 / 256 path refuse a
+   * descriptor with x0 set: YMI_EARG); w_d_h2, scale_d_h2, x0_amax, else YMI_ENULL; ldx0 >= 64 and % 4 == 0, x0 / w_d_h2 16-byte
+   * aligned, M * ldx0 < 2^29, cout_pad_d >= 256, else YMI_ESHAPE.
+   * ALIASING, beside the rules above: y must not overlap x0.  z MAY be x0 exactly in place — z == x0 and ldz == ldx0 — for the
+   * reason given for x (a block reads rows [32 t, 32 t + 32) of x0 before it writes those rows of z), and in no other overlapping
+   * form; the arena can hand conv1's output the buffer of the block input, so engine.Plan checks this before it fuses. */
+  const float *x0, *x0_amax;
+  const void *w_d_h2;
+  const float *scale_d_h2, *bias_d;                          /* bias_d may be NULL */
+  int32_t ldx0, cout_pad_d;
 } ymi_chain_desc;
 int ymi_pointwise_chain_f32(const ymi_chain_desc *d, void *stream);
 

@@ -12,6 +12,9 @@ in the step (profiles/r04_layers.txt), 0.0745 + 0.035 ms alone on resident buffe
 Then the stage EXIT (ymi_stage_exit_chain_f32: layer0.2.conv3 + residual -> layer1.0.conv1, 256 -> 128, y stored at even rows and
 columns only) next to the two launches it replaces: the chain kernel without its second layer ('chain1') and the plan's 1x1
 256 -> 128 convolution on the tile the shipped table gives that shape; same rotating buffer sets.
+
+Then the stage ENTRY (ymi_chain_desc.x0: layer0.0's projection shortcut computed inside the layer0.0.conv3 -> layer0.1.conv1 launch):
+the shortcut launch alone on its shipped tile, the shortcut launch followed by the pair chain, and the entry launch; same sets.
 """
 import argparse
 import ctypes as C
@@ -44,7 +47,7 @@ def main():
         x = torch.randn(M, 64, device=dev).relu_()
         res = torch.randn(M, 256, device=dev).relu_()
         sets.append((x, res, torch.empty(M, 256, device=dev), torch.empty(M, 64, device=dev)))
-    amax = torch.zeros(3 * 1024, device=dev)
+    amax = torch.zeros(5 * 1024, device=dev)
     lib, s = L.lib(), L.stream_ptr()
     L.check(lib.ymi_amax_f32(sets[0][0].data_ptr(), sets[0][0].numel(), amax.data_ptr(), s))
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -116,6 +119,53 @@ def main():
         xs = [exit_desc(k, ys) for k in range(args.sets)]
         arms.append(('stage exit, y_stride %d' % ys, (lambda k, xs=xs: lib.ymi_stage_exit_chain_f32(C.byref(xs[k]), s)),
                      4.0 * M * (64 + 256 + 128) + 4.0 * B * ((H + ys - 1) // ys) * ((W + ys - 1) // ys) * 256))
+    for name, run, nbytes in arms:
+        for k in range(args.sets):
+            L.check(run(k))
+        best = 1e30
+        for _ in range(3):
+            e0.record()
+            for r in range(args.reps):
+                run(r % args.sets)
+            e1.record()
+            e1.synchronize()
+            best = min(best, e0.elapsed_time(e1) / args.reps)
+        print('%-30s M=%d  %.4f ms  %6.1f MB  %.2f TB/s' % (name, M, best, nbytes / 1e6, nbytes / best / 1e9))
+
+    # ---- the stage ENTRY: layer0.0's projection shortcut (1x1, 64 -> 256, no activation) on the tile the shipped table gives it, that
+    # launch followed by the pair chain that reads its output as the residual, and the entry launch that computes it inside
+    wd = torch.randn(256, 64, 1, 1, generator=g) / 8
+    pd = Packed(wd, torch.randn(256, generator=g), None, 1, 0, None, dev)
+    pld, scd, winvd = pd.h2()
+    x0s = [torch.randn(M, 64, device=dev).relu_() for _ in range(args.sets)]
+    L.check(lib.ymi_amax_f32(x0s[0].data_ptr(), x0s[0].numel(), amax.data_ptr() + 12288, s))
+
+    def down_desc(k):
+        d = L.ConvDesc()
+        d.x, d.w, d.bias = x0s[k].data_ptr(), pd.w.data_ptr(), pd.bias.data_ptr()
+        d.scale = pd.scale.data_ptr() if pd.scale is not None else None
+        d.B, d.H, d.W, d.Cin, d.ldx, d.Ho, d.Wo, d.Cout = B, H, W, 64, 64, H, W, 256
+        d.kh, d.kw, d.stride, d.pad, d.Kpad, d.cin_alg, d.cout_alg = 1, 1, 1, 0, pd.Kpad, pd.cin_alg, pd.cout_alg
+        d.nseg = 1
+        d.seg[0] = L.ConvSeg(0, 256, L.ACT_NONE, 256, H * W * 256, sets[k][1].data_ptr())      # (into the set's residual tensor)
+        d.x_amax, d.y_amax = amax.data_ptr() + 12288, amax.data_ptr() + 16384
+        d.w_h2, d.scale_h2, d.winv_h2 = pld.data_ptr(), scd.data_ptr(), winvd.data_ptr()
+        val = TT.load_tune_table(dev).get(TT.conv_key((B, H, W, 64, 256, 1, 1, 1, 0, 0, 1, 64), 'h2'))
+        d.tile = TT.direct_parts(val)[0] if val is not None else L.TILE_AUTO
+        return d
+
+    def entry_desc(k):
+        d = desc(k, True, False)
+        d.x0, d.ldx0, d.x0_amax = x0s[k].data_ptr(), 64, amax.data_ptr() + 12288
+        d.w_d_h2, d.scale_d_h2, d.bias_d, d.cout_pad_d = pld.data_ptr(), scd.data_ptr(), pd.bias.data_ptr(), pd.CoutPad
+        return d
+    dn = [down_desc(k) for k in range(args.sets)]
+    pair = [desc(k, True, True) for k in range(args.sets)]
+    ent = [entry_desc(k) for k in range(args.sets)]
+    arms = [('layer0.0.down (tile %d)' % dn[0].tile, lambda k: lib.ymi_conv2d_nhwc_f32(C.byref(dn[k]), s), 4.0 * M * (64 + 256)),
+            ('down, then pair chain', lambda k: (lib.ymi_conv2d_nhwc_f32(C.byref(dn[k]), s), lib.ymi_pointwise_chain_f32(C.byref(pair[k]), s))[1],
+             4.0 * M * (64 + 256 + 64 + 256 + 256 + 64)),
+            ('entry chain (down inside)', lambda k: lib.ymi_pointwise_chain_f32(C.byref(ent[k]), s), 4.0 * M * (64 + 64 + 256 + 64))]
     for name, run, nbytes in arms:
         for k in range(args.sets):
             L.check(run(k))

@@ -4,7 +4,8 @@
     python tools/make_tune_table.py [--out yolact_amd/tune/gfx950.json] [--fresh] [--only NAME ...]
 
 Every (config, batch, size) below is planned once with on-device measurement of every shape the table does not know yet
-(HIP events on the launch stream, engine.Plan.tune); entries accumulate in ONE file, so a shape shared by several plans
+(HIP events on the launch stream, engine.Plan.tune: tiles, Winograd against direct, and the chain fusions — the pair 'chain(B, H, W)',
+the stage exit 'chainx(B, H, W)' and, where the pair is installed, its entry form 'chain(B, H, W, 64)'); entries accumulate in ONE file, so a shape shared by several plans
 is measured once and every plan that contains it runs the same tile (bit-identical results across plans that share
 layers).  The default plan of the product then reads the table and measures nothing: deterministic across processes and
 boxes (tests/test_gpu_batch_parity.py::test_plan_is_deterministic_across_processes).

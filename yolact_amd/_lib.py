@@ -328,7 +328,10 @@ class ChainDesc(C.Structure):
                 ('M', C.c_int64), ('ldx', C.c_int32), ('res_ld', C.c_int32), ('ldy', C.c_int32), ('ldz', C.c_int32),
                 ('k_a', C.c_int32), ('n_a', C.c_int32), ('n_b', C.c_int32), ('cout_pad_a', C.c_int32), ('cout_pad_b', C.c_int32),
                 ('act_a', C.c_int32), ('act_b', C.c_int32), ('_pad0', C.c_int32),
-                ('res_amax', C.c_void_p), ('gain_a', C.c_float), ('bias_max_a', C.c_float)]
+                ('res_amax', C.c_void_p), ('gain_a', C.c_float), ('bias_max_a', C.c_float),
+                # the ENTRY form (x0 != NULL: the residual is the projection shortcut of x0, computed in the launch)
+                ('x0', C.c_void_p), ('x0_amax', C.c_void_p), ('w_d_h2', C.c_void_p), ('scale_d_h2', C.c_void_p),
+                ('bias_d', C.c_void_p), ('ldx0', C.c_int32), ('cout_pad_d', C.c_int32)]
 
 
 class StageExitDesc(C.Structure):

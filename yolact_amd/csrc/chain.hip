@@ -48,6 +48,12 @@ constexpr int OFF_A1 = 0, OFF_A2 = OFF_A1 + 2 * A1_BUF, OFF_SC = OFF_A2 + 2 * A2
 // 32-deep chunk), conflict-free ds_read_b128): with both planes in registers the kernel needs 256 VGPRs + 156 bytes of scratch
 constexpr int OFF_EP2 = CH_LDS, OFF_WL = OFF_EP2 + NW * 2 * 4 * 32, CH_LDS_X = OFF_WL + 128 * N1 * 2;
 static_assert(CH_LDS_X <= 160 * 1024, "LDS of a CU");
+// ENTRY (the stage's first block, see below): a second double-buffered K = 64 tile — the block input x0, the operand of the projection
+// shortcut — and the shortcut's per-lane epilogue constants, (scale, bias) x (wave, j, g) like conv3's
+// and the LOW plane of the shortcut's filters (32 KB, fragment order as OFF_WL above: 1 KB = the 64 lanes' 16 bytes of one (wave, j, c);
+// every lane reads back what it wrote itself): with both planes in registers the kernel needs 256 VGPRs + 60 bytes of scratch
+constexpr int OFF_A0 = CH_LDS, OFF_EPD = OFF_A0 + 2 * A1_BUF, OFF_WDL = OFF_EPD + NW * 2 * 4 * 32, CH_LDS_E = OFF_WDL + N1 * K1 * 2;
+static_assert(CH_LDS_E <= 160 * 1024, "LDS of a CU");
 
 struct ChainParams {
   const float *x, *res, *x_amax;
@@ -65,6 +71,17 @@ struct ChainParamsX : ChainParams {
   unsigned long long mag_w, mag_h;
   int H, W, y_stride;
 };
+// ENTRY (again a type of its own): the block input x0 [M, ldx0] with its magnitude slot, the shortcut's fp16 planes [2][cpd][64],
+// scale_h2 and bias
+struct ChainParamsE : ChainParams {
+  const float *x0, *x0_amax;
+  const void *wd;
+  const float *sd, *bd;
+  int ldx0;
+  unsigned wd_plane;
+};
+template <int N2, bool ENTRY>
+using chain_params_t = std::conditional_t<ENTRY, ChainParamsE, std::conditional_t<N2 == 128, ChainParamsX, ChainParams>>;
 
 // N2 = the second layer's width.  64: the pair inside the stage (above; this instantiation's ISA is the untemplated kernel's,
 // instruction for instruction).  128: the stage EXIT, layer0.2.conv3 -> layer1.0.conv1 (256 -> 128, ymi_stage_exit_chain_f32): wave
@@ -79,17 +96,34 @@ struct ChainParamsX : ChainParams {
 //     N2 = 128, conv1's LOW plane in LDS          238 VGPRs, 0 AGPRs, no scratch, 155 776 B of LDS   (shipped)
 // 32 + 128 filter registers fit on paper, but next to the two residual sets (32), the accumulators and the addresses the allocator
 // spills 39 of them; the low plane (one of three products) costs 16 conflict-free ds_read_b128 per wave per 32 pixels instead.
-template <int N2>
-__global__ __launch_bounds__(64 * NW) void chain_h2_k(const std::conditional_t<N2 == 128, ChainParamsX, ChainParams> p) {
+//
+// ENTRY (N2 = 64 only): the stage's FIRST block, layer0.0.conv3 -> layer0.1.conv1, whose residual is the projection shortcut
+// r = bn_d(W_d x0) (1x1, 64 -> 256, no activation) of the block input x0.  r is computed HERE instead of being read: per iteration
+// the block also takes its 32 x 64 tile of x0 (this thread's 16 bytes, requested one iteration ahead like t's), splits it into two
+// fp16 planes with x0's OWN power-of-two scale (x0_amax) into a second double-buffered LDS tile, and a second accumulator set
+// accd = W_d x0 runs on the same MFMA with the same three-product order as GEMM 1, one 16-pixel half at a time in front of the
+// epilogue of that half.  The wave's 32 channels of W_d: the high plane as register fragments like conv3's, the low plane in LDS
+// in fragment order (this form loads no residual, so the two residual sets' 32 VGPRs are free).  Epilogue 1 keeps its expression
+// order with r = accd * (scale_d / s_x0) + bias_d in the residual's place, so against the two launches (shortcut, then chain) at
+// most the summation order inside accd differs.  The 256-channel shortcut tensor is never written or read: 273 MB per batch-8
+// launch against 195 + 390.  Registers (same remark as above; none of the other two instantiations' instructions move):
+//     both planes in registers, all four accd tiles next to GEMM 1's   256 VGPRs, 60 B of scratch per lane          (not shipped)
+//     low plane in LDS, all four accd tiles                            256 VGPRs, 12 B of scratch per lane          (not shipped)
+//     low plane in LDS, accd half by half                              253 VGPRs, no scratch, 141 440 B of LDS      (shipped)
+template <int N2, bool ENTRY = false>
+__global__ __launch_bounds__(64 * NW) void chain_h2_k(const chain_params_t<N2, ENTRY> p) {
 #if defined(__HIP_DEVICE_COMPILE__)
   constexpr int NT = N2 / 64;                          // 16-channel tiles of z per wave
   constexpr bool EXIT = N2 == 128;
-  __shared__ __attribute__((aligned(16))) char lds[EXIT ? CH_LDS_X : CH_LDS];
+  static_assert(!(ENTRY && EXIT), "the entry form is the 64-wide pair's");
+  __shared__ __attribute__((aligned(16))) char lds[EXIT ? CH_LDS_X : ENTRY ? CH_LDS_E : CH_LDS];
   const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
   const int lr = lane & 15, g = lane >> 4;
   const int q2 = wave & 3, i2 = wave >> 2;             // GEMM 2: this wave's 16 z channels (16 q2 ..) and 16-pixel half of the tile
   float sA, invA;
   ymi_h2_scale(ymi_amax_read(p.x_amax), sA, invA);
+  float sD = 1.f, invD = 1.f;                          // ENTRY: x0's scale, independent of t's
+  if constexpr (ENTRY) ymi_h2_scale(ymi_amax_read(p.x0_amax), sD, invD);
   const ymi_amax_pre apre_y = ymi_amax_prefetch(p.y_amax);
   const ymi_amax_pre apre_z = ymi_amax_prefetch(p.z_amax);
   const bool two = p.z != nullptr;
@@ -105,6 +139,17 @@ __global__ __launch_bounds__(64 * NW) void chain_h2_k(const std::conditional_t<N
       w3h[j][c] = *reinterpret_cast<const f16x8 *>(src);
       w3l[j][c] = *reinterpret_cast<const f16x8 *>(src + p.wa_plane);
     }
+  f16x8 wdh[ENTRY ? 2 : 1][ENTRY ? 2 : 1];           // ENTRY: the shortcut's, same channels, same fragments; the low plane -> LDS
+  if constexpr (ENTRY) {
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int c = 0; c < 2; ++c) {
+        const char *src = reinterpret_cast<const char *>(p.wd) + (size_t)(32 * wave + 16 * j + lr) * (2 * K1) + c * 64 + g * 16;
+        wdh[j][c] = *reinterpret_cast<const f16x8 *>(src);
+        *reinterpret_cast<f16x8 *>(lds + OFF_WDL + (((wave * 2 + j) * 2 + c) * 64 + lane) * 16) = *reinterpret_cast<const f16x8 *>(src + p.wd_plane);
+      }
+  }
 #pragma unroll
   for (int tt = 0; tt < NT; ++tt)
 #pragma unroll
@@ -134,6 +179,12 @@ __global__ __launch_bounds__(64 * NW) void chain_h2_k(const std::conditional_t<N
       for (int e = 0; e < 4; ++e) { sc[e] = p.sa[n + e] * invA; bi[e] = p.ba ? p.ba[n + e] : 0.f; }
       *reinterpret_cast<f32x4 *>(lds + OFF_EP + ((wave * 2 + j) * 4 + g) * 32) = sc;
       *reinterpret_cast<f32x4 *>(lds + OFF_EP + ((wave * 2 + j) * 4 + g) * 32 + 16) = bi;
+      if constexpr (ENTRY) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { sc[e] = p.sd[n + e] * invD; bi[e] = p.bd ? p.bd[n + e] : 0.f; }
+        *reinterpret_cast<f32x4 *>(lds + OFF_EPD + ((wave * 2 + j) * 4 + g) * 32) = sc;
+        *reinterpret_cast<f32x4 *>(lds + OFF_EPD + ((wave * 2 + j) * 4 + g) * 32 + 16) = bi;
+      }
     }
   }
   f32x4 sc1 = {1.f, 1.f, 1.f, 1.f}, bi1 = {0.f, 0.f, 0.f, 0.f};
@@ -173,6 +224,18 @@ __global__ __launch_bounds__(64 * NW) void chain_h2_k(const std::conditional_t<N
     const unsigned off = (tile < ntiles && m < p.M) ? (unsigned)(m * p.ldx + 4 * xc) * 4u : OOB;
     return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(xrs, off, 0, 0));
   };
+  // ENTRY: this thread's 16 bytes of x0, same pixel and channels as its 16 bytes of t (row pitch ldx0; only channels 0 .. 63 are read)
+  __amdgpu_buffer_rsrc_t x0rs = xrs;
+  if constexpr (ENTRY) x0rs = buf_rsrc(p.x0, (unsigned)p.M * (unsigned)p.ldx0 * 4u);
+  auto load_x0 = [&](int tile) {
+    if constexpr (ENTRY) {
+      const int m = tile * PX + xp;
+      const unsigned off = (tile < ntiles && m < p.M) ? (unsigned)(m * p.ldx0 + 4 * xc) * 4u : OOB;
+      return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(x0rs, off, 0, 0));
+    } else {
+      return f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+  };
   auto load_res = [&](int tile, f32x4 (&r)[2][2]) {
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
@@ -195,11 +258,12 @@ __global__ __launch_bounds__(64 * NW) void chain_h2_k(const std::conditional_t<N
   // an iteration would wait for every outstanding memory operation, the stores of y just issued included (seen in the ISA as
   // s_waitcnt vmcnt(0) on the back edge).  Iterations past the last tile load nothing and store nothing but the last tile's z.
   float am_y = 0.f, am_z = 0.f;
-  f32x4 xv;
+  f32x4 xv, x0v;
   const int grid = (int)gridDim.x;
   auto iteration = [&](const int tile, auto buf_c, f32x4 (&rv)[2][2], f32x4 (&rn)[2][2]) {
     constexpr int BUF = decltype(buf_c)::value;
     char *const a1 = lds + OFF_A1 + BUF * A1_BUF;
+    char *const a0 = lds + OFF_A0 + BUF * A1_BUF;       // (ENTRY only)
     char *const a2w = lds + OFF_A2 + BUF * A2_BUF;
     const char *const a2r = lds + OFF_A2 + (BUF ^ 1) * A2_BUF;
     float *const scw = reinterpret_cast<float *>(lds + OFF_SC) + BUF * (2 * NW);
@@ -218,8 +282,22 @@ __global__ __launch_bounds__(64 * NW) void chain_h2_k(const std::conditional_t<N
       *reinterpret_cast<f16x4 *>(dst) = h4;
       *reinterpret_cast<f16x4 *>(dst + A1_PLANE) = l4;
     }
+    if constexpr (ENTRY) {                              // ... and the x0 tile, with its own scale
+      const f32x4 v = x0v * sD;
+      f16x4 h4, l4;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const _Float16 h = (_Float16)v[e];
+        h4[e] = h;
+        l4[e] = (_Float16)(v[e] - (float)h);
+      }
+      char *dst = a0 + xp * RS1 + xc * 8;
+      *reinterpret_cast<f16x4 *>(dst) = h4;
+      *reinterpret_cast<f16x4 *>(dst + A1_PLANE) = l4;
+    }
     xv = load_x(tile + grid);                           // next iteration's operands: in flight until its P1 / P3
-    load_res(tile + grid, rn);
+    if constexpr (ENTRY) x0v = load_x0(tile + grid);
+    else load_res(tile + grid, rn);
     YMI_BARRIER();
     if (two) {
       // P4 (tile k - 1): GEMM 2 for pixels 16 i2 + lr, z channels 16 q2 ..: the K = 256 sum one 32-channel slice (one producing
@@ -320,12 +398,40 @@ __global__ __launch_bounds__(64 * NW) void chain_h2_k(const std::conditional_t<N
         keep = ok && (p.y_stride == 1 || ((h | w) & 1u) == 0);
       }
       const unsigned yoff = keep ? (unsigned)(m * p.ldy + 32 * wave + 4 * g) * 4u : OOB;
+      // ENTRY: the shortcut's GEMM on this half of the x0 tile, same shape and product order as GEMM 1 (taken half by half, next to
+      // the epilogue that consumes it: eight accumulator registers live instead of sixteen, which is what keeps the kernel out of scratch)
+      f32x4 accd[2];
+      if constexpr (ENTRY) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j) accd[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+          f16x8 wdl[2];
+#pragma unroll
+          for (int j = 0; j < 2; ++j) wdl[j] = *reinterpret_cast<const f16x8 *>(lds + OFF_WDL + (((wave * 2 + j) * 2 + c) * 64 + lane) * 16);
+          const f16x8 xh = *reinterpret_cast<const f16x8 *>(a0 + (16 * i + lr) * RS1 + c * 64 + g * 16);
+          const f16x8 xl = *reinterpret_cast<const f16x8 *>(a0 + A1_PLANE + (16 * i + lr) * RS1 + c * 64 + g * 16);
+#pragma unroll
+          for (int pr = 0; pr < 3; ++pr)
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+              accd[j] = ymi_mfma16(pr == 0 ? wdl[j] : wdh[j][c], pr == 1 ? xl : xh, accd[j]);
+        }
+      }
       float tm = 0.f;
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
         const f32x4 sc3 = *reinterpret_cast<const f32x4 *>(lds + OFF_EP + ((wave * 2 + j) * 4 + g) * 32);
         const f32x4 bi3 = *reinterpret_cast<const f32x4 *>(lds + OFF_EP + ((wave * 2 + j) * 4 + g) * 32 + 16);
-        f32x4 v = acc[i][j] * sc3 + bi3 + rv[i][j];
+        f32x4 v;
+        if constexpr (ENTRY) {
+          const f32x4 scd = *reinterpret_cast<const f32x4 *>(lds + OFF_EPD + ((wave * 2 + j) * 4 + g) * 32);
+          const f32x4 bid = *reinterpret_cast<const f32x4 *>(lds + OFF_EPD + ((wave * 2 + j) * 4 + g) * 32 + 16);
+          const f32x4 r = accd[j] * scd + bid;
+          v = acc[i][j] * sc3 + bi3 + r;
+        } else {
+          v = acc[i][j] * sc3 + bi3 + rv[i][j];
+        }
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], slope_a * v[e]);
         if (!ok) v = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -359,7 +465,8 @@ __global__ __launch_bounds__(64 * NW) void chain_h2_k(const std::conditional_t<N
   int tile = blockIdx.x;
   f32x4 ra[2][2], rb[2][2];
   xv = load_x(tile);
-  load_res(tile, ra);
+  if constexpr (ENTRY) x0v = load_x0(tile);
+  else load_res(tile, ra);
   for (; tile < ntiles + (two ? grid : 0); tile += 2 * grid) {      // (+ one iteration for the last tile's second layer)
     iteration(tile, std::integral_constant<int, 0>{}, ra, rb);
     iteration(tile + grid, std::integral_constant<int, 1>{}, rb, ra);
@@ -373,7 +480,8 @@ __global__ __launch_bounds__(64 * NW) void chain_h2_k(const std::conditional_t<N
 
 // y = act_a(scale_a * (W_a x) + bias_a + res),  z = act_b(scale_b * (W_b y) + bias_b): two chained 1x1 convolutions, 64 -> 256 -> 64
 // (include/yolact_amd.h, ymi_chain_desc).  Profiling: record kind 13 = the launch with conv A's algorithmic FLOPs, then — when z
-// is computed — a kind-12 record (no duration of its own) carrying conv B's.
+// is computed — a kind-12 record (no duration of its own) carrying conv B's.  The ENTRY form (x0 != NULL) puts a kind-12 record
+// with the shortcut's FLOPs between the two.
 int ymi_internal_chain2(const ymi_chain_desc *d, hipStream_t s);    // csrc/chain2.hip: 128 / 256 planes, filters streamed through LDS
 
 extern "C" int ymi_pointwise_chain_f32(const ymi_chain_desc *d, void *stream) {
@@ -389,9 +497,18 @@ extern "C" int ymi_pointwise_chain_f32(const ymi_chain_desc *d, void *stream) {
   if ((((uintptr_t)d->x) | ((uintptr_t)d->y) | ((uintptr_t)d->z) | ((uintptr_t)d->res) | ((uintptr_t)d->w_a_h2) | ((uintptr_t)d->w_b_h2)) & 15)
     return YMI_ESHAPE;
   if (d->M * (int64_t)(d->ldy > d->res_ld ? d->ldy : d->res_ld) >= (1LL << 29) || d->M * (int64_t)d->ldx >= (1LL << 29)) return YMI_ESHAPE;   // 32-bit buffer offsets
+  const bool entry = d->x0 != nullptr;      // the ENTRY form: the residual is the projection shortcut of x0, computed in the launch
+  if (entry) {
+    if (wide || d->res || d->k_a != K1 || d->n_a != N1) return YMI_EARG;
+    if (!d->w_d_h2 || !d->scale_d_h2 || !d->x0_amax) return YMI_ENULL;
+    if (d->ldx0 < K1 || (d->ldx0 & 3) || ((((uintptr_t)d->x0) | ((uintptr_t)d->w_d_h2)) & 15)) return YMI_ESHAPE;
+    if (d->M * (int64_t)d->ldx0 >= (1LL << 29) || d->cout_pad_d < N1) return YMI_ESHAPE;
+  }
   if (wide) return ymi_internal_chain2(d, (hipStream_t)stream);
   if (d->cout_pad_a < N1 || (d->z && d->cout_pad_b < 64)) return YMI_ESHAPE;
-  ChainParams p;
+  ChainParamsE p;                           // (sliced to ChainParams for the plain form: that kernel's argument layout is unchanged)
+  p.x0 = d->x0; p.x0_amax = d->x0_amax; p.wd = d->w_d_h2; p.sd = d->scale_d_h2; p.bd = d->bias_d; p.ldx0 = d->ldx0;
+  p.wd_plane = (unsigned)((long)d->cout_pad_d * K1 * 2);
   p.x = d->x; p.res = d->res; p.x_amax = d->x_amax; p.wa = d->w_a_h2; p.wb = d->w_b_h2;
   p.sa = d->scale_a_h2; p.ba = d->bias_a; p.sb = d->scale_b_h2; p.bb = d->bias_b;
   p.y = d->y; p.z = d->z; p.y_amax = d->y_amax; p.z_amax = d->z_amax;
@@ -403,9 +520,15 @@ extern "C" int ymi_pointwise_chain_f32(const ymi_chain_desc *d, void *stream) {
   hipGetDevice(&dev);
   hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
   const long ntiles = (d->M + PX - 1) / PX;
-  hipLaunchKernelGGL(chain_h2_k<64>, dim3((unsigned)(ntiles < cus ? ntiles : cus)), dim3(64 * NW), 0, s, p);
+  const dim3 grid((unsigned)(ntiles < cus ? ntiles : cus));
+  if (entry) hipLaunchKernelGGL((chain_h2_k<64, true>), grid, dim3(64 * NW), 0, s, p);
+  else hipLaunchKernelGGL(chain_h2_k<64>, grid, dim3(64 * NW), 0, s, static_cast<const ChainParams &>(p));
   const int rc = ymi_launch_status();
   ymi_internal_prof_end(pr, s);
+  if (rc == YMI_OK && entry) {              // the shortcut's FLOPs: a kind-12 record of its own, between conv3's and conv1's
+    const int pd = ymi_internal_prof_begin(2.0 * (double)d->M * K1 * N1, YMI_TILE_H2 | YMI_TILE_64x64, 12, s);
+    ymi_internal_prof_end(pd, s);
+  }
   if (rc == YMI_OK && d->z) {
     const int p2 = ymi_internal_prof_begin(2.0 * (double)d->M * N1 * 64, YMI_TILE_H2 | YMI_TILE_64x64, 12, s);
     ymi_internal_prof_end(p2, s);
@@ -421,6 +544,7 @@ extern "C" int ymi_stage_exit_chain_f32(const ymi_stage_exit_desc *e, void *stre
   const ymi_chain_desc *d = &e->chain;
   if (!d->x || !d->w_a_h2 || !d->scale_a_h2 || !d->y || !d->x_amax || !d->z || !d->w_b_h2 || !d->scale_b_h2) return YMI_ENULL;
   if (d->k_a != K1 || d->n_a != N1 || d->n_b != 128 || (e->y_stride != 1 && e->y_stride != 2)) return YMI_EARG;
+  if (d->x0) return YMI_EARG;               // the entry form belongs to the 64-wide pair
   if (d->M <= 0 || e->B <= 0 || e->H <= 0 || e->W <= 0 || d->M != (int64_t)e->B * e->H * e->W) return YMI_EARG;
   if (d->act_a < 0 || d->act_a > YMI_ACT_LEAKY01 || d->act_b < 0 || d->act_b > YMI_ACT_LEAKY01) return YMI_EARG;
   if (d->ldx < K1 || d->ldy < N1 || d->ldz < 128 || (d->res && d->res_ld < N1)) return YMI_ESHAPE;

@@ -153,14 +153,21 @@ class PlanTuning:
         back); a conv3 of that shape WITHOUT such a successor (the last block of the stage) -> the same streaming kernel with its
         second layer switched off.  Either only where measured faster than the launches it replaces: the decision is a table entry
         like every other choice ('chain(B, H, W)' / 'chain1(B, H, W)': [1 | 0, ms of the plan's launches, ms of the chain launch]);
-        YOLACT_AMD_CHAIN=0 keeps the plan's launches (and those of the stage exit, _fuse_stage_exit, which is tried first)."""
-        self.chain_table, self.chainx_table = [], []
+        YOLACT_AMD_CHAIN=0 keeps the plan's launches (and those of the stage exit, _fuse_stage_exit, which is tried first).
+        A pair that is installed and whose residual is a projection shortcut nothing else reads (entry_chain_candidates: layer0.0)
+        may also COMPUTE that shortcut in the launch (the ENTRY form: the 256-channel shortcut tensor is neither written nor read
+        back); decided the same way, table entry 'chain(B, H, W, 64)': [1 | 0, ms of the shortcut on its table tile + the pair
+        launch, ms of the entry launch].  YOLACT_AMD_CHAIN_ENTRY = 1 (default) | 0 | force (install it whatever the table says)."""
+        self.chain_table, self.chainx_table, self.chaine_table = [], [], []
         if not self.h2 or os.environ.get('YOLACT_AMD_CHAIN', '1') != '1':
             return
         lib = self.lib
 
         def timed(run):
             return _timed(run, e0, e1, reps)
+        entry_mode = os.environ.get('YOLACT_AMD_CHAIN_ENTRY', '1')
+        # (on the op list as built: the stage exit below replaces launches, never moves them, so the indices hold)
+        entry = {i3: idn for idn, i3, _ in self.entry_chain_candidates()} if entry_mode in ('1', 'force') else {}
         self._fuse_stage_exit(s, disk, measure, timed)       # (first: a 'chainx' decision of 1 takes the op before 'chain1' sees it)
         i = 0
         while i < len(self.ops):
@@ -223,6 +230,43 @@ class PlanTuning:
                 if pair:
                     self.ops[i] = ('nop', None, n1 + '[fused into ' + n3 + ']', w1)
                     i += 1
+                    if P_ == 64 and (i - 2) in entry:
+                        self._fuse_entry_shortcut(i - 2, entry[i - 2], cd, s, disk, measure, timed, entry_mode)
+
+    def _fuse_entry_shortcut(self, ic, idn, cd, s, disk, measure, timed, mode):
+        """The pair launch just installed at op `ic` (descriptor `cd`) -> its ENTRY form, with the projection shortcut of op `idn`
+        computed inside (_fuse_pointwise_chains).  The chain op keeps its function and its name; the shortcut's op becomes a nop
+        (its record / wait markers stay where they are)."""
+        lib = self.lib
+        fd, pd, nd, wd = self.ops[idn]
+        ce = self._entry_chain_desc(cd, idn)
+        if ce is None:
+            return
+        dd = pd.contents
+        eptr, cptr = C.pointer(ce), C.pointer(cd)
+        key = TT.chain_key('chain', dd.B, dd.Ho, dd.Wo, 64, self.mode)
+        ent = disk.get(key)
+        if mode == 'force':
+            ent = [1, 0.0, 0.0]
+        if ent is None:
+            self.tune_misses += 1
+            if not measure or lib.ymi_pointwise_chain_f32(eptr, s) != 0:
+                return
+            t_plan = timed(lambda: (fd(pd, s), lib.ymi_pointwise_chain_f32(cptr, s)))
+            t_one = timed(lambda: lib.ymi_pointwise_chain_f32(eptr, s))
+            ent = disk[key] = [1 if t_one < 0.97 * t_plan else 0, round(t_plan, 4), round(t_one, 4)]
+        fc, _, nc, wc = self.ops[ic]
+        self.chaine_table.append((nc, ent[0], ent[1], ent[2]))
+        if ent[0] and lib.ymi_pointwise_chain_f32(eptr, s) == 0:
+            self.keepalive.append(ce)
+            self.ops[ic] = (fc, eptr, nc, wc)
+            self.ops[idn] = ('nop', None, nd + '[fused into ' + nc.split('+')[0] + ']', wd)
+            # profile records map onto conv_meta by position (kind 13 = conv3, kind 12 = the shortcut, kind 12 = conv1)
+            names = [n for n, _ in self.conv_meta]
+            n3 = nc.split('+')[0]
+            if nd in names and n3 in names:
+                m = self.conv_meta.pop(names.index(nd))
+                self.conv_meta.insert([n for n, _ in self.conv_meta].index(n3) + 1, m)
 
     def stage_exit_candidates(self):
         """Op indices (conv3, conv1, [stride-2 readers]) of every stage exit ymi_stage_exit_chain_f32 can take (csrc/chain.hip,
@@ -284,6 +328,91 @@ class PlanTuning:
             if ok:
                 out.append((i3, i1, downs))
         return out
+
+    def entry_chain_candidates(self):
+        """Op indices (shortcut, conv3, conv1) of every 64-plane pair whose residual ymi_pointwise_chain_f32 can COMPUTE instead of
+        reading it (csrc/chain.hip, chain_h2_k<64, true>): a 1x1 64 -> 256 + RES_ADD conv3 directly followed by the 1x1 256 -> 64
+        conv1 that reads its output, whose residual is the output of a 1x1 / stride-1 / pad-0 64 -> 256 convolution of one segment
+        with no activation and no residual (the block's projection shortcut), at conv3's pixels, and which nothing but conv3 reads.
+        Pure shape logic on the op list (works on a dry CPU plan): fp16x2 planes, magnitude slots and aliasing are checked where the
+        launch is installed (_fuse_pointwise_chains).  ResNet plans have one such block, layer0.0; DarkNet plans have none."""
+        conv = self.lib.ymi_conv2d_nhwc_f32
+        out = []
+        for i3, (f3, p3, _, w3) in enumerate(self.ops):
+            if f3 is not conv or i3 in self.wide_ops or i3 + 1 >= len(self.ops):
+                continue
+            d3 = p3.contents
+            if not ((d3.kh, d3.kw, d3.stride, d3.pad, d3.nseg, d3.Cin, d3.Cout) == (1, 1, 1, 0, 1, 64, 256)
+                    and d3.res_mode == L.RES_ADD and not d3.res_after_act and d3.seg[0].n0 == 0 and d3.seg[0].act <= L.ACT_LEAKY01
+                    and d3.res):
+                continue
+            f1, p1, _, w1 = self.ops[i3 + 1]
+            if f1 is not conv or w1 != w3 or (i3 + 1) in self.wide_ops:
+                continue
+            d1 = p1.contents
+            if not ((d1.kh, d1.kw, d1.stride, d1.pad, d1.Cin, d1.Cout, d1.nseg) == (1, 1, 1, 0, 256, 64, 1)
+                    and d1.res_mode == L.RES_NONE and d1.x == d3.seg[0].ptr and d1.ldx == d3.seg[0].row_stride
+                    and d1.seg[0].n0 == 0 and d1.seg[0].act <= L.ACT_LEAKY01):
+                continue
+            rptr = int(d3.res)
+            idn = None
+            for j in range(i3 - 1, -1, -1):                  # the launch that wrote the residual: the last one before conv3 that names it
+                fj, pj, _, _ = self.ops[j]
+                if fj is conv and any(int(pj.contents.seg[k].ptr or 0) == rptr for k in range(pj.contents.nseg)):
+                    idn = j
+                    break
+            if idn is None or idn in self.wide_ops:
+                continue
+            dd = self.ops[idn][1].contents
+            if not ((dd.kh, dd.kw, dd.stride, dd.pad, dd.nseg, dd.Cin, dd.Cout) == (1, 1, 1, 0, 1, 64, 256)
+                    and dd.res_mode == L.RES_NONE and dd.seg[0].act == L.ACT_NONE and dd.seg[0].n0 == 0
+                    and (dd.B, dd.Ho, dd.Wo) == (d3.B, d3.Ho, d3.Wo) and dd.seg[0].row_stride == d3.res_ld
+                    and int(dd.x or 0) != rptr):
+                continue
+            # every other launch that names the shortcut tensor, in program order from the shortcut on: the arena frees its buffer
+            # after conv3, so the first one may be the launch that WRITES the next tensor put there (a convolution that names the
+            # address as an output only) — behind that one the address means another tensor.  Anything else that names it first is
+            # a reader, or a launch this scan cannot tell from one
+            ok = True
+            for j in range(idn + 1, len(self.ops)):
+                fj, pj, _, _ = self.ops[j]
+                if j == i3 or isinstance(fj, str):
+                    continue
+                if isinstance(pj, tuple):                    # pooling / resize passes
+                    ptrs = [a for a in pj if isinstance(a, int)]
+                else:
+                    ptrs = _desc_pointers(pj.contents)
+                if rptr not in ptrs:
+                    continue
+                if fj is conv:
+                    dj = pj.contents
+                    n_out = sum(1 for k in range(dj.nseg) if int(dj.seg[k].ptr or 0) == rptr)
+                    ok = ptrs.count(rptr) == n_out
+                else:
+                    ok = False
+                break
+            if ok:
+                out.append((idn, i3, i3 + 1))
+        return out
+
+    def _entry_chain_desc(self, cd, idn):
+        """The ENTRY form of a pair's ymi_chain_desc `cd` (a copy: the residual is computed from the shortcut's input by the
+        launch), or None where the shortcut of op `idn` has no fp16x2 planes / magnitude slot or the buffers break the aliasing
+        contract of include/yolact_amd.h: y must not overlap x0, z may overlap x0 only exactly in place (the arena hands
+        conv1's output a buffer the block has just freed: conv3's input or the block input, both M x 64)."""
+        dd = self.ops[idn][1].contents
+        if not (dd.w_h2 and dd.scale_h2 and dd.x_amax and dd.x):
+            return None
+        ce = L.ChainDesc.from_buffer_copy(cd)
+        ce.res, ce.res_ld = None, 0
+        ce.x0, ce.ldx0, ce.x0_amax = dd.x, dd.ldx, dd.x_amax
+        ce.w_d_h2, ce.scale_d_h2, ce.bias_d, ce.cout_pad_d = dd.w_h2, dd.scale_h2, dd.bias, _ceil(dd.Cout, 128)
+        M = int(ce.M)
+        if M * ce.ldx0 >= (1 << 29) or _rows_overlap(M, ce.y, ce.ldy, ce.x0, ce.ldx0):
+            return None
+        if _rows_overlap(M, ce.z, ce.ldz, ce.x0, ce.ldx0) and not (int(ce.z) == int(ce.x0) and ce.ldz == ce.ldx0):
+            return None
+        return ce
 
     def _fuse_stage_exit(self, s, disk, measure, timed):
         """layer0.2.conv3 (+ shortcut, ReLU) and layer1.0.conv1 (256 -> 128) -> ONE ymi_stage_exit_chain_f32 launch that takes y from LDS

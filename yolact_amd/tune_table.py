@@ -5,7 +5,10 @@
            dcn     the same 12 ints + 'dcn'                                          -> direct choice
            wino    (B, H, W, C, Cout, act, nseg, (m, ...))    -> [m, Winograd choice, direct ms, Winograd ms, F(2x2) ms, F(4x4) ms]
            chain   (B, H, W[, P])  /  chain1 (B, H, W[, P])  /  chainx (B, H, W)     -> [1 | 0, ms of the plan's launches, ms of the fused one]
-           instep|<wino key>                                                         -> 0: keep the direct kernel (tools/instep_tune.py)
+                   chain (B, H, W, 64): the ENTRY form of the 64-plane pair (the block's projection shortcut computed inside the pair
+                   launch, csrc/chain.hip) -> [1 | 0, ms of the shortcut launch + the pair launch, ms of the entry launch]; the pair's
+                   own decision stays under chain (B, H, W), which never spells P for 64 planes
+           instep|<wino key>                                                      -> 0: keep the direct kernel (tools/instep_tune.py)
     value  direct choice   = tile id + 256 * split_k (split_k 0 = unsplit)
            Winograd choice = GEMM tile id (+ WINO_PLANES: V written as fp16x2 planes)
 
@@ -141,7 +144,8 @@ def wino_key(B, H, W, C, Cout, act, nseg, ms, mode=''):
 
 
 def chain_key(kind, B, H, W, P=None, mode=''):
-    """kind 'chain' (conv3 + the next conv1) | 'chain1' (conv3 alone); P only for the wider stages of csrc/chain2.hip (P > 64)."""
+    """kind 'chain' (conv3 + the next conv1) | 'chain1' (conv3 alone); P only for the wider stages of csrc/chain2.hip (P > 64) and,
+    as ('chain', ..., 64), for the entry form of the 64-plane pair (the projection shortcut computed in the pair launch)."""
     if kind not in ('chain', 'chain1'):
         raise ValueError(kind)
     return format(kind, (B, H, W) + ((P,) if P is not None else ()), mode)
