@@ -233,6 +233,29 @@ typedef struct {
   const float *proj_scale_h2, *proj_bias;   /* proj_bias may be NULL */
   float *proj_y, *proj_y_amax;              /* proj_y_amax: magnitude-bound slot of proj_y, may be NULL */
   int32_t proj_cout, proj_ldy, proj_act, _pad5;
+  /* Level table (trailing fields, ABI number unchanged; all zero = the launch above).  nlev = 2..5: ONE input transform, ONE
+   * grouped GEMM and ONE output transform apply the same filters to nlev feature maps of different sizes (the prediction heads of
+   * P4..P7 share their weights: yolact.py:133-212, share_prediction_module).  V / M rows are level-major: all tiles of lev[0] in
+   * (b, ty, tx) order, then lev[1], ...; T = B * sum_l ceil(H_l / 4) * ceil(W_l / 4) (also what YMI_WS_WINO_V / _M return).
+   * x, y, H, W, x_amax above are ignored; B, C, Cout, act, scale, bias, seg[], tile hold for every level.  Accepted only with
+   * m = 4, tile | YMI_TILE_H2 (v_planes 1 or 0), no x_up, no proj_*: anything else is YMI_EARG.
+   * The merged V has ONE power-of-two scale, derived from the largest of the levels' bounds.  Where the levels name different
+   * x_amax slots the input transform writes that maximum to lev_amax (a slot of the caller's, zeroed like every other slot; required
+   * then) and the GEMM reads it there; where they all name the same slot the GEMM reads that slot and lev_amax is not touched.
+   * nseg = 0: level l writes its dense y and raises its own y_amax (may be NULL; levels may share one slot).
+   * nseg = 1..3: level l writes segment k at (char *)seg[k].ptr + seg_off[k]; y_amax above is raised as in the single launch.
+   * Profile: the launch is recorded with the algorithmic FLOPs of lev[0]; the nabs <= 8 layers it absorbed follow as records of
+   * kind 12 (abs_flops[i], no duration), so that records keep mapping onto the caller's layer list by position. */
+  int32_t nlev, nabs;
+  struct {
+    const float *x;       /* [B,H,W,C] */
+    const float *x_amax;
+    float *y, *y_amax;    /* nseg = 0 */
+    int64_t seg_off[3];   /* nseg > 0: bytes */
+    int32_t H, W;
+  } lev[5];
+  float *lev_amax;
+  double abs_flops[8];
 } ymi_wino_desc;
 int ymi_conv3x3_winograd_f32(const ymi_wino_desc *d, void *stream);
 
@@ -1250,7 +1273,7 @@ int ymi_plan_run(const ymi_plan_op *ops, int first, int last, void *stream_a, vo
  * at the descriptor of the call it belongs to (only shape fields are read, pointers may be NULL).  Returns the size in bytes
  * (>= 0; 0 = the call needs no such workspace in this configuration) or a negative YMI_E* code. */
 enum {
-  YMI_WS_WINO_V = 1,        /* desc: ymi_wino_desc      -> ymi_wino_desc.V  = G*T*C floats, T = B*ceil(H/m)*ceil(W/m), G = (m+2)^2 */
+  YMI_WS_WINO_V = 1,        /* desc: ymi_wino_desc      -> ymi_wino_desc.V  = G*T*C floats, T = B*ceil(H/m)*ceil(W/m) (nlev > 0: summed over lev[]), G = (m+2)^2 */
   YMI_WS_WINO_M = 2,        /* desc: ymi_wino_desc      -> ymi_wino_desc.M  = G*T*ceil(Cout/4)*4 floats */
   YMI_WS_SPLITK = 3,        /* desc: ymi_conv_desc      -> ymi_conv_desc.split_ws = split_k * B*Ho*Wo * Cout floats (0 when split_k <= 1) */
   YMI_WS_MASK_IOU = 4,      /* desc: ymi_mask_iou_shape -> ymi_mask_iou_f32's ws = A*B + A + B floats */

@@ -4,7 +4,8 @@
     python tools/make_tune_table.py [--out yolact_amd/tune/gfx950.json] [--fresh] [--only NAME ...]
 
 Every (config, batch, size) below is planned once with on-device measurement of every shape the table does not know yet
-(HIP events on the launch stream, engine.Plan.tune: tiles, Winograd against direct, and the chain fusions — the pair 'chain(B, H, W)',
+(HIP events on the launch stream, engine.Plan.tune: tiles, Winograd against direct, the merged P4..P7 head launches under their
+virtual Winograd shapes (tune_table.level_key), and the chain fusions — the pair 'chain(B, H, W)',
 the stage exit 'chainx(B, H, W)' and, where the pair is installed, its entry form 'chain(B, H, W, 64)'); entries accumulate in ONE file, so a shape shared by several plans
 is measured once and every plan that contains it runs the same tile (bit-identical results across plans that share
 layers).  The default plan of the product then reads the table and measures nothing: deterministic across processes and
@@ -79,7 +80,10 @@ def main():
         torch.cuda.synchronize()
         n_w = sum(1 for op in plan.ops if isinstance(op[2], str) and op[2].endswith('[wino]'))
         log.append({'plan': name, 'config': config, 'batch': B, 'size': size, 'measured_shapes': plan.tune_misses,
-                    'winograd_layers': n_w, 'seconds': round(time.time() - t0, 1)})
+                    'winograd_layers': n_w, 'seconds': round(time.time() - t0, 1),
+                    # the P4..P7 heads as one Winograd layer per shared conv (tune_table.level_key): installed?, and per merged
+                    # launch (key, choice, summed ms of the per-level launches, ms of the merged launch)
+                    'merged_levels': bool(plan.merged_levels), 'level_table': getattr(plan, 'level_table', [])})
         print(log[-1], flush=True)
         del net, plan, x
         torch.cuda.empty_cache()

@@ -84,6 +84,12 @@ class ConvDesc(C.Structure):
                 ('y_amax', C.c_void_p), ('x_amax_mul', C.c_float), ('_pad3', C.c_int32)]
 
 
+class WinoLevel(C.Structure):
+    """One entry of ymi_wino_desc.lev[]."""
+    _fields_ = [('x', C.c_void_p), ('x_amax', C.c_void_p), ('y', C.c_void_p), ('y_amax', C.c_void_p),
+                ('seg_off', C.c_int64 * 3), ('H', C.c_int32), ('W', C.c_int32)]
+
+
 class WinoDesc(C.Structure):
     _fields_ = [('x', C.c_void_p), ('u', C.c_void_p), ('scale', C.c_void_p), ('bias', C.c_void_p), ('y', C.c_void_p),
                 ('V', C.c_void_p), ('M', C.c_void_p),
@@ -94,7 +100,9 @@ class WinoDesc(C.Structure):
                 ('x_up', C.c_void_p), ('up_relu', C.c_int32), ('_pad4', C.c_int32),
                 ('proj_w_h2', C.c_void_p), ('proj_scale_h2', C.c_void_p), ('proj_bias', C.c_void_p),
                 ('proj_y', C.c_void_p), ('proj_y_amax', C.c_void_p),
-                ('proj_cout', C.c_int32), ('proj_ldy', C.c_int32), ('proj_act', C.c_int32), ('_pad5', C.c_int32)]
+                ('proj_cout', C.c_int32), ('proj_ldy', C.c_int32), ('proj_act', C.c_int32), ('_pad5', C.c_int32),
+                ('nlev', C.c_int32), ('nabs', C.c_int32), ('lev', WinoLevel * 5), ('lev_amax', C.c_void_p),
+                ('abs_flops', C.c_double * 8)]
 
 
 class DcnDesc(C.Structure):

@@ -48,8 +48,17 @@ int64_t ymi_workspace_bytes(int what, const void *desc) {
     case YMI_WS_WINO_M: {
       const ymi_wino_desc *d = (const ymi_wino_desc *)desc;
       const int m = d->m == 4 ? 4 : 2;
+      int64_t G = (int64_t)(m + 2) * (m + 2), T = 0;
+      if (d->nlev != 0) {          // level table: the tiles of every level, one after the other
+        if (d->nlev < 2 || d->nlev > 5 || d->m != 4 || d->B < 1 || d->C < 1 || d->Cout < 1) return -1;
+        for (int l = 0; l < d->nlev; ++l) {
+          if (d->lev[l].H < 1 || d->lev[l].W < 1) return -1;
+          T += (int64_t)d->B * cdiv(d->lev[l].H, 4) * cdiv(d->lev[l].W, 4);
+        }
+        return 4 * G * T * (what == YMI_WS_WINO_V ? (int64_t)d->C : cdiv(d->Cout, 4) * 4);
+      }
       if ((d->m != 0 && d->m != 2 && d->m != 4) || d->B < 1 || d->H < 1 || d->W < 1 || d->C < 1 || d->Cout < 1) return -1;
-      const int64_t G = (int64_t)(m + 2) * (m + 2), T = (int64_t)d->B * cdiv(d->H, m) * cdiv(d->W, m);
+      T = (int64_t)d->B * cdiv(d->H, m) * cdiv(d->W, m);
       return 4 * G * T * (what == YMI_WS_WINO_V ? (int64_t)d->C : cdiv(d->Cout, 4) * 4);
     }
     case YMI_WS_SPLITK: {

@@ -337,15 +337,70 @@ __device__ __forceinline__ void up2_coord(int dst, int in_size, float &l1) {
 // r >> 1 and (r >> 1) + 1 (window addresses clamped to the image: where the reference clamps i0 / i1 the weights it derives are
 // such that the duplicated row reproduces its arithmetic), with the weights of up_coord and the operation order of
 // bilinear_nhwc_k: hy * (hx * v00 + lx * v01) + ly * (hx * v10 + lx * v11).  16 loads instead of 36, no upsampled tensor in HBM.
-template <bool PLANES, bool UPS = false>
+// ---- level table (ymi_wino_desc.nlev): ONE launch of each of the three F(4x4) kernels for up to 5 feature maps that share their
+// filters.  V / M rows are level-major; a row finds its level from the prefix table t0[] (at most 5 entries, passed by value like
+// SegTab) and from there on does exactly what the single-level launch does for that level's geometry.  NoLev = no table: the
+// single-level kernels instantiate the same bodies with it and compile to the code they had before the table existed.
+struct NoLev {};
+struct LevTab {
+  int nlev;
+  int t0[5];                   // first V / M row of level l
+  int H[5], W[5], th[5], tw[5];
+  const float *x[5];
+  const float *x_amax[5];
+  float *y[5], *y_amax[5];     // nseg = 0
+  long off[5][3];              // nseg > 0: FLOATS added to seg[k].ptr
+  float *pub;                  // where the input transform publishes the largest of the levels' bounds (or nullptr)
+};
+struct LevGeo { int l, H, W, th, tw; unsigned t0; };
+__device__ __forceinline__ LevGeo lev_pick(const LevTab &lt, unsigned tu) {
+  LevGeo g = {0, lt.H[0], lt.W[0], lt.th[0], lt.tw[0], 0u};
+#pragma unroll
+  for (int k = 1; k < 5; ++k)
+    if (k < lt.nlev && tu >= (unsigned)lt.t0[k]) { g.l = k; g.H = lt.H[k]; g.W = lt.W[k]; g.th = lt.th[k]; g.tw = lt.tw[k]; g.t0 = (unsigned)lt.t0[k]; }
+  return g;
+}
+template <class P>
+__device__ __forceinline__ P lev_sel(P const (&a)[5], int l) {
+  P v = a[0];
+#pragma unroll
+  for (int k = 1; k < 5; ++k) v = l == k ? a[k] : v;
+  return v;
+}
+// the bound of the merged V: the largest of the levels' bounds (every wave reads the <= 5 slots; wave-uniform result)
+__device__ __forceinline__ float lev_amax_read(const LevTab &lt) {
+  float m = ymi_amax_read(lt.x_amax[0]);
+#pragma unroll
+  for (int k = 1; k < 5; ++k)
+    if (k < lt.nlev) m = fmaxf(m, ymi_amax_read(lt.x_amax[k]));
+  return m;
+}
+
+template <bool PLANES, bool UPS = false, class LT = NoLev>
 __global__ __launch_bounds__(256) void wino43_in_k(const float *__restrict__ x, float *__restrict__ V, int H, int W, int C4,
                                                    int th, int tw, long T, long total, const float *__restrict__ x_amax,
-                                                   int up_relu = 0) {
+                                                   int up_relu, const LT lt) {
+  constexpr bool LEV = !__is_same(LT, NoLev);
   float vs = 1.f, vinv = 1.f;
-  if (PLANES) ymi_h2_scale(ymi_amax_read(x_amax) * 100.f, vs, vinv);
+  if constexpr (LEV) {
+    if (PLANES || lt.pub) {
+      const float bound = lev_amax_read(lt);
+      if (PLANES) ymi_h2_scale(bound * 100.f, vs, vinv);
+      if (lt.pub && blockIdx.x == 0 && threadIdx.x == 0) lt.pub[0] = bound;      // sub-slot 0; the others stay zero: the GEMM reads the maximum
+    }
+  } else {
+    if (PLANES) ymi_h2_scale(ymi_amax_read(x_amax) * 100.f, vs, vinv);
+  }
   for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < (unsigned)total; i += gridDim.x * 256u) {   // 32-bit index math
-    const unsigned tu = i / (unsigned)C4, ru = tu / (unsigned)tw, bu = ru / (unsigned)th;          // (total < 2^31, host-checked;
-    const int c4 = (int)(i - tu * (unsigned)C4), tx = (int)(tu - ru * (unsigned)tw), ty = (int)(ru - bu * (unsigned)th);   // 64-bit
+    const unsigned tu = i / (unsigned)C4;                    // the V row (level-major with a table)
+    unsigned tl = tu;                                        // ... and the tile's index inside its level
+    if constexpr (LEV) {
+      const LevGeo g = lev_pick(lt, tu);
+      H = g.H; W = g.W; th = g.th; tw = g.tw; tl = tu - g.t0;
+      x = lev_sel(lt.x, g.l);
+    }
+    const unsigned ru = tl / (unsigned)tw, bu = ru / (unsigned)th;                                 // (total < 2^31, host-checked;
+    const int c4 = (int)(i - tu * (unsigned)C4), tx = (int)(tl - ru * (unsigned)tw), ty = (int)(ru - bu * (unsigned)th);   // 64-bit
     const long t = tu, b = bu;                                                                  // div / mod cost ~3x the transform)
     const int y0 = 4 * ty - 1, x0 = 4 * tx - 1;
     f32x4 u[6][6];                         // u = B^T d, built column by column
@@ -443,15 +498,34 @@ __device__ __forceinline__ void wino43_out_tile(const float *__restrict__ src, l
   for (int iy = 0; iy < 4; ++iy) at6(s[iy][0], s[iy][1], s[iy][2], s[iy][3], s[iy][4], s[iy][5], o[iy][0], o[iy][1], o[iy][2], o[iy][3]);
 }
 
+// per-level running maxima of the dense level-table launch (compile-time indices + selects, as seg_amax_add)
+__device__ __forceinline__ void lev_amax_add(float (&am)[5], int l, float v) {
+#pragma unroll
+  for (int k = 0; k < 5; ++k) am[k] = l == k ? fmaxf(am[k], v) : am[k];
+}
+
+template <class LT = NoLev>
 __global__ __launch_bounds__(256) void wino43_out_k(const float *__restrict__ Mm, float *__restrict__ y,
                                                     const float *__restrict__ scale, const float *__restrict__ bias, int Ho,
                                                     int Wo, int N4, int th, int tw, long T, int act, long total,
-                                                    float *__restrict__ y_amax) {
+                                                    float *__restrict__ y_amax, const LT lt) {
+  constexpr bool LEV = !__is_same(LT, NoLev);
   float am = 0.f;
-  const ymi_amax_pre apre = ymi_amax_prefetch(y_amax);
+  float aml[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+  ymi_amax_pre apre;
+  if constexpr (!LEV) apre = ymi_amax_prefetch(y_amax);
   for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < (unsigned)total; i += gridDim.x * 256u) {   // 32-bit index math
-    const unsigned tu = i / (unsigned)N4, ru = tu / (unsigned)tw, bu = ru / (unsigned)th;          // (total < 2^31, host-checked;
-    const int n4 = (int)(i - tu * (unsigned)N4), tx = (int)(tu - ru * (unsigned)tw), ty = (int)(ru - bu * (unsigned)th);   // 64-bit
+    const unsigned tu = i / (unsigned)N4;                    // the M row (level-major with a table)
+    unsigned tl = tu;                                        // ... and the tile's index inside its level
+    int lv = 0;
+    if constexpr (LEV) {
+      const LevGeo g = lev_pick(lt, tu);
+      Ho = g.H; Wo = g.W; th = g.th; tw = g.tw; tl = tu - g.t0; lv = g.l;
+      y = lev_sel(lt.y, g.l);
+      am = 0.f;
+    }
+    const unsigned ru = tl / (unsigned)tw, bu = ru / (unsigned)th;                                 // (total < 2^31, host-checked;
+    const int n4 = (int)(i - tu * (unsigned)N4), tx = (int)(tl - ru * (unsigned)tw), ty = (int)(ru - bu * (unsigned)th);   // 64-bit
     const long t = tu, b = bu;                                                                  // div / mod cost ~3x the transform)
     f32x4 o[4][4];
     wino43_out_tile(Mm + t * (N4 * 4L) + n4 * 4, T * (N4 * 4L), o);
@@ -477,8 +551,15 @@ __global__ __launch_bounds__(256) void wino43_out_k(const float *__restrict__ Mm
         const int oy = 4 * ty + iy, ox = 4 * tx + ix;
         if (oy < Ho && ox < Wo) *reinterpret_cast<f32x4 *>(y + ((b * Ho + oy) * (long)Wo + ox) * (N4 * 4L) + n4 * 4) = o[iy][ix];
       }
+    if constexpr (LEV) lev_amax_add(aml, lv, am);
   }
-  if (y_amax) ymi_amax_finish(apre, am);
+  if constexpr (LEV) {       // every level raises its own slot (a converged point of the wave; levels may share a slot)
+#pragma unroll
+    for (int k = 0; k < 5; ++k)
+      if (k < lt.nlev && lt.y_amax[k]) ymi_amax_finish(ymi_amax_prefetch(lt.y_amax[k]), aml[k]);
+  } else {
+    if (y_amax) ymi_amax_finish(apre, am);
+  }
 }
 
 // ---- F(4x4,3x3) output transform + the 1x1 convolution that consumes it, in one launch (ymi_wino_desc.proj_*) ------------------
@@ -595,14 +676,33 @@ __global__ __launch_bounds__(256) void wino43_out_proj_k(const float *__restrict
 #endif
 }
 
-__global__ __launch_bounds__(256) void wino43_out_seg_k(const float *__restrict__ Mm, const SegTab st,
+template <class LT = NoLev>
+__global__ __launch_bounds__(256) void wino43_out_seg_k(const float *__restrict__ Mm, const SegTab st0,
                                                         const float *__restrict__ scale, const float *__restrict__ bias,
-                                                        int Ho, int Wo, int N4, int Cout, int th, int tw, long T, long total, float *__restrict__ y_amax) {
+                                                        int Ho, int Wo, int N4, int Cout, int th, int tw, long T, long total,
+                                                        float *__restrict__ y_amax, const LT lt) {
+  constexpr bool LEV = !__is_same(LT, NoLev);
   float am[3] = {0.f, 0.f, 0.f};
   const ymi_amax_pre apre = ymi_amax_prefetch(y_amax);
   for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < (unsigned)total; i += gridDim.x * 256u) {   // 32-bit index math
-    const unsigned tu = i / (unsigned)N4, ru = tu / (unsigned)tw, bu = ru / (unsigned)th;          // (total < 2^31, host-checked;
-    const int n4 = (int)(i - tu * (unsigned)N4), tx = (int)(tu - ru * (unsigned)tw), ty = (int)(ru - bu * (unsigned)th);   // 64-bit
+    const unsigned tu = i / (unsigned)N4;                    // the M row (level-major with a table)
+    unsigned tl = tu;                                        // ... and the tile's index inside its level
+    SegTab stl;                                              // with a table: this level's rows of the level-concatenated tensors
+    if constexpr (LEV) {
+      const LevGeo g = lev_pick(lt, tu);
+      Ho = g.H; Wo = g.W; th = g.th; tw = g.tw; tl = tu - g.t0;
+      stl = st0;
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        long off = lt.off[0][k];
+#pragma unroll
+        for (int q = 1; q < 5; ++q) off = g.l == q ? lt.off[q][k] : off;
+        stl.seg[k].ptr = st0.seg[k].ptr ? st0.seg[k].ptr + off : nullptr;
+      }
+    }
+    const SegTab &st = LEV ? stl : st0;
+    const unsigned ru = tl / (unsigned)tw, bu = ru / (unsigned)th;                                 // (total < 2^31, host-checked;
+    const int n4 = (int)(i - tu * (unsigned)N4), tx = (int)(tl - ru * (unsigned)tw), ty = (int)(ru - bu * (unsigned)th);   // 64-bit
     const long t = tu, b = bu;                                                                  // div / mod cost ~3x the transform)
     f32x4 o[4][4];
     wino43_out_tile(Mm + t * (N4 * 4L) + n4 * 4, T * (N4 * 4L), o);
@@ -645,7 +745,7 @@ __global__ __launch_bounds__(256) void wino43_out_seg_k(const float *__restrict_
       }
     }
   }
-  seg_amax_commit(y_amax, st.nseg, apre, am);
+  seg_amax_commit(y_amax, st0.nseg, apre, am);
 }
 
 unsigned grid_for(long total) {
@@ -656,7 +756,92 @@ unsigned grid_for(long total) {
 
 }  // namespace
 
+// ymi_wino_desc.nlev = 2..5: the three launches of an F(4x4) fp16x2 layer, once, for every level of the table
+static int wino_levels(const ymi_wino_desc *d, hipStream_t s) {
+  if (d->nlev < 2 || d->nlev > 5 || d->m != 4 || !(d->tile & YMI_TILE_H2) || (d->tile & YMI_TILE_X3) || d->x_up || d->proj_w_h2 ||
+      (d->v_planes != 0 && d->v_planes != 1) || d->nabs < 0 || d->nabs > 8)
+    return YMI_EARG;
+  if (d->B <= 0 || d->C <= 0 || d->Cout <= 0 || d->nseg < 0 || d->nseg > 3) return YMI_EARG;
+  LevTab lt = {};
+  lt.nlev = d->nlev;
+  long T = 0;
+  bool one_slot = true;
+  for (int l = 0; l < d->nlev; ++l) {
+    if (d->lev[l].H <= 0 || d->lev[l].W <= 0) return YMI_EARG;
+    for (int k = 0; k < d->nseg; ++k) if (d->lev[l].seg_off[k] & 3) return YMI_EARG;
+    if (!d->lev[l].x || !d->lev[l].x_amax || (d->nseg == 0 && !d->lev[l].y)) return YMI_ENULL;
+    lt.H[l] = d->lev[l].H; lt.W[l] = d->lev[l].W;
+    lt.th[l] = (d->lev[l].H + 3) / 4; lt.tw[l] = (d->lev[l].W + 3) / 4;
+    lt.x[l] = d->lev[l].x; lt.x_amax[l] = d->lev[l].x_amax; lt.y[l] = d->lev[l].y; lt.y_amax[l] = d->lev[l].y_amax;
+    for (int k = 0; k < 3; ++k) lt.off[l][k] = (long)(d->lev[l].seg_off[k] / 4);
+    one_slot = one_slot && d->lev[l].x_amax == d->lev[0].x_amax;
+    if (T >= (1L << 29)) return YMI_ESHAPE;
+    lt.t0[l] = (int)T;
+    T += (long)d->B * lt.th[l] * lt.tw[l];
+  }
+  if (!d->u || !d->V || !d->M || !d->u_h2 || !d->uinv_h2 || (!one_slot && !d->lev_amax)) return YMI_ENULL;
+  if (d->nseg == 0 && ((d->Cout & 3) || d->act > YMI_ACT_LEAKY01 || d->act < 0)) return YMI_ESHAPE;
+  for (int k = 0; k < d->nseg; ++k) if (!d->seg[k].ptr) return YMI_ENULL;
+  if (d->C & 31) return YMI_ESHAPE;
+  const int Ng = (d->Cout + 3) / 4 * 4;
+  if (T * (long)(d->C > Ng ? d->C : Ng) >= (1L << 29)) return YMI_ESHAPE;   // per-group tensors < 2 GiB
+  const int C4 = d->C / 4, N4 = Ng / 4;
+  const float *bound = one_slot ? d->lev[0].x_amax : d->lev_amax;            // what the GEMM un-scales by: the transform's own value
+  lt.pub = one_slot ? nullptr : d->lev_amax;
+  const bool planes = d->v_planes != 0;
+  if ((d->tile & 31) == YMI_TILE_WG_128x256 && !planes) return YMI_EARG;      // the persistent grouped GEMM takes planes only
+  // profile: the layer record carries lev[0]'s algorithmic FLOPs (the absorbed layers follow as kind 12), the GEMM record what it executes
+  const double alg = 2.0 * d->B * d->lev[0].H * d->lev[0].W * (double)(d->cout_alg > 0 ? d->cout_alg : d->Cout) * 9.0 * d->C;
+  const double exe = 2.0 * 36 * (double)T * d->C * Ng;
+  const int outer = ymi_internal_prof_begin(alg, d->tile, 4, s);
+  const float *nox = nullptr;
+  if (planes) hipLaunchKernelGGL((wino43_in_k<true, false, LevTab>), dim3(grid_for(T * C4)), dim3(256), 0, s, nox, d->V, 0, 0, C4, 0, 0, T, T * C4, nox, 0, lt);
+  else hipLaunchKernelGGL((wino43_in_k<false, false, LevTab>), dim3(grid_for(T * C4)), dim3(256), 0, s, nox, d->V, 0, 0, C4, 0, 0, T, T * C4, nox, 0, lt);
+  int rc = ymi_launch_status();
+  if (rc) return rc;
+  const long cout_pad = ((long)d->Cout + 127) / 128 * 128;
+  if ((d->tile & 31) == YMI_TILE_WG_128x256) {
+    rc = ymi_internal_wgemm(d->V, d->u_h2, d->uinv_h2, bound, 100.f, d->M, 36, T, d->C, Ng, (int)cout_pad, exe, 6, s);
+  } else {
+    ymi_conv_desc g = {};
+    g.x = d->V; g.w = d->u;
+    g.B = 1; g.H = (int)T; g.W = 1; g.Cin = d->C; g.ldx = d->C;
+    g.Ho = (int)T; g.Wo = 1; g.Cout = Ng;
+    g.kh = g.kw = 1; g.stride = 1; g.pad = 0; g.Kpad = d->C;
+    g.nseg = 1; g.tile = d->tile;
+    g.w_h2 = d->u_h2; g.scale_h2 = d->uinv_h2; g.winv_h2 = d->uinv_h2;
+    g.x_amax = bound; g.x_amax_mul = 100.f;
+    g.seg[0].n0 = 0; g.seg[0].n1 = Ng; g.seg[0].act = YMI_ACT_NONE; g.seg[0].row_stride = Ng;
+    g.seg[0].batch_stride = T * Ng; g.seg[0].ptr = d->M;
+    if (planes)
+      rc = ymi_internal_grouped_gemm(&g, 36, T * d->C, cout_pad * d->C, T * Ng, exe, 6, s, d->V, (unsigned)(T * d->C * 2),
+                                     2L * T * d->C * 2, (unsigned)cout_pad);
+    else
+      rc = ymi_internal_grouped_gemm(&g, 36, T * d->C, cout_pad * d->C, T * Ng, exe, 6, s, nullptr, 0, 0, (unsigned)cout_pad);
+  }
+  if (rc) return rc;
+  if (d->nseg > 0) {
+    SegTab st;
+    st.nseg = d->nseg;
+    for (int k = 0; k < 3; ++k) st.seg[k] = d->seg[k];
+    hipLaunchKernelGGL(wino43_out_seg_k<LevTab>, dim3(grid_for(T * N4)), dim3(256), 0, s, d->M, st, d->scale, d->bias, 0, 0, N4, d->Cout,
+                       0, 0, T, T * N4, d->y_amax, lt);
+  } else {
+    float *noy = nullptr;
+    hipLaunchKernelGGL(wino43_out_k<LevTab>, dim3(grid_for(T * N4)), dim3(256), 0, s, d->M, noy, d->scale, d->bias, 0, 0, N4, 0, 0, T,
+                       d->act, T * N4, noy, lt);
+  }
+  rc = ymi_launch_status();
+  ymi_internal_prof_end(outer, s);
+  for (int i = 0; rc == YMI_OK && i < d->nabs; ++i) {      // the layers this launch absorbed keep their places in the profile
+    const int pr = ymi_internal_prof_begin(d->abs_flops[i], d->tile, 12, s);
+    ymi_internal_prof_end(pr, s);
+  }
+  return rc;
+}
+
 extern "C" int ymi_conv3x3_winograd_f32(const ymi_wino_desc *d, void *stream) {
+  if (d && d->nlev != 0) return wino_levels(d, (hipStream_t)stream);
   if (!d || (!d->x && !d->x_up) || !d->u || !d->V || !d->M) return YMI_ENULL;
   if (d->x_up && (d->m != 4 || (d->H & 1) || (d->W & 1) || (((uintptr_t)d->x_up) & 15))) return YMI_ESHAPE;   // fused 2x upsampling: F(4x4) only
   if (d->B <= 0 || d->H <= 0 || d->W <= 0 || d->C <= 0 || d->Cout <= 0 || d->nseg < 0 || d->nseg > 3) return YMI_EARG;
@@ -693,10 +878,10 @@ extern "C" int ymi_conv3x3_winograd_f32(const ymi_wino_desc *d, void *stream) {
 #endif
   if (mt == 4) {
     if (d->x_up) {
-      if (planes) hipLaunchKernelGGL((wino43_in_k<true, true>), dim3(grid_for(T * C4)), dim3(256), 0, s, d->x_up, d->V, d->H, d->W, C4, th, tw, T, T * C4, d->x_amax, d->up_relu);
-      else hipLaunchKernelGGL((wino43_in_k<false, true>), dim3(grid_for(T * C4)), dim3(256), 0, s, d->x_up, d->V, d->H, d->W, C4, th, tw, T, T * C4, d->x_amax, d->up_relu);
-    } else if (planes) hipLaunchKernelGGL((wino43_in_k<true, false>), dim3(grid_for(T * C4)), dim3(256), 0, s, d->x, d->V, d->H, d->W, C4, th, tw, T, T * C4, d->x_amax, 0);
-    else hipLaunchKernelGGL((wino43_in_k<false, false>), dim3(grid_for(T * C4)), dim3(256), 0, s, d->x, d->V, d->H, d->W, C4, th, tw, T, T * C4, d->x_amax, 0);
+      if (planes) hipLaunchKernelGGL((wino43_in_k<true, true>), dim3(grid_for(T * C4)), dim3(256), 0, s, d->x_up, d->V, d->H, d->W, C4, th, tw, T, T * C4, d->x_amax, d->up_relu, NoLev{});
+      else hipLaunchKernelGGL((wino43_in_k<false, true>), dim3(grid_for(T * C4)), dim3(256), 0, s, d->x_up, d->V, d->H, d->W, C4, th, tw, T, T * C4, d->x_amax, d->up_relu, NoLev{});
+    } else if (planes) hipLaunchKernelGGL((wino43_in_k<true, false>), dim3(grid_for(T * C4)), dim3(256), 0, s, d->x, d->V, d->H, d->W, C4, th, tw, T, T * C4, d->x_amax, 0, NoLev{});
+    else hipLaunchKernelGGL((wino43_in_k<false, false>), dim3(grid_for(T * C4)), dim3(256), 0, s, d->x, d->V, d->H, d->W, C4, th, tw, T, T * C4, d->x_amax, 0, NoLev{});
   } else {
     if (planes) hipLaunchKernelGGL(wino_in_k<true>, dim3(grid_for(T * C4)), dim3(256), 0, s, d->x, d->V, d->H, d->W, C4, th, tw, T, T * C4, d->x_amax);
     else hipLaunchKernelGGL(wino_in_k<false>, dim3(grid_for(T * C4)), dim3(256), 0, s, d->x, d->V, d->H, d->W, C4, th, tw, T, T * C4, d->x_amax);
@@ -736,8 +921,8 @@ extern "C" int ymi_conv3x3_winograd_f32(const ymi_wino_desc *d, void *stream) {
     st.nseg = d->nseg;
     for (int k = 0; k < 3; ++k) st.seg[k] = d->seg[k];
     if (mt == 4)
-      hipLaunchKernelGGL(wino43_out_seg_k, dim3(grid_for(T * N4)), dim3(256), 0, s, d->M, st, d->scale, d->bias, d->H, d->W,
-                         N4, d->Cout, th, tw, T, T * N4, d->y_amax);
+      hipLaunchKernelGGL(wino43_out_seg_k<NoLev>, dim3(grid_for(T * N4)), dim3(256), 0, s, d->M, st, d->scale, d->bias, d->H, d->W,
+                         N4, d->Cout, th, tw, T, T * N4, d->y_amax, NoLev{});
     else
       hipLaunchKernelGGL(wino_out_seg_k, dim3(grid_for(T * N4)), dim3(256), 0, s, d->M, st, d->scale, d->bias, d->H, d->W, N4,
                          d->Cout, th, tw, T, T * N4, d->y_amax);
@@ -761,8 +946,8 @@ extern "C" int ymi_conv3x3_winograd_f32(const ymi_wino_desc *d, void *stream) {
     return rc;
   }
   if (mt == 4)
-    hipLaunchKernelGGL(wino43_out_k, dim3(grid_for(T * N4)), dim3(256), 0, s, d->M, d->y, d->scale, d->bias, d->H, d->W, N4, th,
-                       tw, T, d->act, T * N4, d->y_amax);
+    hipLaunchKernelGGL(wino43_out_k<NoLev>, dim3(grid_for(T * N4)), dim3(256), 0, s, d->M, d->y, d->scale, d->bias, d->H, d->W, N4, th,
+                       tw, T, d->act, T * N4, d->y_amax, NoLev{});
   else
     hipLaunchKernelGGL(wino_out_k, dim3(grid_for(T * N4)), dim3(256), 0, s, d->M, d->y, d->scale, d->bias, d->H, d->W, N4, th,
                        tw, T, d->act, T * N4, d->y_amax);

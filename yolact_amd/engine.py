@@ -474,6 +474,7 @@ class Plan(PlanTuning):       # (plan_tune.py: tune() and everything it needs, t
         self._sk_ws = {}
         self.down_on_side_stream = os.environ.get('YOLACT_AMD_DOWN_STREAM', 'B') == 'B'      # measured +1 %
         self.wino_alt, self._wino_packed, self._wino_ws = {}, {}, {}
+        self.level_merge, self.merged_levels = None, False     # P4..P7 heads as one Winograd layer per shared conv (_build_level_merge)
         self._upsrc, self.wino_up = {}, {}     # 2x bilinear upsampling feeding a 3x3 conv: fused into its F(4x4) input transform
         self._done_event = None
         self._priors_timed = False
@@ -652,6 +653,90 @@ class Plan(PlanTuning):       # (plan_tune.py: tune() and everything it needs, t
             ws = self._wino_ws[self.ops[idx][3]]
             for d in alts:
                 d.V, d.M = ws[0].data_ptr(), ws[1].data_ptr()
+        if self.level_merge is not None:
+            ws = self._wino_ws[self.level_merge['where']]
+            for d in self.level_merge['descs']:
+                d.V, d.M = ws[0].data_ptr(), ws[1].data_ptr()
+
+    # ---- the P4..P7 prediction heads as ONE Winograd layer per shared conv ---------------------------------------------------------------
+    # share_prediction_module: every level applies the same up-feature conv and the same bbox | coef | conf conv, on maps of 35^2 .. 5^2
+    # whose launches hold a handful of blocks each (18 launches, 7 % of a serial batch-8 step for 4 % of its FLOPs).  In the Winograd
+    # domain the levels are just more rows of the grouped GEMM: ymi_wino_desc.nlev runs one input transform, one GEMM and one output
+    # transform over the tiles of all of them (csrc/winograd.hip).  Built here as an ALTERNATIVE, like wino_alt: the op list stays the
+    # per-level one, PlanTuning._merge_levels installs the two merged launches where they measured faster (YOLACT_AMD_MERGE_LEVELS).
+    # The merged up-feature writes every level's output at once, so those get buffers of their own (the arena hands the per-level
+    # launches the same buffer again and again); all levels raise ONE bound slot, which is the merged .out launch's input bound.
+    def _build_level_merge(self, lev_ops, up_pk, head_pk, offs, widths, ncols, coef_act):
+        self.level_merge = None
+        self.merged_levels = False
+        lv = sorted(l for l in lev_ops if l >= 1)
+        if not (self.h2 and 2 <= len(lv) <= 5 and len(up_pk) == 1 and all(len(lev_ops[l]) == 3 for l in lv)):
+            return
+        pku = up_pk[0]
+        if not all((pk.kh, pk.kw, pk.stride, pk.pad) == (3, 3, 1, 1) and pk.weight_oihw is not None and pk.Cin % 32 == 0
+                   and not getattr(pk, 'wide', False) for pk in (pku, head_pk)) or pku.Cout % 32 != 0:
+            return
+        if any(i in self.wide_ops for l in lv for i in lev_ops[l][1:]):
+            return
+        feats = [lev_ops[l][0] for l in lv]
+        B = feats[0].B
+        Tn = sum(B * _ceil(f.H, 4) // 4 * (_ceil(f.W, 4) // 4) for f in feats)
+        if Tn * max(pku.Cin, pku.Cout, _ceil(head_pk.Cout, 4)) >= (1 << 29):
+            return
+        ws = self._wino_ws.setdefault(self._cur, [None, None])
+        need_v, need_m = 36 * Tn * max(pku.Cin, pku.Cout), 36 * Tn * max(pku.Cout, _ceil(head_pk.Cout, 4))
+        if ws[0] is None or ws[0].numel() < need_v:
+            ws[0] = torch.empty(need_v, dtype=torch.float32, device=self.device)
+        if ws[1] is None or ws[1].numel() < need_m:
+            ws[1] = torch.empty(need_m, dtype=torch.float32, device=self.device)
+        mid = [torch.empty(B * f.H * f.W * pku.Cout, dtype=torch.float32, device=self.device) for f in feats]
+        uslot, pubslot = self._slot(), self._slot()
+
+        def base(pk, act):
+            key = (id(pk), 4)
+            wp = self._wino_packed.get(key)
+            if wp is None:
+                wp = self._wino_packed[key] = WinoPacked(pk.weight_oihw, self.device, 4)
+            d = L.WinoDesc()
+            d.u = wp.u.data_ptr()
+            planes, uinv = wp.h2()
+            d.u_h2, d.uinv_h2 = planes.data_ptr(), uinv.data_ptr()
+            d.scale = pk.scale.data_ptr() if pk.scale is not None else None
+            d.bias = pk.bias.data_ptr() if pk.bias is not None else None
+            d.B, d.C, d.Cout, d.act, d.m, d.cout_alg = B, pk.Cin, pk.Cout, act, 4, pk.cout_alg
+            d.tile, d.v_planes, d.nlev = L.TILE_128x128 | L.TILE_H2, 1, len(lv)
+            for q, f in enumerate(feats):
+                d.lev[q].H, d.lev[q].W = f.H, f.W
+            d.H, d.W = 4 * (Tn // B), 4           # ignored by the launch: the virtual shape of its table key (tune_table.level_key)
+            return d
+        du = base(pku, L.ACT_RELU)
+        du.lev_amax = self._slot_ptr(pubslot)
+        for q, f in enumerate(feats):
+            assert f.slot is not None
+            du.lev[q].x, du.lev[q].x_amax = f.ptr, self._slot_ptr(f.slot)
+            du.lev[q].y, du.lev[q].y_amax = mid[q].data_ptr(), self._slot_ptr(uslot)
+        do = base(head_pk, L.ACT_NONE)
+        d1 = self.ops[lev_ops[lv[0]][2]][1].contents            # head1.out's direct descriptor: segments and bound slots
+        do.nseg, do.y_amax = d1.nseg, d1.y_amax
+        off1 = offs[lv[0]]
+        for k in range(d1.nseg):
+            do.seg[k] = d1.seg[k]                               # (ptr = level 1's rows of the level-concatenated tensor)
+        for q, l in enumerate(lv):
+            do.lev[q].x, do.lev[q].x_amax = mid[q].data_ptr(), self._slot_ptr(uslot)
+            for k in range(d1.nseg):
+                do.lev[q].seg_off[k] = (offs[l] - off1) * widths[k] * 4
+        # profile records map onto conv_meta by position: head1's two layers carry the launches, the absorbed ones follow as kind 12
+        absorbed = []
+        for l in lv[1:]:
+            for i in lev_ops[l][1:]:
+                absorbed.append(self.lib.ymi_conv_flops(C.byref(self.ops[i][1].contents)))
+        do.nabs = len(absorbed)
+        for q, fl in enumerate(absorbed):
+            do.abs_flops[q] = fl
+        self.keepalive += [mid, du, do]
+        self.level_merge = {'where': self._cur, 'descs': (du, do), 'levels': lv, 'tiles': Tn // B,
+                            'up': [lev_ops[l][1] for l in lv], 'out': [lev_ops[l][2] for l in lv], 'mid': mid,
+                            'shape': (B, pku.Cin, pku.Cout, head_pk.Cout)}
 
     def call(self, fn, *args, name=''):
         self.ops.append((fn, args, name, self._cur))
@@ -932,14 +1017,18 @@ class Plan(PlanTuning):       # (plan_tune.py: tune() and everything it needs, t
                     if u is not f:
                         self.free(u)
                     u = nu
+                    lev_ops.setdefault(lvl, [f]).append(len(self.ops) - 1)
             segs = [
                 (0, n_b, L.ACT_NONE, n_b, P * 4, self.loc.data_ptr() + off * 4 * 4),
                 (n_b, n_b + n_m, coef_act, n_m, P * D, self.coef.data_ptr() + off * D * 4),
                 (n_b + n_m, n_b + n_m + n_c, L.ACT_NONE, n_c, P * Cp, self.conf.data_ptr() + off * Cp * 4),
             ]
             self.conv('head%d.out' % lvl, u, head_pk, segs=segs)
+            lev_ops.setdefault(lvl, [f]).append(len(self.ops) - 1)
             if u is not f:
                 self.free(u)
+
+        lev_ops = {}       # level -> [input, op index of every up-feature conv ..., op index of the .out conv] (_build_level_merge)
 
         def pred(j):   # pred_layers are stored top-down: index n-1-j belongs to level j (yolact.py:286-289)
             i = n - 1 - j
@@ -966,6 +1055,7 @@ class Plan(PlanTuning):       # (plan_tune.py: tune() and everything it needs, t
         self.on('B')
         for lvl in range(1, nlev):
             head(lvl, feats_b[lvl - 1])
+        self._build_level_merge(lev_ops, up_pk, head_pk, offs, (4, D, Cp), (n_b, n_m, n_c), coef_act)
         self.wait('head0')
         for f in feats_b:
             self.free(f)

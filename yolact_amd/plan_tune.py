@@ -121,6 +121,7 @@ class PlanTuning:
         measure = mode != 'table'
         self._tune_direct(e0, e1, s, reps, disk, measure)
         self._tune_winograd(e0, e1, s, reps, disk, measure)
+        self._merge_levels(e0, e1, s, reps, disk, measure)
         self._fuse_pointwise_chains(e0, e1, s, reps, disk, measure)
         torch.cuda.synchronize(self.device)
         if cache_path and (len(disk) != n0 or mode == 'force'):
@@ -689,11 +690,8 @@ class PlanTuning:
                 self.tune_table.append((name, cname(best), times))
             self._apply_choice(fn, dptr, where, cache[key], s)
 
-    def _tune_winograd(self, e0, e1, s, reps, disk, measure):
-        """Per eligible layer: best GEMM tile of the Winograd path, then Winograd vs the (already tuned) direct kernel.
-        The winner replaces the op in the list."""
-        lib = self.lib
-        self.wino_toggle = {}       # table key -> [(op index, direct op, Winograd op, isolated timing favours Winograd)]: tools/instep_tune.py
+    def _wino_gemm_tiles(self):
+        """Winograd choices (GEMM tile, V planes) the tuner measures for a layer of this plan's arithmetic."""
         wtiles = [L.TILE_64x64, L.TILE_64x128, L.TILE_128x64, L.TILE_128x128_W8, L.TILE_64x128_S3, L.TILE_32x64_K2,
                   L.TILE_128x128, L.TILE_128x128_S3, L.TILE_128x128_W8_S3, L.TILE_256x128_W8, L.TILE_256x128_W8_S3]
         if self.split:
@@ -703,6 +701,104 @@ class PlanTuning:
             wtiles = wtiles + [t | L.TILE_H2 for t in hb] + [TT.wino_choice(t | L.TILE_H2, planes=1) for t in hb]
             if os.environ.get('YOLACT_AMD_WGEMM', '1') == '1':       # round 6: the persistent producer / consumer grouped GEMM (planes only)
                 wtiles = wtiles + [TT.wino_choice(L.TILE_WG_128x256 | L.TILE_H2, planes=1)]
+        return wtiles
+
+    def level_merge_keys(self):
+        """Table keys of the merged P4..P7 head launches (engine.Plan._build_level_merge): the VIRTUAL Winograd shapes of
+        tune_table.level_key, (merged up-feature, merged .out); None where the plan has no such alternative."""
+        lm = self.level_merge
+        if lm is None:
+            return None
+        B, Cin, Cup, Chead = lm['shape']
+        return (TT.level_key(B, lm['tiles'], Cin, Cup, L.ACT_RELU, 0, self.mode),
+                TT.level_key(B, lm['tiles'], Cup, Chead, L.ACT_NONE, lm['descs'][1].nseg, self.mode))
+
+    def install_level_merge(self, choices=None):
+        """Replace head1.up0 / head1.out by the merged launches (Winograd choices `choices`, default the descriptors' own) and turn
+        the per-level launches of the other levels into nops.  Pure op-list surgery: works on a dry CPU plan.  conv_meta keeps every
+        entry: the merged launches are recorded as head1's layers, the absorbed ones as kind 12 behind them (ymi_wino_desc.nabs)."""
+        lm = self.level_merge
+        if lm is None or self.merged_levels:
+            return self.merged_levels
+        conv = self.lib.ymi_conv2d_nhwc_f32
+        wino = self.lib.ymi_conv3x3_winograd_f32
+        if not all(self.ops[i][0] in (conv, wino) for i in lm['up'] + lm['out']):
+            return False
+        for d, v in zip(lm['descs'], choices or ()):
+            _set_wino_choice(d, v)
+        for d, idxs in zip(lm['descs'], (lm['up'], lm['out'])):
+            _, _, name, where = self.ops[idxs[0]]
+            name = name.replace('[wino]', '')
+            self.ops[idxs[0]] = (wino, C.pointer(d), name + '[levels %d-%d][wino]' % (lm['levels'][0], lm['levels'][-1]), where)
+            for i in idxs[1:]:
+                _, _, n_i, w_i = self.ops[i]
+                self.ops[i] = ('nop', None, n_i.replace('[wino]', '') + '[merged into ' + name + ']', w_i)
+        self.merged_levels = True
+        return True
+
+    def _merge_levels(self, e0, e1, s, reps, disk, measure):
+        """The P4..P7 prediction heads as ONE Winograd layer per shared conv (engine.Plan._build_level_merge, ymi_wino_desc.nlev),
+        installed where the two merged launches measured faster than the per-level launches they replace (each level's tuned best:
+        called after _tune_direct / _tune_winograd).  Two entries under the virtual shapes of tune_table.level_key:
+        [4, Winograd choice of the merged GEMM, summed ms of the per-level launches, ms of the merged launch, 0, the same].
+        YOLACT_AMD_MERGE_LEVELS = 1 (default) | 0 (keep the per-level launches) | force (install it whatever the table says).
+        The descriptors' own (H, W) hold the virtual shape of their key (the library ignores them with a table): same B, C, Cout,
+        tile and the same T, i.e. the GEMM shape the fp64 pin of that table key launches (tests/test_gpu_winograd_kat.py)."""
+        self.level_table = []
+        mode = os.environ.get('YOLACT_AMD_MERGE_LEVELS', '1')
+        lm = self.level_merge
+        if lm is None or mode not in ('1', 'force') or not self.use_winograd or 4 not in self.wino_variants:
+            return
+        if self.wino_force and mode != 'force':     # YOLACT_AMD_WINOGRAD_FORCE: every eligible layer on its OWN Winograd launches
+            return
+        lib = self.lib
+        keys = self.level_merge_keys()
+        ents = []
+        for key, d, idxs in zip(keys, lm['descs'], (lm['up'], lm['out'])):
+            ent = disk.get(key)
+            if ent is not None and ent[1]:          # validate the stored tile with one launch
+                _set_wino_choice(d, ent[1])
+                if lib.ymi_conv3x3_winograd_f32(C.byref(d), s) != 0:
+                    ent = None
+            if ent is None:
+                self.tune_misses += 1
+                if not measure:
+                    ents.append(None)
+                    continue
+                t_plan = sum(_timed((lambda f=self.ops[i][0], a=self.ops[i][1]: f(a, s)), e0, e1, reps) for i in idxs)
+                best_t, best_ms = 0, 1e30
+                dptr = C.pointer(d)
+                for t in self._wino_gemm_tiles():
+                    if not (TT.wino_parts(t)[0] & L.TILE_H2):
+                        continue
+                    _set_wino_choice(d, t)
+                    if lib.ymi_conv3x3_winograd_f32(dptr, s) != 0:
+                        continue
+                    ms = _timed(lambda: lib.ymi_conv3x3_winograd_f32(dptr, s), e0, e1, reps)
+                    if ms < best_ms:
+                        best_t, best_ms = t, ms
+                ent = disk[key] = [4 if best_t else 0, best_t, round(t_plan, 4), round(best_ms if best_t else 0.0, 4), 0.0,
+                                   round(best_ms if best_t else 0.0, 4)]
+            ents.append(ent)
+        torch.cuda.synchronize(self.device)
+        ok = all(e is not None and e[1] for e in ents)
+        if ok:
+            t_plan, t_one = sum(e[2] for e in ents), sum(e[3] for e in ents)
+            self.level_table = [(k, e[1], e[2], e[3]) for k, e in zip(keys, ents)]
+            if mode == 'force' or t_one < 0.97 * t_plan:
+                self.install_level_merge([e[1] for e in ents])
+        elif mode == 'force':
+            for d in lm['descs']:
+                d.tile, d.v_planes = L.TILE_128x128 | L.TILE_H2, 1
+            if all(lib.ymi_conv3x3_winograd_f32(C.byref(d), s) == 0 for d in lm['descs']):
+                self.install_level_merge()
+
+    def _tune_winograd(self, e0, e1, s, reps, disk, measure):
+        """Per eligible layer: best GEMM tile of the Winograd path, then Winograd vs the (already tuned) direct kernel.
+        The winner replaces the op in the list."""
+        lib = self.lib
+        self.wino_toggle = {}       # table key -> [(op index, direct op, Winograd op, isolated timing favours Winograd)]: tools/instep_tune.py
+        wtiles = self._wino_gemm_tiles()
         memo = {}
         for idx, alts in sorted(self.wino_alt.items()):
             fn, dptr, name, where = self.ops[idx]

@@ -8,6 +8,7 @@
                    chain (B, H, W, 64): the ENTRY form of the 64-plane pair (the block's projection shortcut computed inside the pair
                    launch, csrc/chain.hip) -> [1 | 0, ms of the shortcut launch + the pair launch, ms of the entry launch]; the pair's
                    own decision stays under chain (B, H, W), which never spells P for 64 planes
+                   wino (B, 4 * tiles, 4, ...): a merged P4..P7 head launch, see level_key
            instep|<wino key>                                                      -> 0: keep the direct kernel (tools/instep_tune.py)
     value  direct choice   = tile id + 256 * split_k (split_k 0 = unsplit)
            Winograd choice = GEMM tile id (+ WINO_PLANES: V written as fp16x2 planes)
@@ -141,6 +142,17 @@ def desc_key(d, mode='', dcn=False):
 
 def wino_key(B, H, W, C, Cout, act, nseg, ms, mode=''):
     return format('wino', (B, H, W, C, Cout, act, nseg, tuple(ms)), mode)
+
+
+def level_key(B, tiles, C, Cout, act, nseg, mode=''):
+    """The key of a merged P4..P7 head launch (ymi_wino_desc.nlev: several feature maps, one Winograd layer).  No kind of its own:
+    a wino key of a VIRTUAL shape no real layer has, (H, W) = (4 * F(4x4) tiles per image over all levels, 4), m = (4,).  Its value
+    reads [4 | 0, Winograd choice of the merged GEMM, summed ms of the per-level launches it replaces (where a real layer has its
+    direct ms), ms of the merged launch, 0, the same]; the merged form is installed where both entries of a plan (up-feature and
+    .out) hold a choice and their merged times sum to less than 0.97 of the per-level sums.  A single map of the virtual shape has
+    the merged launch's T = B * tiles GEMM rows, so whatever launches the key as an ordinary layer (the fp64 pin of every shipped
+    Winograd entry) runs the merged launch's GEMM shape on its tile."""
+    return wino_key(B, 4 * int(tiles), 4, C, Cout, act, nseg, (4,), mode)
 
 
 def chain_key(kind, B, H, W, P=None, mode=''):
